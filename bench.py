@@ -3,6 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload mobi_nusc_512|mobi_nusc_256]
                     [--objects B] [--dtype bf16|fp16] [--cfg-scale S] [--e2e] [--no-cpu-baseline]
+                    [--dump-outputs DIR]
 
 A "step" is one DDIM denoising step of the whole per-GPU batch: UNet forward on
 2*B interleaved camera/lidar elements (4*B with classifier-free guidance) plus the fp32
@@ -52,6 +53,26 @@ PARITY_FILES = ("gpurun_out/parity_last.json", "profiles/r05_parity.json")
 # GPU drops its clocks (profiles/r05_e2e_idle_gap.txt): ~0.15 s of steps bring them back (x 4 at the 32 x 32 latent, whose step is 6 ms)
 SUB_WARMUP_STEPS = 8
 NORTH_STAR_REL_L2 = 1e-3
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write every tensor of `arrays` as out_dir/<name>.npy in float32, so that two builds can be compared
+    output for output.  An array over its share of DUMP_LIMIT_BYTES is replaced by a fixed, seeded sample of its
+    elements (flattened, indices in increasing order).  Returns {name: {"shape", "dumped"}} for the result line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays)) // 4
+    written = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        dumped = "all"
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+            dumped = f"seeded sample of {share} elements"
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+        written[name] = {"shape": list(t.shape), "dumped": dumped}
+    return written
 
 
 def lib_sha16():
@@ -156,7 +177,7 @@ def stub_main(args, world, rank):
     if world > 1:                                 # sleeps below, not thread contention, must decide the per-rank times
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group(backend=os.environ.get("MOBI_BENCH_BACKEND", "gloo"))
-    a = torch.randn(64, 64)
+    a = torch.randn(64, 64, generator=torch.Generator().manual_seed(1234 + rank))
 
     def barrier():
         if world > 1:
@@ -191,6 +212,8 @@ def stub_main(args, world, rank):
         if world > 1:
             line.update(ranks_seen=dist.get_world_size(), backend=dist.get_backend(), ranks=ranks,
                         ms_per_step_by_rank=[r["ms_per_step"] for r in ranks])
+        if args.dump_outputs:
+            line["outputs_dumped"] = dump_outputs(args.dump_outputs, {"a": a})
         print(json.dumps(line))
     if world > 1:
         dist.destroy_process_group()
@@ -209,6 +232,9 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--dump-launches", default=None, help="write per-launch (kind, GFLOP, us) records of one step")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step handed its caller "
+                    "(p_sample_ddim's x_prev and pred_x0, rank 0) as DIR/<name>.npy in float32; the inputs are seeded, so "
+                    "two builds run with the same arguments can be compared output for output")
     ap.add_argument("--cpu-threads", type=int, default=32, help="threads for the CPU-oracle baseline leg")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end objects/s pass")
     ap.add_argument("--no-graph", action="store_true", help="issue every launch from the host (no HIP graph)")
@@ -218,6 +244,8 @@ def main():
     ap.add_argument("--no-config-lines", action="store_true", help="skip the sub-records of BASELINE configs 2 and 5 "
                     "(`nusc256`: mobi_nusc_256, 4 objects, 32 x 32, DDIM-50, bf16; `ddim250_fp16`: the DDIM-250 / fp16 per-rank workload)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
@@ -278,9 +306,8 @@ def main():
         index = total - 1 - (i % total)
         step = int(steps_desc[i % total])
         ts = torch.full((N,), step, device=device, dtype=torch.long)
-        x, _ = sampler.p_sample_ddim(x, cond, ts, index=index, unconditional_guidance_scale=args.cfg_scale,
-                                     unconditional_conditioning=uc if cfg else None, step_value=step, **kw)
-        return x
+        return sampler.p_sample_ddim(x, cond, ts, index=index, unconditional_guidance_scale=args.cfg_scale,
+                                     unconditional_conditioning=uc if cfg else None, step_value=step, **kw)   # x_prev, pred_x0
 
     def barrier():
         if world > 1:
@@ -290,13 +317,13 @@ def main():
     with torch.no_grad():
         x = img
         for i in range(args.warmup):
-            x = one_step(x, i)
+            x, _ = one_step(x, i)
         barrier()
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0 = time.perf_counter()
         ev0.record()
         for i in range(args.steps):
-            x = one_step(x, args.warmup + i)
+            x, pred_x0 = one_step(x, args.warmup + i)
         ev1.record()
         t_issued = time.perf_counter() - t0            # host time to issue K steps (the GPU may still be running)
         torch.cuda.synchronize()
@@ -319,6 +346,9 @@ def main():
         ranks = [None] * world
         dist.all_gather_object(ranks, mine)
     finite = bool(torch.isfinite(x).all())
+    dumped = None
+    if args.dump_outputs and rank == 0:                 # the last timed step's outputs, before anything else runs a step
+        dumped = dump_outputs(args.dump_outputs, {"x_prev": x, "pred_x0": pred_x0})
 
     # ---- the shipped invocation (scripts/realism_test_bench.sh:95-102): PLMS, classifier-free guidance 5 -------
     plms_line = None
@@ -803,6 +833,8 @@ def main():
             "model_frac_of_peak": round(value * useful_gf / 1e3 / world / PEAK_TFLOPS, 4),
             "finite": finite,
         }
+        if dumped:
+            out["outputs_dumped"] = dumped
         if objects_per_s is not None:
             out["objects_per_s"] = round(objects_per_s, 4)
             out["objects_per_s_first_pass"] = round(objects_per_s_first, 4)

@@ -3,6 +3,7 @@ ctypes struct layouts match, and the product path refuses to run without a GPU (
 import ctypes as C
 import os
 import re
+import sys
 
 import pytest
 import torch
@@ -277,19 +278,22 @@ CONFIGS = ["mobi_nusc-mini_256", "mobi_nusc-mini_512", "mobi_nusc_256", "mobi_nu
            "mobi_nusc_all-classes_512", "range_autoencoder", "pbe"]
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/configs/mobi_nusc_512.yaml"), reason="reference tree not present")
 @pytest.mark.parametrize("name", CONFIGS)
 def test_restated_configs_equal_the_reference(name):
     """configs/*.yaml (the files the GPU box can name) hold exactly the values of the reference's YAML files, before
-    and after `${}` resolution, and the reference's own files load through the engine's loader."""
+    and after `${}` resolution: tests/golden/reference_interfaces.json keeps the sha256 of the reference files' parsed
+    values and of what the engine's loader made of them (tests/golden/make_reference_interfaces.py)."""
+    import json
     import yaml
     from mobi_amd.ldm.util import load_config
-    with open(f"/root/reference/configs/{name}.yaml") as f:
-        ref_raw = yaml.safe_load(f)
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    from make_reference_interfaces import digest
+    with open(os.path.join(ROOT, "tests", "golden", "reference_interfaces.json")) as f:
+        ref = json.load(f)["configs"][name]
     with open(os.path.join(ROOT, "configs", f"{name}.yaml")) as f:
         mine_raw = yaml.safe_load(f)
-    assert mine_raw == ref_raw
-    assert load_config(os.path.join(ROOT, "configs", f"{name}.yaml")) == load_config(f"/root/reference/configs/{name}.yaml")
+    assert digest(mine_raw) == ref["raw_sha256"]
+    assert digest(load_config(os.path.join(ROOT, "configs", f"{name}.yaml"))) == ref["resolved_sha256"]
 
 
 @pytest.mark.parametrize("name", [c for c in CONFIGS if c.startswith("mobi_")])

@@ -74,3 +74,25 @@ def test_single_process_default():
                        capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr[-2000:]
     assert _line(r.stdout)["n_gpus"] == 1
+
+
+def test_dump_outputs_and_step_count(tmp_path):
+    """`--dump-outputs DIR` writes the last timed step's result as float32 .npy files, the same from run to run (seeded
+    inputs); `--steps` is the number of timed steps the line's ms_per_step divides by, and fewer than one is refused."""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)],
+                           env=_env(), capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = _line(r.stdout)
+        assert out["steps"] == 3 and out["ms_per_step"] >= 1.9                   # the stub sleeps 2 ms per timed step
+        assert out["outputs_dumped"] == {"a": {"shape": [64, 64], "dumped": "all"}}
+        a = np.load(d / "a.npy")
+        assert a.dtype == np.float32 and a.shape == (64, 64) and np.isfinite(a).all()
+        dumps.append(a)
+    assert np.array_equal(dumps[0], dumps[1])
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], env=_env(), capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode != 0 and "--steps" in r.stderr

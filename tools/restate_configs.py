@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Writes configs/*.yaml: the hyper-parameter VALUES of the reference's config files (parsed, re-emitted in this repo's
 own formatting; `${}` interpolations kept as they are), so that BASELINE.json's five configs can be named on the GPU
-box, where /root/reference does not exist.  tests/test_dropin_cpu.py checks value equality against the reference files
-whenever they are present.      python tools/restate_configs.py [/root/reference/configs]"""
+box, where /root/reference does not exist.  tests/test_abi_cpu.py checks value equality against digests of the reference
+files (tests/golden/reference_interfaces.json, tests/golden/make_reference_interfaces.py).
+    python tools/restate_configs.py [/root/reference/configs]"""
 import os
 import sys
 
