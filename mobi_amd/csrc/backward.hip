@@ -845,7 +845,9 @@ __global__ __launch_bounds__(256) void groupnorm_bwd_kernel(const T* __restrict_
 // GNB_PIX pixels of one image with ALL channels: thread (piece, r) keeps one 8-channel piece (16-byte loads) and walks the
 // chunk's pixels r, r + R, ...; per-channel sums go through LDS in a fixed order to partial[image][chunk][k][C]; a small
 // kernel folds them per (image, group) -- fixed order everywhere: bit-reproducible.
-//   pass 1: sum x, sum x^2            -> mean, rstd
+//   pass 1: sum x - k, sum (x - k)^2  -> mean, rstd   (k: the group's first element, x[image][0][first channel], loaded by every
+//                                                     block: fp32 sums of x and x^2 lose the variance of a group whose mean
+//                                                     is large against its spread; a constant group's sums are exactly zero)
 //   pass 2: sum dxh, sum dxh xh       -> m1, m2         (dxh = dy act'(z) gamma, xh = (x - mean) rstd)
 //   pass 3: dx = rstd (dxh - m1 - xh m2) (+ dx_add)
 constexpr int GNB_PIX = 256;
@@ -858,6 +860,12 @@ struct GnbArgs {
   int hw, C, chunks, silu;
   float eps;
 };
+
+// the shift of group g of image img for pass 1's sums (the group's first channel at pixel 0)
+template <typename T>
+__device__ __forceinline__ float gnb_shift(const GnbArgs& a, int img, int g) {
+  return (float)reinterpret_cast<const T*>(a.x)[(long long)img * a.hw * a.C + g * (a.C / 32)];
+}
 
 template <typename T, int PASS>
 __global__ __launch_bounds__(256) void gnb_pass_kernel(const GnbArgs a) {
@@ -879,16 +887,20 @@ __global__ __launch_bounds__(256) void gnb_pass_kernel(const GnbArgs a) {
       ga[j] = a.gamma[c]; be[j] = a.beta[c];
     }
   }
-  float s0[8], s1[8];
+  float s0[8], s1[8], k[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) { s0[j] = 0.f; s1[j] = 0.f; }
+  for (int j = 0; j < 8; ++j) { s0[j] = 0.f; s1[j] = 0.f; k[j] = 0.f; }
+  if (PASS == 1 && active) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) k[j] = gnb_shift<T>(a, img, (piece * 8 + j) / G);
+  }
   if (active) {
     for (int p = p0 + r; p < p1; p += R) {
       float xv[8];
       unpack8<T>(ld16(xp + (long long)p * C), xv);
       if (PASS == 1) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { s0[j] += xv[j]; s1[j] += xv[j] * xv[j]; }
+        for (int j = 0; j < 8; ++j) { const float d = xv[j] - k[j]; s0[j] += d; s1[j] += d * d; }
       } else {
         float dv[8];
         unpack8<T>(ld16(dyp + (long long)p * C), dv);
@@ -933,10 +945,10 @@ __global__ __launch_bounds__(256) void gnb_pass_kernel(const GnbArgs a) {
 }
 
 // one wave per (image, group): fold the chunk partials of the group's channels (fixed order), write the statistics
-template <int PASS>
+template <typename T, int PASS>
 __global__ __launch_bounds__(64) void gnb_fold_kernel(const GnbArgs a) {
-  // (the chunk partials meet in fp64, as in the forward's two-launch form (csrc/norm.hip, gn_apply_kernel): E[x^2] - mean^2 of
-  //  a group whose mean is large against its spread then loses the partials' fp32 rounding only, not the difference's)
+  // (the chunk partials meet in fp64, as in the forward's two-launch form (csrc/norm.hip, gn_apply_kernel); pass 1's partials are
+  //  sums of x - k, so mean = k + S / n and var = Q / n - (S / n)^2 keep the spread of a group whose mean is large against it)
   const int g = blockIdx.x, img = blockIdx.y, lane = threadIdx.x, G = a.C / 32;
   double t0 = 0.0, t1 = 0.0;
   for (int i = lane; i < a.chunks * G; i += 64) {
@@ -954,10 +966,10 @@ __global__ __launch_bounds__(64) void gnb_fold_kernel(const GnbArgs a) {
     float* st = a.stats + ((long long)img * 32 + g) * 4;
     const double inv_m = 1.0 / ((double)G * (double)a.hw);
     if (PASS == 1) {
-      const double mean = t0 * inv_m;
-      double var = t1 * inv_m - mean * mean;
+      const double d = t0 * inv_m;
+      double var = t1 * inv_m - d * d;
       var = var < 0.0 ? 0.0 : var;
-      st[0] = (float)mean;
+      st[0] = (float)((double)gnb_shift<T>(a, img, g) + d);
       st[1] = (float)(1.0 / sqrt(var + (double)a.eps));
     } else {
       st[2] = (float)(t0 * inv_m);
@@ -1202,15 +1214,15 @@ extern "C" int mobi_groupnorm_bwd(const void* x, const void* dy, const float* ga
     const dim3 gp(a.chunks, images), gf(32, images);
     if (dtype == MOBI_F16) {
       hipLaunchKernelGGL((gnb_pass_kernel<f16_t, 1>), gp, dim3(256), 0, ST(stream), a);
-      hipLaunchKernelGGL((gnb_fold_kernel<1>), gf, dim3(64), 0, ST(stream), a);
+      hipLaunchKernelGGL((gnb_fold_kernel<f16_t, 1>), gf, dim3(64), 0, ST(stream), a);
       hipLaunchKernelGGL((gnb_pass_kernel<f16_t, 2>), gp, dim3(256), 0, ST(stream), a);
-      hipLaunchKernelGGL((gnb_fold_kernel<2>), gf, dim3(64), 0, ST(stream), a);
+      hipLaunchKernelGGL((gnb_fold_kernel<f16_t, 2>), gf, dim3(64), 0, ST(stream), a);
       hipLaunchKernelGGL((gnb_pass_kernel<f16_t, 3>), gp, dim3(256), 0, ST(stream), a);
     } else {
       hipLaunchKernelGGL((gnb_pass_kernel<bf16_t, 1>), gp, dim3(256), 0, ST(stream), a);
-      hipLaunchKernelGGL((gnb_fold_kernel<1>), gf, dim3(64), 0, ST(stream), a);
+      hipLaunchKernelGGL((gnb_fold_kernel<bf16_t, 1>), gf, dim3(64), 0, ST(stream), a);
       hipLaunchKernelGGL((gnb_pass_kernel<bf16_t, 2>), gp, dim3(256), 0, ST(stream), a);
-      hipLaunchKernelGGL((gnb_fold_kernel<2>), gf, dim3(64), 0, ST(stream), a);
+      hipLaunchKernelGGL((gnb_fold_kernel<bf16_t, 2>), gf, dim3(64), 0, ST(stream), a);
       hipLaunchKernelGGL((gnb_pass_kernel<bf16_t, 3>), gp, dim3(256), 0, ST(stream), a);
     }
     MOBI_CHECK_LAUNCH();

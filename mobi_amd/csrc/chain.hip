@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void chain_adapter_image_kernel(const float* _
 }
 
 // GroupNorm (32 groups) of x [image][hw][C] folded to two per-image vectors for MOBI_CH_AFFINE_S: scale = rstd gamma,
-// shift = beta - mean rstd gamma (mean, then the variance about the mean: gn_stats_kernel's arithmetic).  One block per
+// shift = beta - mean rstd gamma (mean, then the variance about the mean, as gn_regs_kernel computes them).  One block per
 // (group, image); a thread reads whole pixels of the group (C / 32 consecutive channels).
 template <typename T>
 __global__ __launch_bounds__(256) void gn_scale_shift_kernel(const T* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -391,7 +391,7 @@ __global__ __launch_bounds__(256, 1) void row_chain_kernel(const mobi_row_chain_
       lgh = mfma32(ah, xs[ks], lgh);
       lgl = mfma32(al, xs[ks], lgl);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) { const float v = (float)xs[ks][j]; sx += v; sxx += v * v; }
+      for (int j = 0; j < 8; ++j) sx += (float)xs[ks][j];
       __builtin_amdgcn_sched_barrier(0);
     }
     // (the PACKED rows are what stays in registers: without the pins the compiler keeps the unpacked floats of the
@@ -402,12 +402,16 @@ __global__ __launch_bounds__(256, 1) void row_chain_kernel(const mobi_row_chain_
       asm volatile("" : "+v"(w));
       xs[ks] = __builtin_bit_cast(frag_t, w);
     }
+    // mean, then the variance about the mean from the register-held row (CH_ROWSTATS' arithmetic): E[x^2] - mean^2 in fp32
+    // loses the spread of a row whose mean is large against it, and gives a constant row a spurious variance
     sx += __shfl_xor(sx, 32, 64);
-    sxx += __shfl_xor(sxx, 32, 64);
     const float mean = sx * (1.0f / CH_C);
-    float var = sxx * (1.0f / CH_C) - mean * mean;
-    var = var < 0.f ? 0.f : var;
-    const float rstd = rsqrtf(var + a.ad_eps);
+#pragma unroll
+    for (int ks = 0; ks < CH_KS; ++ks)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { const float d = (float)xs[ks][j] - mean; sxx += d * d; }
+    sxx += __shfl_xor(sxx, 32, 64);
+    const float rstd = rsqrtf(sxx * (1.0f / CH_C) + a.ad_eps);
     // lane (ql, half) holds heads 4 half + j in registers j < 4
     float g[4], gh[4];
 #pragma unroll

@@ -8,9 +8,11 @@
 //          640- and 960-channel inputs;
 //   two launches: stats: grid (chunks, images); each block sweeps a chunk of pixels with every thread owning
 //          a fixed 8-channel column, folds per-channel sums into the 32 groups through LDS in
-//          a fixed order (deterministic) and writes one (sum, sumsq) pair per group;
-//          apply: every block first combines its image's chunk partials in fp64 (cancellation-safe
-//          E[x^2] - mean^2), then streams y = x * a[c] + b[c], optional SiLU.
+//          a fixed order (deterministic) and writes one (sum, sumsq) pair per group -- sums of x - k, with the
+//          group's shift k = its first element (gn_shift): fp32 sums of x and x^2 themselves lose the variance of a
+//          group whose mean is large against its spread, and a constant group's (x - k) sums are exactly zero;
+//          apply: every block first combines its image's chunk partials in fp64 (mean = k + S / n,
+//          var = Q / n - (S / n)^2), then streams y = (x - mean[c]) * a[c] + beta[c], optional SiLU.
 //          2 B read (stats) + 2 B read + 2 B written (apply) per element; fully coalesced 16-byte accesses;
 //   LDS (gn_fused_kernel): one launch, one block per (group, image), the slab in LDS (kept for A/Bs).
 #include "common.h"
@@ -40,6 +42,48 @@ struct GnArgs {
   void* finished;
 };
 
+// The shift of group g of image img for the two-launch and chunked forms' sums: the group's first channel at pixel 0.  Any
+// element of the group serves; every block of the image loads the same one (L2-resident) and the apply recomputes it.
+template <typename T>
+__device__ __forceinline__ float gn_shift(const GnArgs& a, int img, int g) {
+  const int c = g * (a.C / 32);
+  if (a.src_f32) return reinterpret_cast<const float*>(a.src0)[(long long)img * a.hw * a.C + c];
+  return c >= a.c0 ? (float)reinterpret_cast<const T*>(a.src1)[(long long)img * a.hw * a.c1 + (c - a.c0)]
+                   : (float)reinterpret_cast<const T*>(a.src0)[(long long)img * a.hw * a.c0 + c];
+}
+
+// chunk partials (sums of x - k, k = gn_shift) of the image -> per-group shift-free mean, rstd in s_mean / s_rstd; all 256
+// threads take part: thread (sub = tid >> 5, g = tid & 31) sums chunks sub, sub + 8, ... of group g in fp64 (independent loads,
+// one round trip), LDS folds the eight partial sums in a fixed order.  (32 threads walking all chunks serially cost ~8 us of
+// exposed latency per block.)  s_mean holds the fp32 mean, s_dev the fp32 S / n (the mean less k: what the fp32 outputs use).
+template <typename T>
+__device__ __forceinline__ void gn_combine(const GnArgs& a, int img, double (*s_ps)[32], double (*s_pq)[32], float* s_mean,
+                                           float* s_dev, float* s_shift, float* s_rstd) {
+  const int tid = threadIdx.x;
+  {
+    const int g = tid & 31, sub = tid >> 5;
+    double s = 0.0, q = 0.0;
+    const float* w = a.ws + ((long long)img * a.chunks * 32 + g) * 2;
+    for (int c = sub; c < a.chunks; c += 8) { s += (double)w[c * 64]; q += (double)w[c * 64 + 1]; }
+    s_ps[sub][g] = s; s_pq[sub][g] = q;
+  }
+  __syncthreads();
+  if (tid < 32) {
+    double s = 0.0, q = 0.0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { s += s_ps[k][tid]; q += s_pq[k][tid]; }
+    const double n = (double)a.hw * (double)(a.C / 32);
+    const double k = (double)gn_shift<T>(a, img, tid);
+    const double d = s / n;
+    double var = q / n - d * d;
+    var = var < 0.0 ? 0.0 : var;
+    s_mean[tid] = (float)(k + d);
+    if (s_dev) { s_dev[tid] = (float)d; s_shift[tid] = (float)k; }
+    s_rstd[tid] = (float)(1.0 / sqrt(var + (double)a.eps));
+  }
+  __syncthreads();
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const GnArgs a) {
   // LDS: per (row slot, channel) partial sums; rows*C <= 2048+ or C <= 2560 when one slot
@@ -67,6 +111,10 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const GnArgs a) {
       const bool second = c >= a.c0;
       const T* __restrict__ base = second ? s1 + (c - a.c0) : s0 + c;
       const int cs = second ? a.c1 : a.c0;
+      const int cpg = a.C / 32;
+      float k[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) k[j] = gn_shift<T>(a, img, (c + j) / cpg);
       // four independent 16-byte loads in flight per thread (the loop is latency-bound otherwise: one load per
       // thread and iteration keeps only ~32 KB per CU in flight)
       int p = p_begin + slot;
@@ -79,14 +127,14 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const GnArgs a) {
           float f[8];
           unpack8<T>(r[u], f);
 #pragma unroll
-          for (int j = 0; j < 8; ++j) { sum[j] += f[j]; sq[j] += f[j] * f[j]; }
+          for (int j = 0; j < 8; ++j) { const float d = f[j] - k[j]; sum[j] += d; sq[j] += d * d; }
         }
       }
       for (; p < p_end; p += rows) {
         float f[8];
         unpack8<T>(ld16(base + (long long)p * cs), f);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { sum[j] += f[j]; sq[j] += f[j] * f[j]; }
+        for (int j = 0; j < 8; ++j) { const float d = f[j] - k[j]; sum[j] += d; sq[j] += d * d; }
       }
       float* ds = s_sum + slot * a.C + c;
       float* dq = s_sq + slot * a.C + c;
@@ -111,42 +159,25 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const GnArgs a) {
 
 template <typename T>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const GnArgs a) {
-  // per-channel scale / shift of this image, built once per block:  y = x * sc[c] + sh[c]
+  // per-channel mean / scale / beta of this image, built once per block:  y = (x - mu[c]) * sc[c] + beta[c]  (a constant
+  // group gives beta exactly; x * sc + (beta - mean * sc) would leave the rounding of mean * sc behind).  The three tables are
+  // dynamic LDS of 3 C floats (the launch passes 12 C bytes; C % 8 == 0 keeps each 16-byte aligned): sized to the tensor, not to
+  // the largest C, so the blocks per CU of this streaming kernel are not cut by tables it does not use.
   __shared__ float s_mean[32], s_rstd[32];
-  __shared__ __attribute__((aligned(16))) float s_sc[2560];
-  __shared__ __attribute__((aligned(16))) float s_sh[2560];
+  extern __shared__ __attribute__((aligned(16))) float s_tab[];
+  float* const s_mu = s_tab;
+  float* const s_sc = s_tab + a.C;
+  float* const s_be = s_tab + 2 * a.C;
   const int tid = threadIdx.x;
   const int img = blockIdx.y;
-  // chunk partials -> (mean, rstd) of the 32 groups.  All 256 threads take part: thread (sub = tid >> 5, g = tid & 31)
-  // sums chunks sub, sub + 8, ... of group g in fp64 (independent loads, one round trip), LDS folds the eight
-  // partial sums in a fixed order.  (32 threads walking all chunks serially cost ~8 us of exposed latency per block.)
   __shared__ double s_ps[8][32], s_pq[8][32];
-  {
-    const int g = tid & 31, sub = tid >> 5;
-    double s = 0.0, q = 0.0;
-    const float* w = a.ws + ((long long)img * a.chunks * 32 + g) * 2;
-    for (int c = sub; c < a.chunks; c += 8) { s += (double)w[c * 64]; q += (double)w[c * 64 + 1]; }
-    s_ps[sub][g] = s; s_pq[sub][g] = q;
-  }
-  __syncthreads();
-  if (tid < 32) {
-    double s = 0.0, q = 0.0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { s += s_ps[k][tid]; q += s_pq[k][tid]; }
-    const double n = (double)a.hw * (double)(a.C / 32);
-    const double mean = s / n;
-    double var = q / n - mean * mean;
-    var = var < 0.0 ? 0.0 : var;
-    s_mean[tid] = (float)mean;
-    s_rstd[tid] = (float)(1.0 / sqrt(var + (double)a.eps));
-  }
-  __syncthreads();
+  gn_combine<T>(a, img, s_ps, s_pq, s_mean, nullptr, nullptr, s_rstd);
   const int cpg = a.C / 32;
   for (int c = tid; c < a.C; c += 256) {
     const int g = c / cpg;
-    const float sc = s_rstd[g] * a.gamma[c];
-    s_sc[c] = sc;
-    s_sh[c] = a.beta[c] - s_mean[g] * sc;
+    s_mu[c] = s_mean[g];
+    s_sc[c] = s_rstd[g] * a.gamma[c];
+    s_be[c] = a.beta[c];
   }
   __syncthreads();
   const int V = a.C >> 3;
@@ -166,12 +197,13 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const GnArgs a) {
   auto finish = [&](const u32x4& raw, int pp, int c) {
     float f[8];
     unpack8<T>(raw, f);
+    const f32x4 mu0 = *reinterpret_cast<const f32x4*>(s_mu + c), mu1 = *reinterpret_cast<const f32x4*>(s_mu + c + 4);
     const f32x4 sc0 = *reinterpret_cast<const f32x4*>(s_sc + c), sc1 = *reinterpret_cast<const f32x4*>(s_sc + c + 4);
-    const f32x4 sh0 = *reinterpret_cast<const f32x4*>(s_sh + c), sh1 = *reinterpret_cast<const f32x4*>(s_sh + c + 4);
+    const f32x4 be0 = *reinterpret_cast<const f32x4*>(s_be + c), be1 = *reinterpret_cast<const f32x4*>(s_be + c + 4);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      f[j] = f[j] * sc0[j] + sh0[j];
-      f[4 + j] = f[4 + j] * sc1[j] + sh1[j];
+      f[j] = (f[j] - mu0[j]) * sc0[j] + be0[j];
+      f[4 + j] = (f[4 + j] - mu1[j]) * sc1[j] + be1[j];
     }
     if (a.silu) {
 #pragma unroll
@@ -197,7 +229,9 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const GnArgs a) {
 // ---------------------------------------------------------------------------------------
 // The two-launch form for fp32 sources and for the "precise" outputs (GnArgs.src_f32 / out_mode): the lidar decoder's tail of
 // the fp16 parity configuration (ldm/modules/diffusionmodules/model.py).  Same statistics arithmetic as gn_stats_kernel /
-// gn_apply_kernel (per-chunk fp32 partial sums, fp64 fold); not tuned -- a handful of launches per decode.
+// gn_apply_kernel (per-chunk fp32 partial sums of x - k, fp64 fold); the apply keeps the shift apart,
+// y = ((x - k) - S / n) * sc + beta: x - k is exact, so an fp32 output does not carry the rounding of an fp32 mean (|mean| 2^-24
+// against the spread).  Not tuned -- a handful of launches per decode.
 __global__ __launch_bounds__(256) void gn_stats_f32_kernel(const GnArgs a) {
   __shared__ float s_sum[2560 + 512];
   __shared__ float s_sq[2560 + 512];
@@ -218,11 +252,15 @@ __global__ __launch_bounds__(256) void gn_stats_f32_kernel(const GnArgs a) {
     for (int j = 0; j < 8; ++j) { sum[j] = 0.f; sq[j] = 0.f; }
     if (active) {
       const int c = col * 8;
+      const int cpg = a.C / 32;
+      float k[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) k[j] = gn_shift<float>(a, img, (c + j) / cpg);
       for (int p = p_begin + slot; p < p_end; p += rows) {
         float f[8];
         ld8f(s0 + (long long)p * a.C + c, f);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { sum[j] += f[j]; sq[j] += f[j] * f[j]; }
+        for (int j = 0; j < 8; ++j) { const float d = f[j] - k[j]; sum[j] += d; sq[j] += d * d; }
       }
       float* ds = s_sum + slot * a.C + c;
       float* dq = s_sq + slot * a.C + c;
@@ -247,38 +285,19 @@ __global__ __launch_bounds__(256) void gn_stats_f32_kernel(const GnArgs a) {
 
 template <typename T>
 __global__ __launch_bounds__(256) void gn_apply_x_kernel(const GnArgs a) {
-  __shared__ float s_mean[32], s_rstd[32];
-  __shared__ __attribute__((aligned(16))) float s_sc[2560];
-  __shared__ __attribute__((aligned(16))) float s_sh[2560];
+  __shared__ float s_mean[32], s_dev[32], s_shift[32], s_rstd[32];
+  __shared__ float s_k[2560], s_d[2560], s_sc[2560], s_be[2560];
   __shared__ double s_ps[8][32], s_pq[8][32];
   const int tid = threadIdx.x;
   const int img = blockIdx.y;
-  {
-    const int g = tid & 31, sub = tid >> 5;
-    double s = 0.0, q = 0.0;
-    const float* w = a.ws + ((long long)img * a.chunks * 32 + g) * 2;
-    for (int c = sub; c < a.chunks; c += 8) { s += (double)w[c * 64]; q += (double)w[c * 64 + 1]; }
-    s_ps[sub][g] = s; s_pq[sub][g] = q;
-  }
-  __syncthreads();
-  if (tid < 32) {
-    double s = 0.0, q = 0.0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { s += s_ps[k][tid]; q += s_pq[k][tid]; }
-    const double n = (double)a.hw * (double)(a.C / 32);
-    const double mean = s / n;
-    double var = q / n - mean * mean;
-    var = var < 0.0 ? 0.0 : var;
-    s_mean[tid] = (float)mean;
-    s_rstd[tid] = (float)(1.0 / sqrt(var + (double)a.eps));
-  }
-  __syncthreads();
+  gn_combine<T>(a, img, s_ps, s_pq, s_mean, s_dev, s_shift, s_rstd);
   const int cpg = a.C / 32;
   for (int c = tid; c < a.C; c += 256) {
     const int g = c / cpg;
-    const float sc = s_rstd[g] * a.gamma[c];
-    s_sc[c] = sc;
-    s_sh[c] = a.beta[c] - s_mean[g] * sc;
+    s_k[c] = s_shift[g];
+    s_d[c] = s_dev[g];
+    s_sc[c] = s_rstd[g] * a.gamma[c];
+    s_be[c] = a.beta[c];
   }
   __syncthreads();
   const int V = a.C >> 3;
@@ -296,7 +315,7 @@ __global__ __launch_bounds__(256) void gn_apply_x_kernel(const GnArgs a) {
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      f[j] = f[j] * s_sc[c + j] + s_sh[c + j];
+      f[j] = ((f[j] - s_k[c + j]) - s_d[c + j]) * s_sc[c + j] + s_be[c + j];
       if (a.silu) f[j] = silu_f(f[j]);
     }
     if (a.out_mode == 2) {
@@ -597,7 +616,8 @@ __global__ __launch_bounds__(THREADS) void gn_regs_kernel(const GnArgs a, const 
     reduce(lo, hi, 1, inv_n, true);
   }
   pin();
-  // y = x * sc[c] + sh[c]
+  // y = x * sc[c] + sh[c].  (Not (x - mean) sc + beta, which gives a constant group beta exactly where this form leaves the fp32
+  // rounding of mean * sc behind, ~2^-24 |mean| rstd: the selected mean costs the 1024-thread instantiations a spill.)
   for (int cc = tid; cc < GB * cpg; cc += THREADS) {
     const int g = cc / cpg;
     const float sc = s_stat[1][g] * a.gamma[c_first + cc];
@@ -859,15 +879,21 @@ __global__ __launch_bounds__(1024) void gn_coop_kernel(const GnArgs a, const GnC
     if (live && q < geo.ppb && p0 + q < a.hw) raw[i] = ld16(src + (long long)(p0 + q) * cs);
   }
   {
+    // sums of x - k (k: the group's shift, gn_shift), as in the two-launch form
+    const float k_lo = gn_shift<T>(a, img, g0), k_hi = gn_shift<T>(a, img, min(g0 + 1, 31));
     float sm[8], sq[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) { sm[j] = 0.f; sq[j] = 0.f; }
 #pragma unroll
-    for (int i = 0; i < ITEMS; ++i) {                    // (pieces past the chunk are zeros: they add nothing)
+    for (int i = 0; i < ITEMS; ++i) {
+      const bool in = live && slot + i * SLOTS < geo.ppb && p0 + slot + i * SLOTS < a.hw;   // (pieces past the chunk: none)
       float f[8];
       unpack8<T>(raw[i], f);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) { sm[j] += f[j]; sq[j] += f[j] * f[j]; }
+      for (int j = 0; j < 8; ++j) {
+        const float d = in ? f[j] - (j < k ? k_lo : k_hi) : 0.f;
+        sm[j] += d; sq[j] += d * d;
+      }
     }
     float lo_s = 0.f, hi_s = 0.f, lo_q = 0.f, hi_q = 0.f;
 #pragma unroll
@@ -936,25 +962,23 @@ __global__ __launch_bounds__(1024) void gn_coop_kernel(const GnArgs a, const GnC
     double s = 0.0, q = 0.0;
     for (int ch = 0; ch < geo.chunks; ++ch) { s += s_ps[ch][tid]; q += s_pq[ch][tid]; }
     const double n = (double)a.hw * (double)cpg;
-    const double mean = s / n;
-    double var = q / n - mean * mean;
+    const double d = s / n;
+    double var = q / n - d * d;
     var = var < 0.0 ? 0.0 : var;
-    s_mean[tid] = (float)mean;
+    s_mean[tid] = (float)((double)gn_shift<T>(a, img, tid) + d);
     s_rstd[tid] = (float)(1.0 / sqrt(var + (double)a.eps));
   }
   __syncthreads();
   if (!live) return;
+  // y = (x - mean) * sc + beta (sh holds beta: a constant group gives beta exactly)
   float sc[8], sh[8];
+  const float m_lo = s_mean[g0], m_hi = s_mean[min(g0 + 1, 31)];
   {
-    float gm[8], bt[8];
+    float gm[8];
     ld8f(a.gamma + c, gm);
-    ld8f(a.beta + c, bt);
+    ld8f(a.beta + c, sh);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int g = j < k ? g0 : g0 + 1;
-      sc[j] = s_rstd[g] * gm[j];
-      sh[j] = bt[j] - s_mean[g] * sc[j];
-    }
+    for (int j = 0; j < 8; ++j) sc[j] = s_rstd[j < k ? g0 : g0 + 1] * gm[j];
   }
   T* __restrict__ out = reinterpret_cast<T*>(a.out) + (long long)img * a.hw * a.C + c;
 #pragma unroll
@@ -965,7 +989,7 @@ __global__ __launch_bounds__(1024) void gn_coop_kernel(const GnArgs a, const GnC
       unpack8<T>(raw[i], f);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        f[j] = f[j] * sc[j] + sh[j];
+        f[j] = (f[j] - (j < k ? m_lo : m_hi)) * sc[j] + sh[j];
         if (a.silu) f[j] = silu_f(f[j]);
       }
       st16(out + (long long)(p0 + q) * a.C, pack8<T>(f));
@@ -1075,7 +1099,7 @@ static int launch_gn(const GnArgs& a, int batch, hipStream_t st) {
   const long long cap = (2048 + batch - 1) / batch;
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL((gn_apply_kernel<T>), dim3((unsigned)blocks, batch), dim3(256), 0, st, a);
+  hipLaunchKernelGGL((gn_apply_kernel<T>), dim3((unsigned)blocks, batch), dim3(256), (size_t)12 * a.C, st, a);
   MOBI_CHECK_LAUNCH();
   return MOBI_OK;
 }

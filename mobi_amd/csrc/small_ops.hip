@@ -189,14 +189,17 @@ __global__ void layernorm_rows_f32_kernel(const float* __restrict__ x, const flo
   const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows) return;
   const float* xr = x + (long long)row * x_stride;
+  // sums about the row's first element k: x - k is exact where x and k are close, so the mean (k + dm) and x - mean =
+  // (x - k) - dm carry no rounding of |mean| (a large common offset; a constant row normalises to exactly zero)
+  const float k = xr[0];
   float s = 0.f;
-  for (int c = lane; c < cols; c += 64) s += xr[c];
-  const float mean = wave_sum(s) / (float)cols;
+  for (int c = lane; c < cols; c += 64) s += xr[c] - k;
+  const float dm = wave_sum(s) / (float)cols;
   float v = 0.f;
-  for (int c = lane; c < cols; c += 64) { const float d = xr[c] - mean; v += d * d; }
+  for (int c = lane; c < cols; c += 64) { const float d = (xr[c] - k) - dm; v += d * d; }
   const float rstd = rsqrtf(wave_sum(v) / (float)cols + eps);
   float* o = out + (long long)row * out_stride;
-  for (int c = lane; c < cols; c += 64) o[c] = (xr[c] - mean) * rstd * gamma[c] + beta[c];
+  for (int c = lane; c < cols; c += 64) o[c] = ((xr[c] - k) - dm) * rstd * gamma[c] + beta[c];
 }
 
 // CLIP's "quick_gelu" (transformers: x * sigmoid(1.702 x)), elementwise on a T tensor, 8 values per thread
@@ -604,6 +607,9 @@ __global__ __launch_bounds__(256) void two_key_adapter_kernel(const mobi_two_key
     load_row(r + 4, nxt);
     float x[MAXV][8];
     float acc[16];
+    // LayerNorm sums about the row's first element k (shift-safe one pass: a large common offset keeps its spread, a
+    // constant row has exactly zero variance)
+    const float k = (float)xb[(long long)r * C];
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
 #pragma unroll
@@ -612,7 +618,7 @@ __global__ __launch_bounds__(256) void two_key_adapter_kernel(const mobi_two_key
       if (v < V) {
         unpack8<T>(cur[i], x[i]);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { acc[0] += x[i][j]; acc[1] += x[i][j] * x[i][j]; }
+        for (int j = 0; j < 8; ++j) { const float d = x[i][j] - k; acc[0] += d; acc[1] += d * d; }
 #pragma unroll
         for (int h = 0; h < 8; ++h) {
           const f32x4 a0 = reinterpret_cast<const f32x4*>(s_a)[h * (C >> 2) + v];
@@ -662,8 +668,9 @@ __global__ __launch_bounds__(256) void two_key_adapter_kernel(const mobi_two_key
       const int src = ((k >> 3) & 1) * 32 + ((k >> 2) & 1) * 16 + ((k >> 1) & 1) * 8 + (k & 1) * 4;
       return __builtin_amdgcn_readlane(__builtin_bit_cast(int, v1), src);
     };
-    const float mean = __builtin_bit_cast(float, total(0)) * inv_c;
-    float var = __builtin_bit_cast(float, total(1)) * inv_c - mean * mean;
+    const float dm = __builtin_bit_cast(float, total(0)) * inv_c;
+    const float mean = k + dm;
+    float var = __builtin_bit_cast(float, total(1)) * inv_c - dm * dm;
     var = var < 0.f ? 0.f : var;
     const float rstd = rsqrtf(var + p.eps);
     float g[8];
@@ -846,9 +853,10 @@ __global__ __launch_bounds__(256) void two_key_adapter_mfma_kernel(const mobi_tw
     fetch(r0 + 64);
     __builtin_amdgcn_s_waitcnt(0xc07f);             // lgkmcnt(0); the tile is private to the wave
     __builtin_amdgcn_wave_barrier();
-    // ---- logits + LayerNorm sums --------------------------------------------------------------------------------
+    // ---- logits + LayerNorm sums (about the row's first element k: shift-safe one pass) ------------------------------
     f32x4 lg = f32x4{0.f, 0.f, 0.f, 0.f};
     float sx = 0.f, sxx = 0.f;
+    const float k = r0 + r16 < r_end ? (float)xb[(long long)(r0 + r16) * C] : 0.f;
     for (int k0 = 0; k0 < C; k0 += 32) {
       const frag_t xf = __builtin_bit_cast(frag_t, ld16(xt + r16 * XST + (k0 + 8 * g4) * 2));
       frag_t ah, al;
@@ -859,14 +867,15 @@ __global__ __launch_bounds__(256) void two_key_adapter_mfma_kernel(const mobi_tw
         al = __builtin_bit_cast(frag_t, ld16(s_alo + r16 * AST + (k0 + 8 * g4) * 2));
       }
 #pragma unroll
-      for (int j = 0; j < 8; ++j) { const float v = (float)xf[j]; sx += v; sxx += v * v; }
+      for (int j = 0; j < 8; ++j) { const float v = (float)xf[j] - k; sx += v; sxx += v * v; }
       lg = mfma16(ah, xf, lg);
       lg = mfma16(al, xf, lg);
     }
     sx += __shfl_xor(sx, 16, 64); sx += __shfl_xor(sx, 32, 64);            // the four k-chunk lanes of a token
     sxx += __shfl_xor(sxx, 16, 64); sxx += __shfl_xor(sxx, 32, 64);
-    const float mean = sx * inv_c;
-    float var = sxx * inv_c - mean * mean;
+    const float dm = sx * inv_c;
+    const float mean = k + dm;
+    float var = sxx * inv_c - dm * dm;
     var = var < 0.f ? 0.f : var;
     const float rstd = rsqrtf(var + p.eps);
     float g[4];
@@ -1047,16 +1056,17 @@ __global__ __launch_bounds__(256) void two_key_adapter_regs_kernel(const mobi_tw
       for (int e = 0; e < 4; ++e) xf[f][e] = v[e];
     }
     auto frag = [&](int f) { return __builtin_bit_cast(frag_t, u32x4{xf[f][0], xf[f][1], xf[f][2], xf[f][3]}); };
-    // ---- logits + LayerNorm sums --------------------------------------------------------------------------------
+    // ---- logits + LayerNorm sums (about the row's first element k: shift-safe one pass) ------------------------------
     f32x4 lg = f32x4{0.f, 0.f, 0.f, 0.f};
     float sx = 0.f, sxx = 0.f;
+    const float k = (float)xb[(long long)(live ? row : r_end - 1) * C];
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
       const frag_t x8 = frag(f);
       const frag_t ah = __builtin_bit_cast(frag_t, ld16(s_ahi + a_off + 64 * f));
       const frag_t al = __builtin_bit_cast(frag_t, ld16(s_alo + a_off + 64 * f));
 #pragma unroll
-      for (int j = 0; j < 8; ++j) { const float v = (float)x8[j]; sx += v; sxx += v * v; }
+      for (int j = 0; j < 8; ++j) { const float v = (float)x8[j] - k; sx += v; sxx += v * v; }
       lg = mfma16(ah, x8, lg);
       lg = mfma16(al, x8, lg);
     }
@@ -1068,8 +1078,9 @@ __global__ __launch_bounds__(256) void two_key_adapter_regs_kernel(const mobi_tw
       for (int e = 0; e < 4; ++e) asm volatile("" : "+v"(xf[f][e]));
     sx += __shfl_xor(sx, 16, 64); sx += __shfl_xor(sx, 32, 64);            // the four k-chunk lanes of a token
     sxx += __shfl_xor(sxx, 16, 64); sxx += __shfl_xor(sxx, 32, 64);
-    const float mean = sx * inv_c;
-    float var = sxx * inv_c - mean * mean;
+    const float dm = sx * inv_c;
+    const float mean = k + dm;
+    float var = sxx * inv_c - dm * dm;
     var = var < 0.f ? 0.f : var;
     const float rstd = rsqrtf(var + p.eps);
     float g[4];
