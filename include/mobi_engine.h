@@ -45,7 +45,8 @@ extern "C" {
  *      mobi_groupnorm_params.src_f32 / out_mode (0..3); mobi_split_f32
  *   6  mobi_igemm_params.defer_finish + mobi_igemm_slab_count / mobi_igemm_finish; mobi_split_source (struct id 19) and
  *      mobi_groupnorm_params.src0_split + mobi_groupnorm_takes_split: a split-K launch's partial sums are summed by the
- *      GroupNorm that consumes them instead of by a reduce launch of their own */
+ *      GroupNorm that consumes them instead of by a reduce launch of their own; later, without a layout change (an
+ *      addition only), mobi_dpm_step and its mobi_dpm_step_params (struct id 20) */
 #define MOBI_ABI_VERSION 6
 
 enum { MOBI_OK = 0, MOBI_ERR_ARG = -1, MOBI_ERR_UNSUPPORTED = -2, MOBI_ERR_LAUNCH = -3, MOBI_ERR_ALIGN = -4 };
@@ -57,7 +58,8 @@ const char* mobi_error_string(int code);
  * their own layout before the first call.  id: 0 igemm, 1 groupnorm, 2 layernorm,
  * 3 attention, 4 ctx_attention, 5 skinny_linear, 6 conv_small_cin, 7 conv_small_cout,
  * 8 ddim_step, 9 two_key_adapter, 10 range_paste, 11 lidar_metrics, 12 range_prepare, 13 image_prepare, 14 ff_geglu,
- * 15 row_chain, 16 chain_op, 17 layernorm_bwd, 18 attention_bwd, 19 split_source.  Returns 0 for an unknown id. */
+ * 15 row_chain, 16 chain_op, 17 layernorm_bwd, 18 attention_bwd, 19 split_source, 20 dpm_step.  Returns 0 for an
+ * unknown id. */
 size_t mobi_struct_size(int id);
 /* Development hook: the library reads its MOBI_* A/B environment variables once, at the first launch
  * (mobi_amd/csrc/tuning.h lists them); this re-reads them.  Not needed by a product caller. */
@@ -595,6 +597,29 @@ typedef struct mobi_ddim_step_params {
   const float* coef_dev;
 } mobi_ddim_step_params;
 int mobi_ddim_step(const mobi_ddim_step_params* p, void* stream);
+
+/* One step of DPM-Solver++(2M) (Lu et al. 2022, multistep second order, data prediction) from s to t on the
+ * DDIM grid (mobi_amd/ldm/models/diffusion/dpm_solver.py), alpha = sqrt(abar), sigma = sqrt(1 - abar),
+ * lambda = log alpha - log sigma, h = lambda_t - lambda_s, r = h_prev / h.  In fp32, in this order (no FMA):
+ *   e      = e_uncond + cfg_scale * (e_cond - e_uncond)           (e_uncond NULL: e = e_cond)
+ *   x0     = inv_alpha_s * x - sigma_over_alpha_s * e             ((x - sigma_s e) / alpha_s)
+ *   x_next = c_x * x + c_0 * x0                                   (c_1 == 0: first order; x0_hist is NOT read)
+ *   x_next = (c_x * x + c_0 * x0) + c_1 * x0_hist                 (c_1 != 0: second order)
+ *   pred_x0 = x0;  x0_hist = x0                                   (written after the read: in place per element)
+ * with c_x = sigma_t / sigma_s, c_0 = -alpha_t (e^-h - 1) (1 + 1/(2r)), c_1 = alpha_t (e^-h - 1) / (2r)
+ * (first order: c_0 = -alpha_t (e^-h - 1), c_1 = 0), computed in fp64 on the host and rounded once to fp32.
+ * `coef_dev` (or NULL): DEVICE pointer to the five floats {inv_alpha_s, sigma_over_alpha_s, c_x, c_0, c_1} that
+ * replace the by-value fields (one row of the run's [S, 5] table; a graph-captured step reads it per replay).
+ * A first-order step never reads x0_hist, so a stale (even NaN) history cannot leak into it.
+ * Null x / e_cond / x0_hist / x_next / pred_x0 or n <= 0: MOBI_ERR_ARG before any launch. */
+typedef struct mobi_dpm_step_params {
+  const float* x; const float* e_cond; const float* e_uncond;
+  float* x0_hist; float* x_next; float* pred_x0;
+  int64_t n;
+  float cfg_scale, inv_alpha_s, sigma_over_alpha_s, c_x, c_0, c_1;
+  const float* coef_dev;
+} mobi_dpm_step_params;
+int mobi_dpm_step(const mobi_dpm_step_params* p, void* stream);
 
 /* out = c0*e0 + c1*e1 + c2*e2 + c3*e3, the Adams-Bashforth mixes of plms.py:219-233
  * (null pointers are skipped). */

@@ -134,6 +134,12 @@ class DdimStepParams(C.Structure):
                 ("sqrt_one_minus_at", f32), ("temperature", f32), ("coef_dev", vp)]
 
 
+class DpmStepParams(C.Structure):
+    _fields_ = [("x", vp), ("e_cond", vp), ("e_uncond", vp), ("x0_hist", vp), ("x_next", vp), ("pred_x0", vp),
+                ("n", i64), ("cfg_scale", f32), ("inv_alpha_s", f32), ("sigma_over_alpha_s", f32), ("c_x", f32),
+                ("c_0", f32), ("c_1", f32), ("coef_dev", vp)]
+
+
 class RangePasteParams(C.Structure):
     _fields_ = [("sample_depth", vp), ("sample_int", vp), ("depth_orig", vp), ("int_orig", vp), ("pitch", vp), ("yaw", vp),
                 ("gt_mask", vp), ("planes", vp), ("crop_left", vp), ("width_crop", vp), ("depth_unc", vp), ("int_unc", vp),
@@ -162,7 +168,7 @@ STRUCT_IDS = {0: IgemmParams, 1: GroupNormParams, 2: LayerNormParams, 3: Attenti
               5: SkinnyLinearParams, 6: ConvSmallCinParams, 7: ConvSmallCoutParams, 8: DdimStepParams, 9: TwoKeyAdapterParams,
               10: RangePasteParams, 11: LidarMetricsParams, 12: RangePrepareParams, 13: ImagePrepareParams,
               14: FfGegluParams, 15: RowChainParams, 16: ChainOp,
-              17: LayerNormBwdParams, 18: AttentionBwdParams, 19: SplitSource}
+              17: LayerNormBwdParams, 18: AttentionBwdParams, 19: SplitSource, 20: DpmStepParams}
 
 # every symbol include/mobi_engine.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -219,6 +225,7 @@ SYMBOLS = {
     "mobi_conv_small_cin": (C.c_int, [C.POINTER(ConvSmallCinParams), vp]),
     "mobi_conv_small_cout": (C.c_int, [C.POINTER(ConvSmallCoutParams), vp]),
     "mobi_ddim_step": (C.c_int, [C.POINTER(DdimStepParams), vp]),
+    "mobi_dpm_step": (C.c_int, [C.POINTER(DpmStepParams), vp]),
     "mobi_lincomb4": (C.c_int, [vp, vp, vp, vp, vp, f32, f32, f32, f32, i64, vp]),
     "mobi_q_sample": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "mobi_mask_blend": (C.c_int, [vp, vp, vp, vp, f32, f32, i32, i32, i32, vp]),

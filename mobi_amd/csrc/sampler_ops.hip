@@ -30,6 +30,32 @@ __global__ void ddim_step_kernel(const mobi_ddim_step_params a) {
   }
 }
 
+// DPM-Solver++(2M) step (include/mobi_engine.h, mobi_dpm_step): the documented fp32 order, no FMA (-ffp-contract=off),
+// so a torch fp32 restatement in the same order is bit-identical.  c_1 == 0 is uniform across the launch: a first-order
+// step never loads x0_hist (a captured graph's history holds the previous run's values, possibly NaN; 0 * NaN = NaN).
+__global__ void dpm_step_kernel(const mobi_dpm_step_params a) {
+  float inv_a = a.inv_alpha_s, s_over_a = a.sigma_over_alpha_s, c_x = a.c_x, c_0 = a.c_0, c_1 = a.c_1;
+  if (a.coef_dev) {
+    inv_a = a.coef_dev[0]; s_over_a = a.coef_dev[1]; c_x = a.coef_dev[2]; c_0 = a.coef_dev[3]; c_1 = a.coef_dev[4];
+  }
+  const bool second = c_1 != 0.0f;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n;
+       i += (long long)gridDim.x * blockDim.x) {
+    float e = a.e_cond[i];
+    if (a.e_uncond) {
+      const float eu = a.e_uncond[i];
+      e = eu + a.cfg_scale * (e - eu);
+    }
+    const float x = a.x[i];
+    const float x0 = inv_a * x - s_over_a * e;
+    float xn = c_x * x + c_0 * x0;
+    if (second) xn = xn + c_1 * a.x0_hist[i];
+    a.x_next[i] = xn;
+    a.pred_x0[i] = x0;
+    a.x0_hist[i] = x0;
+  }
+}
+
 __global__ void lincomb4_kernel(float* out, const float* e0, const float* e1, const float* e2, const float* e3,
                                 float c0, float c1, float c2, float c3, long long n) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
@@ -152,6 +178,13 @@ extern "C" int mobi_ddim_step(const mobi_ddim_step_params* p, void* stream) {
   return MOBI_OK;
 }
 
+extern "C" int mobi_dpm_step(const mobi_dpm_step_params* p, void* stream) {
+  if (!p || !p->x || !p->e_cond || !p->x0_hist || !p->x_next || !p->pred_x0 || p->n <= 0) return MOBI_ERR_ARG;
+  hipLaunchKernelGGL(dpm_step_kernel, dim3(egrid(p->n)), dim3(256), 0, ST(stream), *p);
+  MOBI_CHECK_LAUNCH();
+  return MOBI_OK;
+}
+
 extern "C" int mobi_lincomb4(float* out, const float* e0, const float* e1, const float* e2, const float* e3, float c0,
                              float c1, float c2, float c3, int64_t n, void* stream) {
   if (!out || !e0 || n <= 0) return MOBI_ERR_ARG;
@@ -235,6 +268,7 @@ extern "C" size_t mobi_struct_size(int id) {
     case 17: return sizeof(mobi_layernorm_bwd_params);
     case 18: return sizeof(mobi_attention_bwd_params);
     case 19: return sizeof(mobi_split_source);
+    case 20: return sizeof(mobi_dpm_step_params);
     default: return 0;
   }
 }

@@ -2,13 +2,16 @@
 
 A UNet forward is ~590 engine launches (ctypes call + parameter struct each); at the 32x32 latent of
 `mobi_nusc_256` the GPU finishes them faster than the host can issue them.  `StepGraph` captures the launch
-sequence of one step -- UNet forward (both halves with classifier-free guidance) and, for DDIM, the fp32 latent
-update -- into a HIP graph once per (shapes, storage type, guidance, sampler-kind) key and replays it per step.
+sequence of one step -- UNet forward (both halves with classifier-free guidance) and, for DDIM and DPM-Solver++(2M), the
+fp32 latent update -- into a HIP graph once per (shapes, storage type, guidance, sampler-kind) key and replays it per step.
 
 What changes from step to step lives in device buffers the graph reads:
   x        the latent state                    (copied in before a replay)
   ts       int64 timestep vector               (filled)
-  coef     {a_t, a_prev, sigma_t, sqrt(1-a_t)} (copied from the run's device table; `mobi_ddim_step.coef_dev`)
+  coef     {a_t, a_prev, sigma_t, sqrt(1-a_t)} (copied from the run's device table; `mobi_ddim_step.coef_dev`), or for
+           DPM {1/alpha_s, sigma_s/alpha_s, c_x, c_0, c_1} (`mobi_dpm_step.coef_dev`; c_1 = 0 makes a step first
+           order, so one capture serves every step of a run)
+  x0_hist  DPM only: the previous step's x0, read and rewritten in place by the captured update
   noise    the step's Gaussian draw            (eta > 0 only)
 What changes from sampling run to sampling run (conditioning tokens, inpaint latents, mask) is copied into static
 buffers when the caller's tensors change (identity / version counter); the transformer blocks then refresh their
@@ -65,8 +68,9 @@ def _context_blocks(model):
 
 
 class StepGraph:
-    """kind = "ddim": eps + latent update -> (x_prev, pred_x0); kind = "eps": UNet forward(s) only ->
-    (e_cond, e_uncond | None) (PLMS mixes the eps history eagerly)."""
+    """kind = "ddim": eps + latent update -> (x_prev, pred_x0); kind = "dpm": eps + DPM-Solver++(2M) update ->
+    (x_next, pred_x0); kind = "eps": UNet forward(s) only -> (e_cond, e_uncond | None) (PLMS mixes the eps history
+    eagerly)."""
 
     def __init__(self, sampler, kind, x, cond, uncond, scale, parts_extra, parts_key, temperature, has_noise):
         # (weak: the sampler owns this object through its graph table -- a strong back-reference would make a cycle whose
@@ -78,7 +82,8 @@ class StepGraph:
         self.parts_key = parts_key
         self.x = torch.empty_like(x)
         self.ts = torch.zeros((x.shape[0],), device=dev, dtype=torch.long)
-        self.coef = torch.ones(4, device=dev, dtype=torch.float32)
+        self.coef = torch.ones(5 if kind == "dpm" else 4, device=dev, dtype=torch.float32)
+        self.x0_hist = torch.zeros_like(x) if kind == "dpm" else None
         self.noise = torch.zeros_like(x) if has_noise else None
         self.extra = [torch.empty(p.shape, device=dev, dtype=torch.float32) for p in parts_extra]
         # conditioning tokens as the UNet sees them: [uncond ; cond] with guidance (ddim.py:180-183 of the reference)
@@ -134,6 +139,8 @@ class StepGraph:
                           cfg_ctx=self.ctx if self.cfg else None)
         if self.kind == "eps":
             return e_c, e_u
+        if self.kind == "dpm":
+            return ops.dpm_step(self.x, e_c, self.x0_hist, e_uncond=e_u, cfg_scale=self.scale, coef_dev=self.coef)
         x_prev, pred, _ = ops.ddim_step(self.x, e_c, e_uncond=e_u, noise=self.noise, cfg_scale=self.scale,
                                         temperature=self.temperature, coef_dev=self.coef)
         return x_prev, pred

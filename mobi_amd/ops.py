@@ -1143,6 +1143,28 @@ def ddim_step(x, e_cond, *, e_uncond=None, noise=None, cfg_scale=1.0, a_t=1.0, a
     return x_prev, pred, e_out
 
 
+def dpm_step(x, e_cond, x0_hist, *, e_uncond=None, cfg_scale=1.0, inv_alpha_s=1.0, sigma_over_alpha_s=0.0, c_x=1.0,
+             c_0=0.0, c_1=0.0, coef_dev=None):
+    """One DPM-Solver++(2M) update (include/mobi_engine.h, mobi_dpm_step) -> (x_next, pred_x0); x0_hist is read (only
+    when c_1 != 0) and then overwritten with pred_x0.  coef_dev: fp32 device tensor {inv_alpha_s, sigma_over_alpha_s,
+    c_x, c_0, c_1} replacing the by-value coefficients (graph-captured steps, mobi_amd/graph.py)."""
+    lib = _lib.load()
+    for t in (x, e_cond, e_uncond, x0_hist):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
+    assert x0_hist.numel() == x.numel() and e_cond.numel() == x.numel() and (e_uncond is None or e_uncond.numel() == x.numel())
+    x_next, pred = torch.empty_like(x), torch.empty_like(x)
+    p = _lib.DpmStepParams()
+    p.x, p.e_cond, p.e_uncond, p.x0_hist = _ptr(x), _ptr(e_cond), _ptr(e_uncond), _ptr(x0_hist)
+    p.x_next, p.pred_x0, p.n = _ptr(x_next), _ptr(pred), x.numel()
+    p.cfg_scale, p.inv_alpha_s, p.sigma_over_alpha_s = cfg_scale, inv_alpha_s, sigma_over_alpha_s
+    p.c_x, p.c_0, p.c_1 = c_x, c_0, c_1
+    if coef_dev is not None:
+        assert coef_dev.dtype == torch.float32 and coef_dev.numel() == 5 and coef_dev.is_contiguous()
+        p.coef_dev = _ptr(coef_dev)
+    _lib.check(lib.mobi_dpm_step(C.byref(p), _stream()), "mobi_dpm_step")
+    return x_next, pred
+
+
 def lincomb4(es, cs):
     lib = _lib.load()
     es = list(es) + [None] * (4 - len(es))
