@@ -166,11 +166,11 @@ def unet_param_shapes(cfg: UNetConfig):
 # forward
 # ----------------------------------------------------------------------------
 
-def timestep_embedding(t, dim, max_period=10000):
-    """util.py:151-171 (repeat_only=False)."""
+def timestep_embedding(t, dim, max_period=10000, dtype=torch.float32):
+    """util.py:151-171 (repeat_only=False); dtype: float32 as the reference, float64 for an fp64 restatement."""
     half = dim // 2
-    freqs = torch.exp(-math.log(max_period) * torch.arange(0, half, dtype=torch.float32) / half)
-    args = t[:, None].float() * freqs[None]
+    freqs = torch.exp(-math.log(max_period) * torch.arange(0, half, dtype=dtype, device=t.device) / half)
+    args = t[:, None].to(dtype) * freqs[None]
     emb = torch.cat([torch.cos(args), torch.sin(args)], dim=-1)
     if dim % 2:
         emb = torch.cat([emb, torch.zeros_like(emb[:, :1])], dim=-1)
@@ -186,7 +186,7 @@ def _conv(sd, p, x, stride=1, padding=1):
 
 
 def _gn(sd, p, x, eps):
-    return F.group_norm(x.float(), 32, sd[p + ".weight"], sd[p + ".bias"], eps)
+    return F.group_norm(x if x.dtype == torch.float64 else x.float(), 32, sd[p + ".weight"], sd[p + ".bias"], eps)
 
 
 def _ln(sd, p, x):

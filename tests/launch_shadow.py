@@ -1,0 +1,622 @@
+"""Launch shadow (TEST INFRASTRUCTURE, not a conftest): every launch of a UNet forward checked on its own against a float64
+restatement of its entry point's contract (include/mobi_engine.h, the docstrings of mobi_amd/ops.py).
+
+`LaunchShadow(monkeypatch)` wraps the `mobi_amd.ops` entry points the model files call as `ops.<name>(...)`: igemm (and with it
+`linear`, which calls the module's igemm), Deferred.finish, groupnorm, layernorm, attention, ctx_attention, ff_geglu and
+two_key_adapter.  Per call it snapshots the operands, runs the original with the same arguments, synchronises, computes the
+fp64 reference on the device from the snapshots (the storage-rounded packed weights, the fp32 bias / rowvec / svec the launch
+read) and compares:
+  * whole-tensor rel-L2 within the bound the form's own unit test asserts (tests/test_gpu_ops.py);
+  * the worst 128-row x 64-channel tile of an image within 4x that bound, a tile's error being
+    |d| / max(|ref tile|, 0.1 x the norm a tile of the tensor's RMS would have);
+  * every output element finite; the inputs unchanged (but a declared in-place residual); the bytes of `out`'s storage
+    outside the view unchanged.
+A split-K launch that returns an `ops.Deferred` stashes its fp64 product on it: the GroupNorm that sums its slabs is checked
+against fp64 GroupNorm of that product (and, with `keep`, the tensor it writes against the product), a reduce launch
+(`finish`) like any launch.  The first launch of every distinct variant tag also has 64 of its rows recomputed on the CPU
+in fp64, which must agree with the device reference to 1e-9 (the device BLAS is not trusted blindly).
+
+Nothing here calls a `mobi_*` entry point: the references are torch float64 (matmul per tap, attention per image and head).
+"""
+import math
+
+import torch
+import torch.nn.functional as F
+
+from tests.golden_cases import record
+from tests.test_gpu_ops import TOL
+
+LN2 = math.log(2.0)
+TILE_ROWS, TILE_COLS = 128, 64
+TILE_FACTOR = 4.0
+CPU_AGREE = 1e-9
+CPU_ROWS = 64
+
+
+def bound_f32_rows(dtype):
+    """OUT_ROWS_F32 (fp32 output of 16-bit operands): test_igemm_epilogues' bound."""
+    return 2e-5 * (100 if dtype == torch.bfloat16 else 1) + 1e-6
+
+
+def bound_gn_f32(dtype):
+    """GN_OUT_F32: test_groupnorm_fp32_source_and_precise_outputs."""
+    return 2e-6
+
+
+def bound_gn_split(dtype):
+    """hi + lo of GN_OUT_SPLIT / SPLIT3: test_groupnorm_fp32_source_and_precise_outputs."""
+    return 2e-6 if dtype == torch.float16 else 2e-5
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# metric
+# ------------------------------------------------------------------------------------------------------------------
+def compare(got, ref):
+    """got, ref: [images, rows, channels] (any float type; compared in fp64 on ref's device) -> dict(rel, tile, where,
+    finite): whole-tensor rel-L2, the worst tile's error and its (image, first row, first channel)."""
+    g = got.to(device=ref.device, dtype=torch.float64)
+    r = ref.double()
+    finite = bool(torch.isfinite(g).all())
+    d = g - r
+    rel = float(d.norm() / r.norm().clamp_min(1e-30))
+    n, rows, cols = r.shape
+    pr, pc = (-rows) % TILE_ROWS, (-cols) % TILE_COLS
+
+    def tiles(t):
+        t = F.pad(t, (0, pc, 0, pr))
+        return t.reshape(n, (rows + pr) // TILE_ROWS, TILE_ROWS, (cols + pc) // TILE_COLS, TILE_COLS).sum(dim=(2, 4))
+
+    ed = tiles(d.square())
+    er = tiles(r.square())
+    cnt = tiles(torch.ones_like(r))
+    rms2 = float(r.square().mean())
+    floor = 0.01 * rms2 * cnt                                # (0.1 x RMS-equivalent tile norm)^2
+    te = (ed / torch.maximum(er, floor).clamp_min(1e-300)).sqrt()
+    te = torch.where(torch.isfinite(te), te, torch.full_like(te, float("inf")))
+    flat = int(torch.argmax(te))
+    tr, tc = te.shape[1], te.shape[2]
+    where = (flat // (tr * tc), (flat // tc) % tr * TILE_ROWS, flat % tc * TILE_COLS)
+    return dict(rel=rel, tile=float(te.max()), where=where, finite=finite)
+
+
+def passes(res, bound):
+    return res["finite"] and res["rel"] < bound and res["tile"] < TILE_FACTOR * bound
+
+
+def _bits(t):
+    return t.view({2: torch.int16, 4: torch.int32, 8: torch.int64, 1: torch.uint8}[t.element_size()])
+
+
+class OutsideView:
+    """The elements of a view's storage that lie outside the view, kept to check that a launch wrote none of them."""
+
+    def __init__(self, t):
+        self.flat = torch.empty(0, dtype=t.dtype, device=t.device).set_(t.untyped_storage())
+        idx = torch.arange(self.flat.numel(), device=t.device).as_strided(t.shape, t.stride(), t.storage_offset())
+        self.mask = torch.ones(self.flat.numel(), dtype=torch.bool, device=t.device)
+        self.mask[idx.reshape(-1)] = False
+        self.any = bool(self.mask.any())
+        self.before = _bits(self.flat)[self.mask].clone() if self.any else None
+
+    def unchanged(self):
+        return not self.any or torch.equal(_bits(self.flat)[self.mask], self.before)
+
+
+def _snap(t):
+    return None if t is None else t.detach().clone()
+
+
+def _same(a, b):
+    return a.shape == b.shape and torch.equal(_bits(a.contiguous()), _bits(b.contiguous()))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# references (fp64; `rows`: flattened output rows to compute, None = all; every operand is moved to `dev`)
+# ------------------------------------------------------------------------------------------------------------------
+def _chunks(total, rows, per):
+    if rows is not None:
+        yield rows
+        return
+    for r0 in range(0, total, per):
+        yield torch.arange(r0, min(total, r0 + per))
+
+
+def igemm_reference(op, rows=None, dev=None):
+    """mobi_igemm's contract: out[m] = epilogue(scale * sum_taps A_tap[m] W_tap^T (+ bias) (+ rowvec[image]) (+ residual[m])),
+    the LayerNorm fold as ((x - mean) rstd) W'^T + bias, GEGLU as value * gelu_erf(gate) of the packed row pairs.
+    -> fp64 [len(rows), cout] (or [images, hout * wout, cout] for rows=None)."""
+    dev = op["x"].device if dev is None else dev
+    to = lambda t: None if t is None else t.to(dev)
+    src = to(op["x"]) if op["x2"] is None else torch.cat([to(op["x"]), to(op["x2"])], dim=3)
+    n, hin, win, c = src.shape
+    kh, kw, st, ph, pw = op["kh"], op["kw"], op["stride"], op["pad_h"], op["pad_w"]
+    hl, wl = (2 * hin, 2 * win) if op["upsample"] else (hin, win)
+    hout, wout, cout, npk, groups = op["hout"], op["wout"], op["cout"], op["n_packed"], op["groups"]
+    w = to(op["w"]).double().reshape(groups, npk, kh * kw, c)          # k = tap * C + c
+    bias = None if op["bias"] is None or op["rowvec_has_bias"] else to(op["bias"]).double()
+    rowvec = None if op["rowvec"] is None else to(op["rowvec"]).double()
+    res = None if op["residual"] is None else to(op["residual"]).double().reshape(-1, cout)
+    hw = hout * wout
+    total = n * hw
+    per = max(256, (1 << 25) // max(kh * kw * c, npk))
+    outs = []
+    for r in _chunks(total, None if rows is None else rows.to(dev), per):
+        r = r.to(dev)
+        img, p = r // hw, r % hw
+        oy, ox = p // wout, p % wout
+        grp = img // (n // groups)
+        acc = torch.zeros((r.numel(), npk), dtype=torch.float64, device=dev)
+        for tap in range(kh * kw):
+            ly, lx = oy * st - ph + tap // kw, ox * st - pw + tap % kw
+            ok = (ly >= 0) & (ly < hl) & (lx >= 0) & (lx < wl)
+            sy, sx = ly.clamp(0, hl - 1), lx.clamp(0, wl - 1)
+            if op["upsample"]:
+                sy, sx = sy // 2, sx // 2
+            a = src[img, sy, sx].double() * ok[:, None]
+            if op["ln"]:
+                mean = a.mean(dim=1, keepdim=True)
+                var = (a - mean).square().mean(dim=1, keepdim=True)
+                a = (a - mean) * (var + op["ln_eps"]).rsqrt()
+            for g in range(groups):
+                sel = grp == g
+                if groups == 1:
+                    acc += a @ w[0, :, tap].T
+                elif bool(sel.any()):
+                    acc[sel] += a[sel] @ w[g, :, tap].T
+        v = acc * op["scale"]
+        if bias is not None:
+            v = v + bias
+        if op["geglu"]:
+            t = v.reshape(r.numel(), npk // 16, 2, 8)
+            v = (t[:, :, 0] * F.gelu(t[:, :, 1])).reshape(r.numel(), cout)
+        if rowvec is not None:
+            v = v + rowvec[img]
+        if res is not None:
+            v = v + res[r]
+        outs.append(v)
+    out = torch.cat(outs)
+    return out if rows is not None else out.reshape(n, hw, cout)
+
+
+def groupnorm_reference(op, rows=None, dev=None):
+    """GroupNorm(32 groups, eps) (+ SiLU) over the channel concat of the sources, fp64 -> [images, hw, C] (rows: those rows,
+    flattened over images)."""
+    dev = op["x"].device if dev is None else dev
+    x = op["x"].to(dev).double()
+    n, c0 = x.shape[0], x.shape[-1]
+    x = x.reshape(n, -1, c0)
+    if op["x2"] is not None:
+        x = torch.cat([x, op["x2"].to(dev).double().reshape(n, x.shape[1], -1)], dim=2)
+    hw, c = x.shape[1], x.shape[2]
+    imgs = torch.arange(n, device=dev) if rows is None else torch.unique(rows.to(dev) // hw)
+    xs = x[imgs].reshape(imgs.numel(), hw, 32, c // 32)
+    mean = xs.mean(dim=(1, 3), keepdim=True)
+    var = (xs - mean).square().mean(dim=(1, 3), keepdim=True)
+    y = ((xs - mean) * (var + op["eps"]).rsqrt()).reshape(imgs.numel(), hw, c)
+    y = y * op["gamma"].to(dev).double() + op["beta"].to(dev).double()
+    if op["silu"]:
+        y = F.silu(y)
+    if rows is None:
+        return y
+    pos = torch.searchsorted(imgs, rows.to(dev) // hw)
+    return y[pos, rows.to(dev) % hw]
+
+
+def layernorm_rows(x, gamma, beta, eps):
+    x = x.double()
+    mean = x.mean(dim=-1, keepdim=True)
+    var = (x - mean).square().mean(dim=-1, keepdim=True)
+    y = (x - mean) * (var + eps).rsqrt()
+    return y if gamma is None else y * gamma.double() + beta.double()
+
+
+def layernorm_reference(op, rows=None, dev=None):
+    dev = op["x"].device if dev is None else dev
+    x = op["x"].to(dev)
+    n, t, c = x.shape
+    sel = x.reshape(n * t, c) if rows is None else x.reshape(n * t, c)[rows.to(dev)]
+    y = layernorm_rows(sel, op["gamma"].to(dev), op["beta"].to(dev), op["eps"])
+    return y.reshape(n, t, c) if rows is None else y
+
+
+def attention_reference(op, rows=None, dev=None):
+    """softmax(q k^T * scale) v per image and head (q_log2_scaled: q carries scale * log2 e, the logits are q.k * ln 2);
+    v_rows: v [N, Tk, C] like k, else V^T [N, C, Tk].  rows: flattened (image, query) rows."""
+    dev = op["q"].device if dev is None else dev
+    q, k, v = op["q"].to(dev), op["k"].to(dev), op["v"].to(dev)
+    n, tq = q.shape[0], q.shape[1]
+    h = op["heads"]
+    c = v.shape[2] if op["v_rows"] else v.shape[1]
+    dh = c // h
+    mult = LN2 if op["q_log2_scaled"] else op["scale"]
+    rsel = torch.arange(n * tq, device=dev) if rows is None else rows.to(dev)
+    out = torch.empty((rsel.numel(), c), dtype=torch.float64, device=dev)
+    for i in range(n):
+        pos = (rsel // tq == i).nonzero().flatten()
+        if pos.numel() == 0:
+            continue
+        kk = k[i, :, :c].double().reshape(-1, h, dh).transpose(0, 1)                  # [H, Tk, dh]
+        vv = (v[i, :, :c].double().reshape(-1, h, dh) if op["v_rows"] else v[i].double().T.reshape(-1, h, dh)).transpose(0, 1)
+        for p0 in range(0, pos.numel(), 1024):
+            pp = pos[p0:p0 + 1024]
+            qq = q[i, rsel[pp] % tq, :c].double().reshape(-1, h, dh).transpose(0, 1)    # [H, R, dh]
+            # (softmax spelled out: torch.softmax in fp64 on the device is off by ~5e-8 rel-L2 over 4,096 keys, measured against
+            #  the CPU; exp / max / sum / matmul agree to 1e-16)
+            s = qq @ kk.transpose(1, 2) * mult
+            e = torch.exp(s - s.amax(dim=-1, keepdim=True))
+            out[pp] = ((e @ vv) / e.sum(dim=-1, keepdim=True)).transpose(0, 1).reshape(-1, c)
+    return out if rows is not None else out.reshape(n, tq, c)
+
+
+def ctx_attention_reference(op, rows=None, dev=None):
+    dev = op["q"].device if dev is None else dev
+    q, k, v = op["q"].to(dev), op["k"].to(dev), op["v"].to(dev)
+    return attention_reference(dict(q=q, k=k, v=v, heads=op["heads"], scale=op["scale"], v_rows=True, q_log2_scaled=False),
+                               rows, dev)
+
+
+def decode_ff_geglu(buf, c, hidden, dtype):
+    """The chunk images of mobi_ff_geglu (include/mobi_engine.h, the w_packed layout) -> (W1 [2 hidden, c], b1 [2 hidden]
+    fp32, W2 [c, hidden]) as the storage type / fp32: index arithmetic on the documented formula, not the packer."""
+    ks_n, mt_n, nch = c // 16, c // 32, hidden // 32
+    dev = buf.device
+    ar = lambda k: torch.arange(k, device=dev)
+    n1 = nch * 2 * ks_n * 512
+    img1 = buf[:2 * n1].view(dtype).reshape(nch, 2, ks_n, 64, 8)
+    rest = buf[2 * n1:].reshape(nch, -1)
+    img2 = rest[:, :2 * mt_n * 1024].contiguous().view(dtype).reshape(nch, mt_n, 2, 64, 8)
+    bias = rest[:, 2 * mt_n * 1024:].contiguous().view(torch.float32).reshape(nch, 256)
+    lane, j = ar(64), ar(8)
+    # first product: element j of fragment (t, ks), lane l = W1[t hidden + 32 chunk + (l & 31)][16 ks + 8 (l >> 5) + j]
+    r1 = ar(2)[None, :, None, None, None] * hidden + ar(nch)[:, None, None, None, None] * 32 + (lane & 31)[None, None, None, :, None]
+    c1 = ar(ks_n)[None, None, :, None, None] * 16 + (lane >> 5)[None, None, None, :, None] * 8 + j[None, None, None, None, :]
+    w1 = torch.zeros((2 * hidden, c), dtype=dtype, device=dev)
+    w1[r1.expand_as(img1), c1.expand_as(img1)] = img1
+    # second product: fragment 2 m + s: element j = W2[32 m + (l & 31)][32 chunk + 16 s + 8 (j >> 2) + 4 (l >> 5) + (j & 3)]
+    r2 = ar(mt_n)[None, :, None, None, None] * 32 + (lane & 31)[None, None, None, :, None]
+    c2 = (ar(nch)[:, None, None, None, None] * 32 + ar(2)[None, None, :, None, None] * 16 + (j >> 2)[None, None, None, None, :] * 8
+          + (lane >> 5)[None, None, None, :, None] * 4 + (j & 3)[None, None, None, None, :])
+    w2 = torch.zeros((c, hidden), dtype=dtype, device=dev)
+    w2[r2.expand_as(img2), c2.expand_as(img2)] = img2
+    b1 = torch.cat([bias[:, :32].reshape(hidden), bias[:, 32:64].reshape(hidden)])
+    return w1, b1, w2
+
+
+def ff_geglu_reference(op, rows=None, dev=None):
+    """((x' W1v^T + b1v) * gelu_erf(x' W1g^T + b1g)) W2^T + b2 (+ residual), x' = x or LayerNorm(x) -> [images, T, c]."""
+    dev = op["x"].device if dev is None else dev
+    x = op["x"].to(dev)
+    c = x.shape[-1]
+    xr = x.reshape(-1, c)
+    w1, b1, w2 = (t.to(dev).double() for t in op["dec"])
+    hidden = w2.shape[1]
+    b2 = None if op["b2"] is None else op["b2"].to(dev).double()
+    res = None if op["residual"] is None else op["residual"].to(dev).reshape(-1, c)
+    outs = []
+    for r in _chunks(xr.shape[0], None if rows is None else rows.to(dev), 16384):
+        r = r.to(dev)
+        a = xr[r].double()
+        if op["ln"] is not None:
+            g, b, eps = op["ln"]
+            a = layernorm_rows(a, g.to(dev), b.to(dev), eps)
+        pre = a @ w1.T + b1
+        y = (pre[:, :hidden] * F.gelu(pre[:, hidden:])) @ w2.T
+        if b2 is not None:
+            y = y + b2
+        if res is not None:
+            y = y + res[r].double()
+        outs.append(y)
+    out = torch.cat(outs)
+    return out if rows is not None else out.reshape(x.shape[0], -1, c)
+
+
+def two_key_adapter_reference(x, a, a_sum, c, u, b, eps):
+    """mobi_two_key_adapter's contract, fp64: x + b + sum_h sigmoid(rstd (x . a_h - mean a_sum_h) + c_h) u_h with the token's
+    LayerNorm statistics.  x [N, T, C]; a, u [N, H, C]; a_sum, c [N, H]; b [N, C] -> [N, T, C]."""
+    x, a, a_sum, c, u, b = (t.double() for t in (x, a, a_sum, c, u, b))
+    mean = x.mean(-1, keepdim=True)
+    rstd = ((x - mean).square().mean(-1, keepdim=True) + eps).rsqrt()
+    z = rstd * (torch.einsum("ntc,nhc->nth", x, a) - mean * a_sum[:, None, :]) + c[:, None, :]
+    return x + b[:, None, :] + torch.einsum("nth,nhc->ntc", torch.sigmoid(z), u)
+
+
+def two_key_adapter_op_reference(op, rows=None, dev=None):
+    dev = op["x"].device if dev is None else dev
+    x = op["x"].to(dev)
+    n, t, ch = x.shape
+    if rows is None:
+        return two_key_adapter_reference(x, *(op[k].to(dev) for k in ("a", "a_sum", "c", "u", "b")), op["eps"])
+    rows = rows.to(dev)
+    img = rows // t
+    y = two_key_adapter_reference(x.reshape(n * t, 1, ch)[rows], *(op[k].to(dev)[img] for k in ("a", "a_sum", "c", "u", "b")),
+                                  op["eps"])
+    return y.reshape(-1, ch)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the shadow
+# ------------------------------------------------------------------------------------------------------------------
+class LaunchShadow:
+    """Context manager: `with LaunchShadow(monkeypatch) as sh: net(...)`; then `sh.failures` (strings), `sh.records` (one
+    dict per compared launch), `sh.counts` (launches shadowed per profiler kind)."""
+
+    def __init__(self, monkeypatch, verbose=False, label="", cpu_check=True, seed=0):
+        from mobi_amd import ops
+        self.ops, self.mp, self.verbose, self.label, self.cpu_check = ops, monkeypatch, verbose, label, cpu_check
+        self.records, self.failures, self.counts = [], [], {}
+        self.cpu_checked = set()
+        self.pending = {}
+        self.gen = torch.Generator().manual_seed(seed)
+
+    # -- plumbing ------------------------------------------------------------------------------------------------------
+    def __enter__(self):
+        ops = self.ops
+        if ops._PROFILE is None:
+            self.sink = []
+            self.mp.setattr(ops, "_PROFILE", self.sink)
+        else:
+            self.sink = ops._PROFILE
+        orig = {k: getattr(ops, k) for k in ("igemm", "groupnorm", "layernorm", "attention", "ctx_attention", "ff_geglu",
+                                               "two_key_adapter")}
+        orig_finish = ops.Deferred.finish
+        self.orig = orig
+        sh = self
+        self.mp.setattr(ops, "igemm", lambda *a, **k: sh._igemm(orig["igemm"], *a, **k))
+        self.mp.setattr(ops, "groupnorm", lambda *a, **k: sh._groupnorm(orig["groupnorm"], *a, **k))
+        self.mp.setattr(ops, "layernorm", lambda *a, **k: sh._layernorm(orig["layernorm"], *a, **k))
+        self.mp.setattr(ops, "attention", lambda *a, **k: sh._attention(orig["attention"], *a, **k))
+        self.mp.setattr(ops, "ctx_attention", lambda *a, **k: sh._ctx_attention(orig["ctx_attention"], *a, **k))
+        self.mp.setattr(ops, "ff_geglu", lambda *a, **k: sh._ff_geglu(orig["ff_geglu"], *a, **k))
+        self.mp.setattr(ops, "two_key_adapter", lambda *a, **k: sh._two_key_adapter(orig["two_key_adapter"], *a, **k))
+        self.mp.setattr(ops.Deferred, "finish", lambda d: sh._finish(orig_finish, d))
+        return self
+
+    def __exit__(self, *exc):
+        self.mp.undo()
+        if exc[0] is None and self.pending:
+            self.failures.append(f"{len(self.pending)} split-K launches whose partial sums nobody consumed")
+        return False
+
+    def _tag(self, n0, kind):
+        """The profiler record the original appended (ops._Timed), or ''."""
+        for rec in self.sink[n0:]:
+            if rec[0] == kind:
+                return rec[5]
+        return ""
+
+    def _count(self, kind):
+        self.counts[kind] = self.counts.get(kind, 0) + 1
+
+    def _fail(self, msg):
+        self.failures.append(f"{self.label} {msg}")
+
+    def _inputs_unchanged(self, what, pairs):
+        for name, live, snap in pairs:
+            if live is not None and not _same(live, snap):
+                self._fail(f"{what}: input {name} changed")
+
+    def _cpu_agree(self, key, fn, op, dev_ref, total):
+        """First launch of a variant: 64 rows (first, last, 62 random) in fp64 on the CPU against the device reference."""
+        if not self.cpu_check or key in self.cpu_checked:
+            return
+        self.cpu_checked.add(key)
+        rnd = torch.randperm(max(total - 2, 1), generator=self.gen)[:CPU_ROWS - 2] + 1
+        rows = torch.unique(torch.cat([torch.tensor([0, total - 1]), rnd.clamp(max=total - 1)]))
+        cpu = fn(op, rows=rows, dev=torch.device("cpu"))
+        dev = dev_ref.reshape(total, -1)[rows.to(dev_ref.device)].cpu()
+        err = float((cpu - dev).norm() / cpu.norm().clamp_min(1e-300))
+        if not err <= CPU_AGREE:
+            self._fail(f"{key}: device fp64 reference disagrees with the CPU on {rows.numel()} rows: {err:.3e}")
+
+    def _judge(self, kind, tag, got, ref, bound, extra=""):
+        res = compare(got, ref)
+        ok = passes(res, bound)
+        rec = dict(kind=kind, tag=tag, bound=bound, extra=extra, **res)
+        self.records.append(rec)
+        name = f"{kind} {tag} {extra}".strip()
+        record(f"shadow {self.label} {name}", res["rel"], bound)
+        record(f"shadow {self.label} {name} worst_tile", res["tile"], TILE_FACTOR * bound)
+        if self.verbose:
+            print(f"[shadow {self.label}] {kind:16s} {tag} {extra} rel={res['rel']:.3e} tile={res['tile']:.3e} "
+                  f"at(img,row,col)={res['where']} bound={bound:.1e}{'' if ok else '  FAIL'}")
+        if not ok:
+            self._fail(f"{name}: rel-L2 {res['rel']:.3e}, worst tile {res['tile']:.3e} at {res['where']}, finite "
+                       f"{res['finite']} (bound {bound:.1e}, tile bound {TILE_FACTOR * bound:.1e})")
+        return res
+
+    # -- igemm ---------------------------------------------------------------------------------------------------------
+    def _igemm(self, orig, x, pw, *, x2=None, stride=1, pad=None, upsample=False, hout=None, wout=None, rowvec=None,
+               rowvec_has_bias=False, residual=None, out=None, out_mode=0, scale=1.0, weight_per_image=False,
+               w_group_stride=0, split_k=None, groups=1, defer=None):
+        ops = self.ops
+        x, x2, residual = ops.finished(x), ops.finished(x2), ops.finished(residual)
+        if weight_per_image or w_group_stride or pw.k_order:
+            raise NotImplementedError("launch shadow: per-image weights / chunk-major k order are not forms of the UNet step")
+        n, hin, win, _ = x.shape
+        ph, pw_ = (pw.kh // 2, pw.kw // 2) if pad is None else pad
+        hl, wl = (hin * 2, win * 2) if upsample else (hin, win)
+        ho = (hl + 2 * ph - pw.kh) // stride + 1 if hout is None else hout
+        wo = (wl + 2 * pw_ - pw.kw) // stride + 1 if wout is None else wout
+        cout, npk = (pw.cout // groups, pw.n_packed // groups) if groups > 1 else (pw.cout, pw.n_packed)
+        op = dict(x=_snap(x), x2=_snap(x2), w=pw.w, bias=pw.bias, kh=pw.kh, kw=pw.kw, stride=stride, pad_h=ph, pad_w=pw_,
+                  upsample=upsample, hout=ho, wout=wo, cout=cout, n_packed=npk, groups=groups, geglu=pw.geglu,
+                  ln=pw.svec is not None, ln_eps=pw.ln_eps, scale=scale, rowvec=_snap(rowvec), rowvec_has_bias=rowvec_has_bias,
+                  residual=None if residual is None else residual.detach().reshape(n, ho * wo, cout).clone())
+        ins = [("x", x, op["x"]), ("x2", x2, op["x2"]), ("rowvec", rowvec, op["rowvec"])]
+        in_place = residual is not None and out is not None and residual.data_ptr() == out.data_ptr()
+        if residual is not None and not in_place:
+            ins.append(("residual", residual, residual.detach().clone()))
+        wsnap = [pw.w.clone(), None if pw.bias is None else pw.bias.clone(), None if pw.svec is None else pw.svec.clone()]
+        outside = OutsideView(out) if out is not None else None
+        n0 = len(self.sink)
+        y = orig(x, pw, x2=x2, stride=stride, pad=pad, upsample=upsample, hout=hout, wout=wout, rowvec=rowvec,
+                 rowvec_has_bias=rowvec_has_bias, residual=residual, out=out, out_mode=out_mode, scale=scale, split_k=split_k,
+                 groups=groups, defer=defer)
+        torch.cuda.synchronize()
+        self._count("igemm")
+        tag = self._tag(n0, "igemm")
+        self._inputs_unchanged(tag, ins + [("weight", pw.w, wsnap[0]), ("bias", pw.bias, wsnap[1]), ("svec", pw.svec, wsnap[2])])
+        if outside is not None and not outside.unchanged():
+            self._fail(f"{tag}: wrote outside its out view")
+        ref = igemm_reference(op)
+        self._cpu_agree(tag, igemm_reference, op, ref, ref.shape[0] * ref.shape[1])
+        dtype = x.dtype
+        bound = bound_f32_rows(dtype) if out_mode == ops.OUT_ROWS_F32 else TOL[dtype]
+        if isinstance(y, ops.Deferred):
+            y._shadow = dict(ref=ref, tag=tag, bound=bound)
+            self.pending[id(y)] = y
+            return y
+        got = y.transpose(1, 2) if out_mode == ops.OUT_TRANSPOSED else y.reshape(n, ho * wo, cout)
+        self._judge("igemm", tag, got, ref, bound)
+        return y
+
+    def _finish(self, orig, d):
+        if d.done:
+            return orig(d)
+        n0 = len(self.sink)
+        t = orig(d)
+        torch.cuda.synchronize()
+        self._count("split_finish")
+        if self.pending.pop(id(d), None) is None:
+            self._fail("a reduce launch of a split-K launch the shadow did not see")
+            return t
+        s = d._shadow
+        d._shadow_finished = True
+        self._judge("split_finish", self._tag(n0, "split_finish"), t.reshape(t.shape[0], -1, t.shape[3]), s["ref"], s["bound"],
+                    extra=f"of [{s['tag']}]")
+        return t
+
+    # -- normalisation -------------------------------------------------------------------------------------------------
+    def _groupnorm(self, orig, x, gamma, beta, eps, silu, x2=None, out_mode=0, dtype=None):
+        ops = self.ops
+        x2 = ops.finished(x2)
+        d = x if isinstance(x, ops.Deferred) else None
+        d_shape, d_dtype = (tuple(d.shape), d.dtype) if d is not None else (None, None)     # (tensor is dropped after "drop")
+        snap = None if d is not None else _snap(x)
+        x2s = _snap(x2)
+        n0 = len(self.sink)
+        y = orig(x, gamma, beta, eps, silu, x2=x2, out_mode=out_mode, dtype=dtype)
+        torch.cuda.synchronize()
+        self._count("groupnorm")
+        tag = self._tag(n0, "groupnorm")
+        extra = ""
+        if d is not None:
+            s = d._shadow
+            if getattr(d, "_shadow_finished", False):          # the GroupNorm ran the reduce launch first (checked there)
+                src = d.tensor
+            else:                                              # it summed the slabs: against GroupNorm of the fp64 product
+                self.pending.pop(id(d), None)
+                src = s["ref"].reshape(d_shape)
+                extra = f"slabs of [{s['tag']}]"
+                if d.keep:
+                    self._judge("igemm", s["tag"], d.tensor.reshape(s["ref"].shape), s["ref"], s["bound"], extra="summed by groupnorm")
+            t_dtype = d_dtype
+        else:
+            src = x
+            self._inputs_unchanged(tag, [("x", x, snap)])
+            t_dtype = dtype if x.dtype == torch.float32 else x.dtype
+        self._inputs_unchanged(tag, [("x2", x2, x2s)])
+        op = dict(x=src, x2=x2s, gamma=gamma, beta=beta, eps=eps, silu=silu)
+        ref = groupnorm_reference(op)
+        self._cpu_agree(f"groupnorm {tag} {out_mode} {silu}", groupnorm_reference, op, ref, ref.shape[0] * ref.shape[1])
+        n, c = ref.shape[0], ref.shape[2]
+        y3 = y.reshape(n, ref.shape[1], -1)
+        if out_mode == ops.GN_OUT_T:
+            self._judge("groupnorm", tag, y3, ref, TOL[t_dtype], extra)
+        elif out_mode == ops.GN_OUT_F32:
+            self._judge("groupnorm", tag, y3, ref, bound_gn_f32(t_dtype), extra + " f32")
+        else:
+            self._judge("groupnorm", tag, y3[..., :c].double() + y3[..., c:2 * c].double(), ref, bound_gn_split(t_dtype),
+                        extra + " hi+lo")
+            self._judge("groupnorm", tag, y3[..., :c], ref, TOL[t_dtype], extra + " hi")
+            if out_mode == ops.GN_OUT_SPLIT3 and not torch.equal(y3[..., 2 * c:], y3[..., :c]):
+                self._fail(f"groupnorm {tag}: SPLIT3's third part is not hi")
+        return y
+
+    def _layernorm(self, orig, x, gamma, beta, eps=1e-5):
+        snap = _snap(x)
+        y = orig(x, gamma, beta, eps)
+        torch.cuda.synchronize()
+        self._count("layernorm")
+        tag = f"n={x.shape[0]} t={x.shape[1]} c={x.shape[2]} strided={int(not x.is_contiguous())}"
+        self._inputs_unchanged(tag, [("x", x, snap)])
+        op = dict(x=snap, gamma=gamma, beta=beta, eps=eps)
+        ref = layernorm_reference(op)
+        self._cpu_agree("layernorm " + tag, layernorm_reference, op, ref, ref.shape[0] * ref.shape[1])
+        self._judge("layernorm", tag, y, ref, TOL[x.dtype])
+        return y
+
+    # -- attention -----------------------------------------------------------------------------------------------------
+    def _attention(self, orig, q, k, v, heads, scale, v_rows=False, q_log2_scaled=False):
+        snaps = [_snap(t) for t in (q, k, v)]
+        n0 = len(self.sink)
+        y = orig(q, k, v, heads, scale, v_rows=v_rows, q_log2_scaled=q_log2_scaled)
+        torch.cuda.synchronize()
+        self._count("attention")
+        tag = self._tag(n0, "attention") + f" v_rows={int(v_rows)} log2q={int(q_log2_scaled)}"
+        self._inputs_unchanged(tag, [("q", q, snaps[0]), ("k", k, snaps[1]), ("v", v, snaps[2])])
+        op = dict(q=snaps[0], k=snaps[1], v=snaps[2], heads=heads, scale=scale, v_rows=v_rows, q_log2_scaled=q_log2_scaled)
+        ref = attention_reference(op)
+        self._cpu_agree("attention " + tag, attention_reference, op, ref, ref.shape[0] * ref.shape[1])
+        self._judge("attention", tag, y, ref, TOL[q.dtype] * (1.0 if q_log2_scaled else 1.5))
+        return y
+
+    def _ctx_attention(self, orig, q, k, v, heads, scale):
+        snaps = [_snap(t) for t in (q, k, v)]
+        y = orig(q, k, v, heads, scale)
+        torch.cuda.synchronize()
+        self._count("ctx_attention")
+        tag = f"n={q.shape[0]} tq={q.shape[1]} tk={k.shape[1]} heads={heads}"
+        self._inputs_unchanged(tag, [("q", q, snaps[0]), ("k", k, snaps[1]), ("v", v, snaps[2])])
+        op = dict(q=snaps[0], k=snaps[1], v=snaps[2], heads=heads, scale=scale)
+        ref = ctx_attention_reference(op)
+        self._cpu_agree("ctx_attention " + tag, ctx_attention_reference, op, ref, ref.shape[0] * ref.shape[1])
+        self._judge("ctx_attention", tag, y, ref, TOL[q.dtype])
+        return y
+
+    # -- fused feed-forward, adapter -----------------------------------------------------------------------------------
+    def _ff_geglu(self, orig, x, pf, residual=None, out=None, ln=None):
+        xs = _snap(x)
+        rs = xs if residual is not None and residual.data_ptr() == x.data_ptr() else _snap(residual)
+        in_place = residual is not None and out is not None and residual.data_ptr() == out.data_ptr()
+        bufs = pf.buf.clone()
+        n0 = len(self.sink)
+        y = orig(x, pf, residual=residual, out=out, ln=ln)
+        torch.cuda.synchronize()
+        self._count("ff_geglu")
+        tag = self._tag(n0, "ff_geglu") + f" ln={int(ln is not None)} residual={int(residual is not None)}"
+        ins = [("w_packed", pf.buf, bufs)]
+        if not (out is not None and out.data_ptr() == x.data_ptr()):
+            ins.append(("x", x, xs))
+        if residual is not None and not in_place:
+            ins.append(("residual", residual, rs))
+        self._inputs_unchanged(tag, ins)
+        op = dict(x=xs, residual=rs, b2=pf.b2, ln=ln, dec=decode_ff_geglu(bufs, pf.c, pf.hidden, pf.dtype))
+        ref = ff_geglu_reference(op)
+        self._cpu_agree("ff_geglu " + tag, ff_geglu_reference, op, ref, ref.shape[0] * ref.shape[1])
+        self._judge("ff_geglu", tag, y.reshape(ref.shape), ref, TOL[x.dtype])
+        return y
+
+    def _two_key_adapter(self, orig, x, a, a_sum, c, u, b, eps, out=None, ln_pair=None):
+        snaps = {k: _snap(t) for k, t in (("x", x), ("a", a), ("a_sum", a_sum), ("c", c), ("u", u), ("b", b))}
+        outside = OutsideView(out) if out is not None else None
+        r = orig(x, a, a_sum, c, u, b, eps, out=out, ln_pair=ln_pair)
+        torch.cuda.synchronize()
+        self._count("two_key_adapter")
+        y, lns = (r, None) if ln_pair is None else r
+        tag = f"n={x.shape[0]} t={x.shape[1]} c={x.shape[2]} in_place={int(out is not None)} ln_pair={int(ln_pair is not None)}"
+        live = {"x": x, "a": a, "a_sum": a_sum, "c": c, "u": u, "b": b}
+        self._inputs_unchanged(tag, [(k, live[k], snaps[k]) for k in snaps if not (k == "x" and out is not None
+                                                                                      and out.data_ptr() == x.data_ptr())])
+        if outside is not None and not outside.unchanged():
+            self._fail(f"two_key_adapter {tag}: wrote outside its out view")
+        op = dict(snaps, eps=eps)
+        ref = two_key_adapter_op_reference(op)
+        self._cpu_agree("two_key_adapter " + tag, two_key_adapter_op_reference, op, ref, ref.shape[0] * ref.shape[1])
+        self._judge("two_key_adapter", tag, y, ref, TOL[x.dtype])
+        if lns is not None:
+            (g0, b0), (g1, b1), ln_eps = ln_pair
+            for i, (got, g, bb) in enumerate(((lns[0], g0, b0), (lns[1], g1, b1))):
+                want = layernorm_rows(ref[i::2], g, bb, ln_eps)
+                self._judge("two_key_adapter", tag, got, want, TOL[x.dtype], extra=f"ln_pair[{i}]")
+        return r

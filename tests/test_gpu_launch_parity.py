@@ -1,0 +1,183 @@
+"""Every launch of the production UNet step against fp64, at the shapes the product runs (`-m gpu`).
+
+Configurations: mobi_nusc_512 (latent 64 x 64, UNet batch 16 = 8 camera / lidar pairs), mobi_nusc_256 (32 x 32, batch 8) and
+the guidance batch of the shipped PLMS / CFG-5 invocation (64 x 64, batch 32: [uncond ; cond] built as ddim.py:_eps builds it),
+each in fp16 and bf16 storage, on the full-width net of tests/test_gpu_production.py.
+
+  * launch shadow (tests/launch_shadow.py): every igemm / split-K reduce / GroupNorm / LayerNorm / attention / ff_geglu /
+    two-key-adapter launch of one forward against a float64 restatement of its contract on the operands it read, within the
+    bound its unit test in tests/test_gpu_ops.py asserts, its worst 128 x 64 tile within 4x that, finite, inputs and the
+    storage outside its view untouched; the shadow must have seen every launch the profiler saw (row_chain aside: its
+    operations are covered below);
+  * block shadow: a second forward with ops.DEFER_SPLIT = False (bit-identical, test_full_width_forward_vs_oracle) whose
+    every input / middle / output block is compared with oracle/unet.py::_run_block on the block's engine input, in float64
+    on the device, pair by pair, with the fp32 master weights: row_chain, its adapter image, the routing thresholds and the
+    Python glue between launches, within TOL_FULL per block and 1.4 TOL_FULL per pair.
+A routing change that removes one of the kernel forms REQUIRED_FORMS lists must update that list explicitly.
+"""
+import collections
+import functools
+import os
+
+import pytest
+import torch
+
+from oracle import unet as ounet, weights as W
+from tests.golden_cases import record
+from tests.launch_shadow import LaunchShadow, compare
+from tests.test_gpu_production import TOL_FULL, _full_width_net, _set
+
+pytestmark = pytest.mark.gpu
+
+DT = [torch.float16, torch.bfloat16]
+CONFIGS = {"nusc512_b16": (64, 16, False), "nusc256_b8": (32, 8, False), "nusc512_guidance_b32": (64, 16, True)}
+# kernel forms the step must route to somewhere across the configurations (kern= of the igemm variant tag, ops.igemm)
+REQUIRED_FORMS = ("ring256", "ring128", "pingpong", "small")
+
+
+def _inputs(side, n, guidance):
+    """(input parts [x, inpaint image, mask] fp32 NCHW as the samplers pass them, timesteps, context) on the device."""
+    from tests import oracle_cases as oc
+    x, ctx, t = oc.prod_inputs(side, n)
+    parts = [x[:, :4], x[:, 4:8], x[:, 8:9]]
+    if guidance:                                               # ddim.py:_eps: [uncond ; cond]
+        uc = W.synth_input(f"prod.uc{side}", (n, 2, 768))
+        parts = [torch.cat([p] * 2) for p in parts]
+        t = torch.cat([t] * 2)
+        ctx = torch.cat([uc, ctx])
+    return [p.float().contiguous().cuda() for p in parts], t.cuda(), ctx.cuda()
+
+
+def _dname(dtype):
+    return "fp16" if dtype == torch.float16 else "bf16"
+
+
+@functools.lru_cache(maxsize=None)
+def _launch_run(dtype, name):
+    from mobi_amd import ops
+    _set(dtype)
+    net = _full_width_net()
+    xs, t, ctx = _inputs(*CONFIGS[name])
+    sink = []
+    label = f"{name} {_dname(dtype)}"
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setattr(ops, "_PROFILE", sink)
+        assert ops.DEFER_SPLIT
+        with LaunchShadow(mp, verbose=True, label=label) as sh, torch.no_grad():
+            net(xs, t, context=ctx)
+        torch.cuda.synchronize()
+    kinds = collections.Counter(r[0] for r in sink)
+    return dict(failures=list(sh.failures), counts=dict(sh.counts), kinds=dict(kinds), records=list(sh.records))
+
+
+@pytest.mark.parametrize("dtype", DT, ids=_dname)
+@pytest.mark.parametrize("name", list(CONFIGS))
+def test_launch_shadow(dtype, name):
+    r = _launch_run(dtype, name)
+    for kind, count in r["kinds"].items():
+        if kind != "row_chain":
+            assert r["counts"].get(kind, 0) == count, (kind, count, r["counts"])
+    assert r["counts"].get("igemm", 0) > 0 and r["counts"].get("attention", 0) > 0
+    assert not r["failures"], "\n".join(r["failures"][:40])
+
+
+def test_launch_shadow_covers_the_routing():
+    """Across the configurations: each kernel form of REQUIRED_FORMS, a LayerNorm-folded instantiation, a split-K launch
+    whose slabs a GroupNorm summed and one finished by its reduce launch were compared at least once.  Also prints the
+    worst rel-L2 / tile per launch family, dtype and configuration."""
+    recs = [(dtype, name, rec) for dtype in DT for name in CONFIGS for rec in _launch_run(dtype, name)["records"]]
+    kerns = {rec["tag"].split()[0][5:] for _, _, rec in recs if rec["kind"] == "igemm" and rec["tag"].startswith("kern=")}
+    for form in REQUIRED_FORMS:
+        assert form in kerns, (form, sorted(kerns))
+    assert any(k.endswith("_ln") for k in kerns), sorted(kerns)
+    assert any(rec["kind"] == "groupnorm" and rec["extra"].startswith("slabs of") for _, _, rec in recs)
+    assert any(rec["kind"] == "split_finish" for _, _, rec in recs)
+    worst = {}
+    for dtype, name, rec in recs:
+        fam = rec["kind"] + (" " + rec["tag"].split()[0][5:] if rec["tag"].startswith("kern=") else "")
+        if rec["kind"] == "groupnorm" and rec["extra"]:
+            fam += " (split-K slabs)"
+        if rec["kind"] == "attention":
+            fam += " dh=" + rec["tag"].split("dh=")[1].split()[0]
+        key = (name, _dname(dtype), fam)
+        w = worst.setdefault(key, [0.0, 0.0, 0, rec["bound"]])
+        w[0], w[1], w[2] = max(w[0], rec["rel"]), max(w[1], rec["tile"]), w[2] + 1
+    lines = [f"{'configuration':22s} {'dtype':5s} {'launch family':34s} {'launches':>8s} {'worst rel-L2':>12s} "
+             f"{'worst tile':>10s} {'bound':>7s}"]
+    for (name, dn, fam), (rel, tile, cnt, bound) in sorted(worst.items()):
+        lines.append(f"{name:22s} {dn:5s} {fam:34s} {cnt:8d} {rel:12.3e} {tile:10.3e} {bound:7.1e}")
+    print("\n".join(lines))
+    path = os.environ.get("MOBI_LAUNCH_PARITY_TABLE")
+    if path:
+        with open(path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+# ---- block shadow ------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _sd64():
+    return {k: v.detach().double() for k, v in _full_width_net().state_dict().items()}
+
+
+@functools.lru_cache(maxsize=None)
+def _block_run(dtype, name):
+    from mobi_amd import ops
+    from mobi_amd.ldm.modules.diffusionmodules.openaimodel import TimestepEmbedSequential
+    _set(dtype)
+    net = _full_width_net()
+    cfg = ounet.UNetConfig()
+    sd = _sd64()
+    xs, t, ctx = _inputs(*CONFIGS[name])
+    inputs, middle, outputs = ounet.unet_layout(cfg)
+    blocks = {id(m): (f"input_blocks.{i}", inputs[i]) for i, m in enumerate(net.input_blocks)}
+    blocks[id(net.middle_block)] = ("middle_block", middle)
+    blocks.update({id(m): (f"output_blocks.{i}", outputs[i]) for i, m in enumerate(net.output_blocks)})
+    emb = ounet.timestep_embedding(t, cfg.model_channels, dtype=torch.float64)
+    emb = ounet._lin(sd, "time_embed.2", torch.nn.functional.silu(ounet._lin(sd, "time_embed.0", emb)))
+    ctx64 = ctx.double()
+    orig = TimestepEmbedSequential.forward
+    results = []
+
+    def nchw64(v):
+        return ops.finished(v).double().permute(0, 3, 1, 2)
+
+    def forward(self, x, emb_, context=None, skip=None, then_groupnorm=False):
+        prefix, layers = blocks[id(self)]
+        h = torch.cat([s.double() for s in x], dim=1) if isinstance(x, (list, tuple)) else nchw64(x)
+        if skip is not None:
+            h = torch.cat([h, nchw64(skip)], dim=1)               # the un-materialised skip concat, openaimodel.py:893
+        y = orig(self, x, emb_, context, skip=skip, then_groupnorm=then_groupnorm)
+        got = ops.finished(y).double()
+        torch.cuda.synchronize()
+        with torch.backends.cudnn.flags(enabled=False):
+            ref = torch.cat([ounet._run_block(sd, prefix, layers, h[i:i + 2], emb[i:i + 2], ctx64[i:i + 2], cfg)
+                             for i in range(0, h.shape[0], 2)]).permute(0, 2, 3, 1)
+        pairs = [compare(got[i:i + 2].reshape(1, -1, got.shape[3]), ref[i:i + 2].reshape(1, -1, ref.shape[3]))["rel"]
+                 for i in range(0, got.shape[0], 2)]
+        whole = compare(got.reshape(1, -1, got.shape[3]), ref.reshape(1, -1, ref.shape[3]))
+        results.append(dict(block=prefix, rel=whole["rel"], finite=whole["finite"], worst_pair=max(pairs),
+                            pair=pairs.index(max(pairs))))
+        return y
+
+    with pytest.MonkeyPatch.context() as mp, torch.no_grad():
+        mp.setattr(ops, "DEFER_SPLIT", False)
+        mp.setattr(TimestepEmbedSequential, "forward", forward)
+        net(xs, t, context=ctx)
+    return results
+
+
+@pytest.mark.parametrize("dtype", DT, ids=_dname)
+@pytest.mark.parametrize("name", list(CONFIGS))
+def test_block_shadow(dtype, name):
+    res = _block_run(dtype, name)
+    assert len(res) == len(_full_width_net().input_blocks) + 1 + len(_full_width_net().output_blocks)
+    tol = TOL_FULL[dtype]
+    bad = []
+    for r in res:
+        print(f"[block {name} {_dname(dtype)}] {r['block']:17s} rel={r['rel']:.3e} worst pair={r['worst_pair']:.3e} "
+              f"(pair {r['pair']})")
+        record(f"block {name} {r['block']}", r["rel"], tol)
+        record(f"block {name} {r['block']} worst_pair", r["worst_pair"], 1.4 * tol)
+        if not (r["finite"] and r["rel"] < tol and r["worst_pair"] < 1.4 * tol):
+            bad.append(r)
+    assert not bad, bad

@@ -1030,11 +1030,9 @@ def test_two_key_adapter(ops, dtype, n, t, c, heads, strided, tune):
     u = W.synth_input(name + ".u", (n, heads, c))
     b = W.synth_input(name + ".b", (n, c))
     cc = W.synth_input(name + ".c", (n, heads))
+    from tests.launch_shadow import two_key_adapter_reference
     xs = xf[::2] if strided else xf
-    mean = xs.mean(-1, keepdim=True)
-    rstd = (xs.var(-1, unbiased=False, keepdim=True) + 1e-5).rsqrt()
-    z = rstd * (torch.einsum("ntc,nhc->nth", xs, a) - mean * a.sum(-1)[:, None, :]) + cc[:, None, :]
-    ref = xs + b[:, None, :] + torch.einsum("nth,nhc->ntc", torch.sigmoid(z), u)
+    ref = two_key_adapter_reference(xs, a, a.sum(-1), cc, u, b, 1e-5)
     view = xd[::2] if strided else xd
     y = ops.two_key_adapter(view, a.cuda(), a.sum(-1).contiguous().cuda(), cc.cuda(), u.cuda(), b.cuda(), 1e-5)
     assert rel(y.float(), ref) < TOL[dtype]

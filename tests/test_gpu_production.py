@@ -3,9 +3,10 @@ reference ... within a stated fp16 tolerance"), inside the driver-run `-m gpu` s
 
   * mobi_nusc_512's full-width UNet (1.04 B parameters) at the benched shape -- latent 64x64, UNet batch 16 = 8
     camera/lidar pairs -- against the CPU oracle evaluated pair by pair (objects are independent; a pair is the unit of
-    coupling, ldm/modules/attention.py:245-263 of the reference); fp16 and bf16 storage.  This is the only place the
-    ping-pong igemm at m = 65,536 / K = 2,880 ... 23,040, its 256-block persistent walk and dh = 40 attention inside
-    the model are compared with something other than themselves.
+    coupling, ldm/modules/attention.py:245-263 of the reference); fp16 and bf16 storage.  The whole forward in one norm:
+    every launch of it at these shapes (the ping-pong igemm at m = 65,536 / K = 2,880 ... 23,040, its 256-block
+    persistent walk, dh = 40 attention, the split-K slabs) and every block are compared with fp64 on their own in
+    tests/test_gpu_launch_parity.py.
   * BASELINE config 2 (mobi_nusc_256, batch 4): full width at 32x32, UNet batch 8.
   * trajectories on the reduced net: DDIM-50 (fp16 <= 1e-3 asserted: the north-star figure) and the DDIM-250 schedule
     of config 5 ([1, 5, ..., 997], fp16).

@@ -1,0 +1,252 @@
+"""The launch shadow's own references and metric (tests/launch_shadow.py), on the CPU: every igemm reference form against
+F.conv2d / F.linear in fp64, the other references against torch's fp64 ops, the ff_geglu chunk-image decode against the
+packer, and the metric passing a merely storage-rounded result while failing a dropped k-chunk tile, a NaN row and a write
+outside a strided view."""
+import math
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import launch_shadow as ls
+from tests.test_gpu_ops import TOL
+
+DT = [torch.float16, torch.bfloat16]
+
+
+def _rand(shape, seed, scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(shape, generator=g, dtype=torch.float64) * scale
+
+
+def _op(x, w, bias=None, x2=None, stride=1, pad=None, upsample=False, hout=None, wout=None, rowvec=None, rowvec_has_bias=False,
+        residual=None, scale=1.0, groups=1, geglu=False, ln_eps=None, cout=None):
+    """x NHWC, w OIHW (fp64) -> the shadow's igemm operand record, weights packed k = tap * C + c as ops.pack_conv does."""
+    o, i, kh, kw = w.shape
+    src_w = (x.shape[2] * 2 if upsample else x.shape[2], x.shape[1] * 2 if upsample else x.shape[1])
+    ph, pw = (kh // 2, kw // 2) if pad is None else pad
+    ho = (src_w[1] + 2 * ph - kh) // stride + 1 if hout is None else hout
+    wo = (src_w[0] + 2 * pw - kw) // stride + 1 if wout is None else wout
+    npk = o // groups
+    return dict(x=x, x2=x2, w=w.permute(0, 2, 3, 1).reshape(o, kh * kw * i), bias=bias, kh=kh, kw=kw, stride=stride, pad_h=ph,
+                pad_w=pw, upsample=upsample, hout=ho, wout=wo, cout=cout or npk, n_packed=npk, groups=groups, geglu=geglu,
+                ln=ln_eps is not None, ln_eps=ln_eps or 0.0, scale=scale, rowvec=rowvec, rowvec_has_bias=rowvec_has_bias,
+                residual=residual)
+
+
+def _nhwc(t):
+    return t.permute(0, 2, 3, 1)
+
+
+def _flat(t):
+    return t.reshape(t.shape[0], -1, t.shape[-1])
+
+
+CONV_CASES = [
+    # name, cin, cout, k, h, w, stride, upsample
+    ("c3", 32, 48, 3, 9, 7, 1, False),
+    ("c1", 64, 40, 1, 6, 5, 1, False),
+    ("c3_s2", 32, 32, 3, 8, 8, 2, False),
+    ("c3_up", 32, 16, 3, 5, 4, 1, True),
+    ("c15", 32, 24, (1, 5), 4, 9, 1, False),
+]
+
+
+@pytest.mark.parametrize("case", CONV_CASES, ids=[c[0] for c in CONV_CASES])
+def test_igemm_reference_conv_forms(case):
+    name, cin, cout, k, h, w, stride, up = case
+    kh, kw = (k, k) if isinstance(k, int) else k
+    x = _rand((3, cin, h, w), 1)
+    wt = _rand((cout, cin, kh, kw), 2, 0.1)
+    b = _rand((cout,), 3)
+    op = _op(_nhwc(x), wt, bias=b, stride=stride, upsample=up)
+    xi = F.interpolate(x, scale_factor=2, mode="nearest") if up else x
+    want = F.conv2d(xi, wt, b, stride=stride, padding=(kh // 2, kw // 2))
+    got = ls.igemm_reference(op)
+    assert torch.allclose(got, _flat(_nhwc(want)), rtol=1e-12, atol=1e-12)
+    rows = torch.tensor([0, 5, got.shape[0] * got.shape[1] - 1])
+    assert torch.allclose(ls.igemm_reference(op, rows=rows), got.reshape(-1, cout)[rows], rtol=1e-13, atol=1e-13)
+
+
+def test_igemm_reference_stride2_explicit_size_concat_and_epilogue():
+    """stride 2 with an explicit hout / wout (the asymmetric-pad Downsample: reads past the bottom / right edge are zero), a
+    second source concatenated on channels, rowvec with and without the layer's bias in it, residual, scale."""
+    x0, x1 = _rand((2, 32, 8, 8), 4), _rand((2, 32, 8, 8), 5)
+    wt = _rand((24, 64, 3, 3), 6, 0.1)
+    b = _rand((24,), 7)
+    op = _op(_nhwc(x0), wt, x2=_nhwc(x1), bias=b, stride=2, pad=(0, 0), hout=4, wout=4)
+    want = F.conv2d(F.pad(torch.cat([x0, x1], 1), (0, 1, 0, 1)), wt, b, stride=2)
+    assert torch.allclose(ls.igemm_reference(op), _flat(_nhwc(want)), rtol=1e-12, atol=1e-12)
+    rv, res = _rand((2, 24), 8), _rand((2, 4, 4, 24), 9)
+    base = F.conv2d(F.pad(torch.cat([x0, x1], 1), (0, 1, 0, 1)), wt, None, stride=2)
+    for has_bias in (False, True):
+        op = _op(_nhwc(x0), wt, x2=_nhwc(x1), bias=b, stride=2, pad=(0, 0), hout=4, wout=4, rowvec=rv, rowvec_has_bias=has_bias,
+                 residual=res.reshape(2, 16, 24), scale=0.5)
+        want = _nhwc(base) * 0.5 + (0 if has_bias else b) + rv[:, None, None, :] + res
+        assert torch.allclose(ls.igemm_reference(op), _flat(want), rtol=1e-12, atol=1e-12), has_bias
+
+
+def test_igemm_reference_linear_groups_ln_fold_geglu():
+    """Token rows as [N, T, 1, C]: groups (image i takes matrix i // (N / g)), the LayerNorm fold, the packed GEGLU rows."""
+    n, t, c = 4, 6, 64
+    x = _rand((n, t, 1, c), 10, 2.0) + 0.5
+    w = _rand((2 * 32, c), 11, 0.1)
+    op = _op(x, w[:, :, None, None], groups=2)
+    want = torch.cat([F.linear(x[:2, :, 0], w[:32]), F.linear(x[2:, :, 0], w[32:])])
+    assert torch.allclose(ls.igemm_reference(op), want, rtol=1e-12, atol=1e-12)
+    # LayerNorm folded: W' = W diag(gamma), bias' = W beta + b  ==  Linear(LayerNorm(x))
+    wl, bl = _rand((40, c), 12, 0.1), _rand((40,), 13)
+    gamma, beta = _rand((c,), 14) * 0.2 + 1.0, _rand((c,), 15) * 0.1
+    op = _op(x, (wl * gamma)[:, :, None, None], bias=wl @ beta + bl, ln_eps=1e-5)
+    want = F.linear(F.layer_norm(x[:, :, 0], (c,), gamma, beta, 1e-5), wl, bl)
+    assert torch.allclose(ls.igemm_reference(op), want, rtol=1e-10, atol=1e-10)
+    # GEGLU: rows of every 16-row tile = 8 value rows, then the 8 gate rows of the same outputs (ops.pack_geglu / geglu_layout)
+    from mobi_amd import ops
+    inner = 32
+    wg, bg = _rand((2 * inner, c), 16, 0.1), _rand((2 * inner,), 17)
+    pk = ops.pack_geglu(wg.float(), bg.float(), torch.float32, "cpu")
+    op = _op(x, pk.w.double()[:, :, None, None], bias=pk.bias.double(), geglu=True, cout=inner)
+    op["n_packed"] = 2 * inner
+    pre = F.linear(x[:, :, 0], wg.float().double(), bg.float().double())
+    want = pre[..., :inner] * F.gelu(pre[..., inner:])
+    assert torch.allclose(ls.igemm_reference(op), want, rtol=1e-6, atol=1e-6)
+
+
+def test_norm_and_attention_references():
+    x = _rand((3, 4, 5, 64), 20, 1.5) + 2.0
+    x2 = _rand((3, 4, 5, 32), 21)
+    g, b = _rand((96,), 22), _rand((96,), 23)
+    op = dict(x=x, x2=x2, gamma=g, beta=b, eps=1e-5, silu=True)
+    want = F.silu(F.group_norm(torch.cat([x, x2], 3).permute(0, 3, 1, 2), 32, g, b, 1e-5)).permute(0, 2, 3, 1)
+    got = ls.groupnorm_reference(op)
+    assert torch.allclose(got, _flat(want), rtol=1e-11, atol=1e-11)
+    rows = torch.tensor([0, 19, 20, 59])
+    assert torch.allclose(ls.groupnorm_reference(op, rows=rows), got.reshape(-1, 96)[rows], rtol=1e-13, atol=1e-13)
+    t = _rand((4, 7, 64), 24)
+    gl, bl = _rand((64,), 25), _rand((64,), 26)
+    assert torch.allclose(ls.layernorm_reference(dict(x=t[1::2], gamma=gl, beta=bl, eps=1e-5)),
+                          F.layer_norm(t[1::2], (64,), gl, bl, 1e-5), rtol=1e-12, atol=1e-12)
+    # attention: strided q / k / v views (stacked projections), V^T and V rows, q pre-scaled by scale * log2 e
+    n, tq, tk, h, dh = 2, 9, 11, 4, 8
+    c = h * dh
+    qkv = _rand((n, tq, 3 * c), 27)
+    kv = _rand((n, tk, 2 * c), 28)
+    scale = dh ** -0.5
+    split = lambda z, tt: z.reshape(n, tt, h, dh).transpose(1, 2)
+    want = F.scaled_dot_product_attention(split(qkv[..., :c], tq), split(kv[..., :c], tk), split(kv[..., c:], tk), scale=scale)
+    want = want.transpose(1, 2).reshape(n, tq, c)
+    for v_rows in (True, False):
+        v = kv[..., c:] if v_rows else kv[..., c:].transpose(1, 2)
+        got = ls.attention_reference(dict(q=qkv[..., :c], k=kv[..., :c], v=v, heads=h, scale=scale, v_rows=v_rows,
+                                          q_log2_scaled=False))
+        assert torch.allclose(got, want, rtol=1e-12, atol=1e-12), v_rows
+    got = ls.attention_reference(dict(q=qkv[..., :c] * (scale * math.log2(math.e)), k=kv[..., :c], v=kv[..., c:], heads=h,
+                                      scale=123.0, v_rows=True, q_log2_scaled=True))
+    assert torch.allclose(got, want, rtol=1e-12, atol=1e-12)
+    rows = torch.tensor([0, 3, tq, 2 * tq - 1])
+    assert torch.allclose(ls.attention_reference(dict(q=qkv[..., :c], k=kv[..., :c], v=kv[..., c:], heads=h, scale=scale,
+                                                      v_rows=True, q_log2_scaled=False), rows=rows),
+                          want.reshape(-1, c)[rows], rtol=1e-12, atol=1e-12)
+
+
+def test_two_key_adapter_reference_is_two_key_attention():
+    """The shared restatement x + b + sum_h sigmoid(...) u_h against what it folds (BasicTransformerBlock._two_key_terms):
+    x + W (softmax over two keys of q_h = LN(x) Wq_h^T) v, W the folded output projection, for per-head tables built from
+    k / v of the two tokens."""
+    n, t, c, h = 2, 5, 32, 4
+    dh = c // h
+    x = _rand((n, t, c), 30, 2.0) + 0.3
+    wq, w = _rand((c, c), 31, 0.2), _rand((c, c), 32, 0.2)
+    k, v = _rand((n, 2, c), 33), _rand((n, 2, c), 34)
+    b0 = _rand((c,), 35)
+    ln = F.layer_norm(x, (c,), None, None, 1e-5)
+    q = (ln @ wq.T).reshape(n, t, h, dh)
+    sc = torch.einsum("nthd,nkhd->nthk", q, k.reshape(n, 2, h, dh)) * dh ** -0.5
+    att = torch.einsum("nthk,nkhd->nthd", sc.softmax(-1), v.reshape(n, 2, h, dh)).reshape(n, t, c)
+    want = x + att @ w.T + b0
+    mask = torch.zeros(h, c, dtype=torch.float64)
+    for i in range(h):
+        mask[i, i * dh:(i + 1) * dh] = 1
+    dk, dv = (k[:, 0] - k[:, 1])[:, None] * mask, (v[:, 0] - v[:, 1])[:, None] * mask
+    a = dk @ wq * dh ** -0.5                                         # Wq_h^T dk_h, scaled
+    u = dv @ w.T
+    got = ls.two_key_adapter_reference(x, a, a.sum(-1), torch.zeros(n, h, dtype=torch.float64), u, v[:, 1] @ w.T + b0, 1e-5)
+    assert torch.allclose(got, want, rtol=1e-11, atol=1e-11)
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_ff_geglu_decode_round_trips_the_packer(dtype):
+    """decode_ff_geglu restates the chunk-image layout of include/mobi_engine.h; the packer's images must decode to the
+    storage-rounded masters, and the reference must be the plain GEGLU feed-forward of them."""
+    from mobi_amd import ops
+    c, hidden = 320, 64
+    w1, b1 = _rand((2 * hidden, c), 40, 0.05).float(), _rand((2 * hidden,), 41).float()
+    w2, b2 = _rand((c, hidden), 42, 0.05).float(), _rand((c,), 43).float()
+    pf = ops.pack_ff_geglu(w1, b1, w2, b2, dtype, "cpu")
+    d1, db1, d2 = ls.decode_ff_geglu(pf.buf, c, hidden, dtype)
+    assert torch.equal(d1, w1.to(dtype)) and torch.equal(d2, w2.to(dtype)) and torch.equal(db1, b1)
+    x = _rand((2, 3, c), 44).to(dtype)
+    res = _rand((2, 3, c), 45).to(dtype)
+    g, bt = _rand((c,), 46).float(), _rand((c,), 47).float()
+    got = ls.ff_geglu_reference(dict(x=x, residual=res, b2=pf.b2, ln=(g, bt, 1e-5), dec=(d1, db1, d2)))
+    xl = F.layer_norm(x.double(), (c,), g.double(), bt.double(), 1e-5)
+    pre = F.linear(xl, w1.to(dtype).double(), b1.double())
+    want = F.linear(pre[..., :hidden] * F.gelu(pre[..., hidden:]), w2.to(dtype).double(), b2.double()) + res.double()
+    assert torch.allclose(got, want, rtol=1e-11, atol=1e-11)
+
+
+# ---- the metric -------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", DT)
+def test_metric_passes_storage_rounding(dtype):
+    ref = _rand((4, 300, 320), 50) * torch.linspace(0.1, 10, 320, dtype=torch.float64)
+    res = ls.compare(ref.to(dtype), ref)
+    assert ls.passes(res, TOL[dtype]), res
+
+
+@pytest.fixture(scope="module")
+def dropped_chunk():
+    """A 65,536 x 320 product with K = 2,880 whose 128 x 64 tile at rows 4,096.. / channels 128.. lost one 64-deep k-chunk:
+    the tensor is drawn with the product's statistics, the tile is the real product of its operands."""
+    k, r0, c0 = 2880, 4096, 128
+    ref = _rand((1, 65536, 320), 51) * math.sqrt(k)
+    a, w = _rand((128, k), 52), _rand((64, k), 53)
+    ref[0, r0:r0 + 128, c0:c0 + 64] = a @ w.T
+    bad = ref.clone()
+    bad[0, r0:r0 + 128, c0:c0 + 64] = a[:, 64:] @ w[:, 64:].T
+    return ref, bad, (0, r0, c0)
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_metric_fails_dropped_k_chunk(dtype, dropped_chunk):
+    ref, bad, where = dropped_chunk
+    res = ls.compare(bad.to(dtype), ref)
+    assert res["tile"] > 0.1 and res["where"] == where, res                       # ~ sqrt(1 / 45)
+    assert not ls.passes(res, TOL[dtype]), res
+    if dtype == torch.bfloat16:
+        assert res["rel"] < TOL[dtype], res                                      # whole-tensor rel-L2 alone would pass
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_metric_fails_nan_row(dtype):
+    ref = _rand((2, 256, 64), 54)
+    got = ref.to(dtype)
+    got[1, 77] = float("nan")
+    res = ls.compare(got, ref)
+    assert not res["finite"] and not ls.passes(res, TOL[dtype]), res
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_outside_view_write_is_caught(dtype):
+    """The camera / lidar halves are updated in place through batch-strided views: a write one row past a view's rows, or
+    into the partner image, must show; writes inside the view must not."""
+    base = _rand((4, 20, 64), 55).to(dtype)
+    view = base[::2, 2:18]
+    ov = ls.OutsideView(view)
+    view.add_(1.0)
+    assert ov.unchanged()
+    base[0, 18] += 1.0                                          # one row past the view's last row of image 0
+    assert not ov.unchanged()
+    base2 = _rand((4, 16, 64), 56).to(dtype)
+    ov2 = ls.OutsideView(base2[::2])
+    base2[1, 0] = float("nan")                                  # the partner image's first row
+    assert not ov2.unchanged()
