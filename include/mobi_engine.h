@@ -46,7 +46,9 @@ extern "C" {
  *   6  mobi_igemm_params.defer_finish + mobi_igemm_slab_count / mobi_igemm_finish; mobi_split_source (struct id 19) and
  *      mobi_groupnorm_params.src0_split + mobi_groupnorm_takes_split: a split-K launch's partial sums are summed by the
  *      GroupNorm that consumes them instead of by a reduce launch of their own; later, without a layout change (an
- *      addition only), mobi_dpm_step and its mobi_dpm_step_params (struct id 20) */
+ *      addition only), mobi_dpm_step and its mobi_dpm_step_params (struct id 20); likewise the realism metrics' kernels
+ *      mobi_maxpool3s2, mobi_lpips_distance + mobi_lpips_distance_ws_floats (mobi_lpips_distance_params, struct id 21),
+ *      mobi_image_normalize (mobi_image_normalize_params, struct id 22) and mobi_row_cosine */
 #define MOBI_ABI_VERSION 6
 
 enum { MOBI_OK = 0, MOBI_ERR_ARG = -1, MOBI_ERR_UNSUPPORTED = -2, MOBI_ERR_LAUNCH = -3, MOBI_ERR_ALIGN = -4 };
@@ -58,8 +60,8 @@ const char* mobi_error_string(int code);
  * their own layout before the first call.  id: 0 igemm, 1 groupnorm, 2 layernorm,
  * 3 attention, 4 ctx_attention, 5 skinny_linear, 6 conv_small_cin, 7 conv_small_cout,
  * 8 ddim_step, 9 two_key_adapter, 10 range_paste, 11 lidar_metrics, 12 range_prepare, 13 image_prepare, 14 ff_geglu,
- * 15 row_chain, 16 chain_op, 17 layernorm_bwd, 18 attention_bwd, 19 split_source, 20 dpm_step.  Returns 0 for an
- * unknown id. */
+ * 15 row_chain, 16 chain_op, 17 layernorm_bwd, 18 attention_bwd, 19 split_source, 20 dpm_step, 21 lpips_distance,
+ * 22 image_normalize.  Returns 0 for an unknown id. */
 size_t mobi_struct_size(int id);
 /* Development hook: the library reads its MOBI_* A/B environment variables once, at the first launch
  * (mobi_amd/csrc/tuning.h lists them); this re-reads them.  Not needed by a product caller. */
@@ -773,6 +775,54 @@ int mobi_nchw_f32_to_nhwc(const float* src, void* out, int32_t batch, int32_t c,
                           void* stream);
 int mobi_nhwc_to_nchw_f32(const void* src, float* out, int32_t batch, int32_t c, int32_t hw, int32_t dtype,
                           void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Realism metrics (mobi_amd/realism.py): LPIPS (Zhang et al. 2018, lpips 0.1.4 `LPIPS(net='alex')`, version 0.1) on
+ * AlexNet's five convolutions (mobi_igemm), and CLIP score (100 cos of two ViT-B/32 image embeddings) -- the per-pair
+ * columns of the reference's realism table (eval_tool/camera/{lpips,clip}_score.py).
+ * ------------------------------------------------------------------------- */
+/* 3 x 3 max-pool, stride 2, no padding, floor mode (F.max_pool2d(x, 3, 2)) on T channels-last [batch][h][w][c] ->
+ * T [batch][(h - 3) / 2 + 1][(w - 3) / 2 + 1][c].  relu = 1: max(0, window max) == max_pool2d(relu(x)) (AlexNet's ReLU
+ * after conv1 / conv2, taken here).  Exact: the result is one of the stored values (or 0).  c % 8 == 0, h, w >= 3. */
+int mobi_maxpool3s2(const void* src, void* out, int32_t batch, int32_t h, int32_t w, int32_t c, int32_t relu, int32_t dtype,
+                    void* stream);
+
+/* One LPIPS layer term, ACCUMULATED into out (lpips 0.1.4, pretrained_networks.alexnet + LPIPS.forward, spatial = False):
+ *   out[i] += mean_{pixels} sum_c lin[c] (A_c - B_c)^2,  A = relu(a) / (sqrt(sum_c relu(a)_c^2) + eps), B likewise,
+ * with a = pixel of image i, b = the same pixel of image i + pairs (both sets run through AlexNet as one batch).  fp32
+ * throughout (sum a^2 of a 16-bit feature can overflow fp16).  Reproducible bit for bit: every block writes one partial
+ * to `ws` in a fixed order, a second launch sums a pair's partials in ascending order (no float atomics).
+ * relu_in_place = 1: feat is also overwritten with relu(feat) (conv3 / conv4 outputs feed the next convolution). */
+typedef struct mobi_lpips_distance_params {
+  void* feat;            /* T [2 * pairs][hw][channels] as mobi_igemm wrote it                     */
+  const float* lin;      /* f32 [channels]: the layer's 1 x 1 lin weights (lin{k}.model.1.weight)  */
+  float* out;            /* f32 [pairs], accumulated                                               */
+  float* ws;             /* f32 [mobi_lpips_distance_ws_floats(pairs, hw)]                         */
+  int32_t pairs, hw, channels;   /* channels % 8 == 0                                              */
+  float eps;             /* 1e-10 (lpips.normalize_tensor)                                         */
+  int32_t relu_in_place;
+  int32_t dtype;
+} mobi_lpips_distance_params;
+size_t mobi_lpips_distance_ws_floats(int32_t pairs, int32_t hw);
+int mobi_lpips_distance(const mobi_lpips_distance_params* p, void* stream);
+
+/* Per-channel input normalisation out = (x - shift[c]) / scale[c] in fp32 (lpips ScalingLayer; CLIP's Normalize), from
+ * f32 NCHW.  nhwc_channels = 0: f32 NCHW out; > 0: T channels-last [batch][hw][nhwc_channels], channels past `channels`
+ * zero (the padded-input-channel operand of a mobi_igemm whose weights are zero-padded likewise). */
+typedef struct mobi_image_normalize_params {
+  const float* src;      /* f32 [batch][channels][hw] */
+  void* out;
+  int32_t batch, channels, hw;   /* 1 <= channels <= 4 */
+  float shift[4], scale[4];
+  int32_t nhwc_channels;         /* 0, or >= channels and % 8 == 0 */
+  int32_t dtype;                 /* T of the channels-last output */
+} mobi_image_normalize_params;
+int mobi_image_normalize(const mobi_image_normalize_params* p, void* stream);
+
+/* out[i] = scale * sum_d (a_id / max(|a_i|, eps)) (b_id / max(|b_i|, eps)) on f32 [rows][dim] pairs of rows
+ * (F.cosine_similarity(a, b, dim=-1, eps)), fp32, one block per row, fixed reduction order. */
+int mobi_row_cosine(const float* a, const float* b, float* out, int32_t rows, int32_t dim, float eps, float scale,
+                    void* stream);
 
 #ifdef __cplusplus
 }

@@ -164,11 +164,22 @@ class ImagePrepareParams(C.Structure):
                 ("batch", i32), ("H", i32), ("W", i32), ("height", i32), ("width", i32)]
 
 
+class LpipsDistanceParams(C.Structure):
+    _fields_ = [("feat", vp), ("lin", vp), ("out", vp), ("ws", vp), ("pairs", i32), ("hw", i32), ("channels", i32), ("eps", f32),
+                ("relu_in_place", i32), ("dtype", i32)]
+
+
+class ImageNormalizeParams(C.Structure):
+    _fields_ = [("src", vp), ("out", vp), ("batch", i32), ("channels", i32), ("hw", i32), ("shift", f32 * 4), ("scale", f32 * 4),
+                ("nhwc_channels", i32), ("dtype", i32)]
+
+
 STRUCT_IDS = {0: IgemmParams, 1: GroupNormParams, 2: LayerNormParams, 3: AttentionParams, 4: CtxAttentionParams,
               5: SkinnyLinearParams, 6: ConvSmallCinParams, 7: ConvSmallCoutParams, 8: DdimStepParams, 9: TwoKeyAdapterParams,
               10: RangePasteParams, 11: LidarMetricsParams, 12: RangePrepareParams, 13: ImagePrepareParams,
               14: FfGegluParams, 15: RowChainParams, 16: ChainOp,
-              17: LayerNormBwdParams, 18: AttentionBwdParams, 19: SplitSource, 20: DpmStepParams}
+              17: LayerNormBwdParams, 18: AttentionBwdParams, 19: SplitSource, 20: DpmStepParams,
+              21: LpipsDistanceParams, 22: ImageNormalizeParams}
 
 # every symbol include/mobi_engine.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -243,6 +254,11 @@ SYMBOLS = {
     "mobi_pack_nchw_sources": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
     "mobi_nchw_f32_to_nhwc": (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),
     "mobi_nhwc_to_nchw_f32": (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),
+    "mobi_maxpool3s2": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "mobi_lpips_distance_ws_floats": (C.c_size_t, [i32, i32]),
+    "mobi_lpips_distance": (C.c_int, [C.POINTER(LpipsDistanceParams), vp]),
+    "mobi_image_normalize": (C.c_int, [C.POINTER(ImageNormalizeParams), vp]),
+    "mobi_row_cosine": (C.c_int, [vp, vp, vp, i32, i32, f32, f32, vp]),
 }
 
 _lib = None

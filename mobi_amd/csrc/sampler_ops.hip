@@ -269,6 +269,8 @@ extern "C" size_t mobi_struct_size(int id) {
     case 18: return sizeof(mobi_attention_bwd_params);
     case 19: return sizeof(mobi_split_source);
     case 20: return sizeof(mobi_dpm_step_params);
+    case 21: return sizeof(mobi_lpips_distance_params);
+    case 22: return sizeof(mobi_image_normalize_params);
     default: return 0;
   }
 }

@@ -1402,3 +1402,58 @@ def blend_frame(mask_blur, image, pred):
     out = torch.empty((h, w, 3), device=mask_blur.device, dtype=torch.float32)
     _lib.check(lib.mobi_blend_frame(_ptr(mask_blur), _ptr(image), _ptr(pred), _ptr(out), h, w, _stream()), "mobi_blend_frame")
     return out
+
+
+# --------------------------------------------------------------------------------------
+# realism metrics (mobi_amd/realism.py)
+# --------------------------------------------------------------------------------------
+def maxpool3s2(x, relu=False):
+    """T [N,H,W,C] -> T [N,(H-3)//2+1,(W-3)//2+1,C]: F.max_pool2d(x, 3, 2) (of relu(x) when `relu`), exact."""
+    lib = _lib.load()
+    n, h, w, c = x.shape
+    assert x.is_contiguous()
+    out = torch.empty((n, (h - 3) // 2 + 1, (w - 3) // 2 + 1, c), device=x.device, dtype=x.dtype)
+    _lib.check(lib.mobi_maxpool3s2(_ptr(x), _ptr(out), n, h, w, c, int(relu), _dt(x.dtype), _stream()), "mobi_maxpool3s2")
+    return out
+
+
+def lpips_distance(feat, lin, out, eps=1e-10, relu_in_place=False):
+    """out f32 [P] += one LPIPS layer term of feat T [2P,H,W,C] (pairs i, i + P) with lin weights f32 [C]."""
+    lib = _lib.load()
+    n2, h, w, c = feat.shape
+    assert n2 % 2 == 0 and feat.is_contiguous() and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n2 // 2
+    assert lin.dtype == torch.float32 and lin.is_contiguous() and lin.numel() == c
+    ws = torch.empty((lib.mobi_lpips_distance_ws_floats(n2 // 2, h * w),), device=feat.device, dtype=torch.float32)
+    p = _lib.LpipsDistanceParams()
+    p.feat, p.lin, p.out, p.ws = _ptr(feat), _ptr(lin), _ptr(out), _ptr(ws)
+    p.pairs, p.hw, p.channels, p.eps = n2 // 2, h * w, c, eps
+    p.relu_in_place, p.dtype = int(relu_in_place), _dt(feat.dtype)
+    _lib.check(lib.mobi_lpips_distance(C.byref(p), _stream()), "mobi_lpips_distance")
+    return out
+
+
+def image_normalize(x, shift, scale, dtype=None, nhwc_channels=0):
+    """f32 NCHW x -> (x - shift[c]) / scale[c]: f32 NCHW (nhwc_channels 0) or T [N,H,W,nhwc_channels] zero-padded."""
+    lib = _lib.load()
+    n, c, h, w = x.shape
+    assert x.dtype == torch.float32 and x.is_contiguous() and len(shift) == len(scale) == c
+    p = _lib.ImageNormalizeParams()
+    if nhwc_channels:
+        out = torch.empty((n, h, w, nhwc_channels), device=x.device, dtype=dtype)
+        p.dtype = _dt(dtype)
+    else:
+        out = torch.empty_like(x)
+    p.src, p.out, p.batch, p.channels, p.hw, p.nhwc_channels = _ptr(x), _ptr(out), n, c, h * w, nhwc_channels
+    for i in range(c):
+        p.shift[i], p.scale[i] = shift[i], scale[i]
+    _lib.check(lib.mobi_image_normalize(C.byref(p), _stream()), "mobi_image_normalize")
+    return out
+
+
+def row_cosine(a, b, eps=1e-8, scale=1.0):
+    """f32 [N, D] x 2 -> f32 [N]: scale * F.cosine_similarity(a, b, dim=-1, eps=eps)."""
+    lib = _lib.load()
+    assert a.dtype == b.dtype == torch.float32 and a.shape == b.shape and a.dim() == 2 and a.is_contiguous() and b.is_contiguous()
+    out = torch.empty((a.shape[0],), device=a.device, dtype=torch.float32)
+    _lib.check(lib.mobi_row_cosine(_ptr(a), _ptr(b), _ptr(out), a.shape[0], a.shape[1], eps, scale, _stream()), "mobi_row_cosine")
+    return out
