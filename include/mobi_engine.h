@@ -85,7 +85,12 @@ int mobi_build_info(void);
  * (model.py:47,66,72-79,92,102) and AttnBlock q/k/v/proj_out + both bmm
  * (model.py:178-202).
  * ------------------------------------------------------------------------- */
-enum { MOBI_EPI_NONE = 0, MOBI_EPI_GEGLU = 1 };
+/* MOBI_EPI_LEAKY_RELU: out = leaky(scale * acc + bias + rowvec) + residual with leaky(v) = v > 0 ? v : 0.1 v (RangeNet++'s
+ * LeakyReLU(0.1) after a folded BatchNorm, the BasicBlock's residual added after the activation), one rounding.  Row-major
+ * output (T or f32), one k pass (split_k <= 1; mobi_igemm_plan_splits returns 1), tap-major k, no LayerNorm fold; it runs on
+ * the ring kernels' LDS-staged epilogue (MOBI_IGEMM_RING_256 for launches of 256-pixel tiles with n_packed >= 256,
+ * MOBI_IGEMM_RING_128 otherwise).  Anything else, and operands beyond the ring kernels' 2 GB, is MOBI_ERR_UNSUPPORTED. */
+enum { MOBI_EPI_NONE = 0, MOBI_EPI_GEGLU = 1, MOBI_EPI_LEAKY_RELU = 2 };
 enum { MOBI_OUT_ROWS = 0,        /* T   [m][cout]                               */
        MOBI_OUT_TRANSPOSED = 1,  /* T   [image][cout][hout*wout]                */
        MOBI_OUT_ROWS_F32 = 2 };  /* f32 [m][cout]                               */
@@ -823,6 +828,31 @@ int mobi_image_normalize(const mobi_image_normalize_params* p, void* stream);
  * (F.cosine_similarity(a, b, dim=-1, eps)), fp32, one block per row, fixed reduction order. */
 int mobi_row_cosine(const float* a, const float* b, float* out, int32_t rows, int32_t dim, float eps, float scale,
                     void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Fréchet realism metrics (mobi_amd/realism.py): FID on CLIP ViT-B/32 image embeddings and FRD on RangeNet++ features
+ * (eval_tool/camera/fid_score.py, eval_tool/lidar/frd_score.py).  RangeNet's convolutions are mobi_igemm launches with
+ * MOBI_EPI_LEAKY_RELU; the distance itself is computed on the host in fp64.
+ * ------------------------------------------------------------------------- */
+/* Moments of a feature batch, ACCUMULATED in fp64: sum[i] += sum_r (feat[r][i] - shift[i]) and, unless cross is NULL,
+ * cross[i][j] += sum_r (feat[r][i] - shift[i]) (feat[r][j] - shift[j]) over f32 [rows][dim] (shift NULL: zero).  A fixed
+ * order of fp64 operations per element, no atomics: reproducible bit for bit. */
+int mobi_feature_moments(const float* feat, int32_t rows, int32_t dim, const double* shift, double* sum, double* cross,
+                         void* stream);
+
+/* RangeNet++ input of the FRD tool (frd_score.py RangePathDataset): f32 [batch][4][h][w] range views (normalised depth,
+ * intensity, pitch, yaw) -> T channels-last [batch][hout][wout][cpad]: depth = (d + 1) / 2 * depth_max, valid =
+ * depth_min < depth < depth_max (fp64, as numpy), channels [depth, intensity, cos(yaw) cos(pitch) depth,
+ * -sin(yaw) cos(pitch) depth, sin(pitch) depth] rounded to f32 then T, all five -1 where invalid, channels 5 .. cpad - 1 zero;
+ * nearest resize, source index dst * in / out.  cpad % 8 == 0, cpad >= 8. */
+int mobi_frd_input(const float* raw, void* out, int32_t batch, int32_t h, int32_t w, int32_t hout, int32_t wout, int32_t cpad,
+                   double depth_min, double depth_max, int32_t dtype, void* stream);
+
+/* Band mean (RangeNet Model.forward, agg_type 'depth'): out[n][ch * bands + b] = mean of (src + skip)[n][y][x][ch] over the
+ * h / bands rows of band b and all w columns, fp32, fixed order, no atomics.  src, skip (or NULL): T channels-last
+ * [batch][h][w][c]; out f32 [batch][c * bands].  c % 8 == 0, c / 8 divides 256, h % bands == 0. */
+int mobi_band_mean(const void* src, const void* skip, float* out, int32_t batch, int32_t h, int32_t w, int32_t c,
+                   int32_t bands, int32_t dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,7 @@ LIB_PATH = os.path.join(HERE, "libmobi_hip.so")
 
 MOBI_F16, MOBI_BF16 = 0, 1
 ABI_VERSION = 6            # include/mobi_engine.h MOBI_ABI_VERSION
-EPI_NONE, EPI_GEGLU = 0, 1
+EPI_NONE, EPI_GEGLU, EPI_LEAKY_RELU = 0, 1, 2
 OUT_ROWS, OUT_TRANSPOSED, OUT_ROWS_F32 = 0, 1, 2
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
 
@@ -259,6 +259,9 @@ SYMBOLS = {
     "mobi_lpips_distance": (C.c_int, [C.POINTER(LpipsDistanceParams), vp]),
     "mobi_image_normalize": (C.c_int, [C.POINTER(ImageNormalizeParams), vp]),
     "mobi_row_cosine": (C.c_int, [vp, vp, vp, i32, i32, f32, f32, vp]),
+    "mobi_feature_moments": (C.c_int, [vp, i32, i32, vp, vp, vp, vp]),
+    "mobi_frd_input": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, C.c_double, C.c_double, i32, vp]),
+    "mobi_band_mean": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
 }
 
 _lib = None

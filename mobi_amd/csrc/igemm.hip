@@ -174,7 +174,8 @@ struct EpiGeom {
 
 // RES_EARLY = false: the residual rows of a pass are requested at the start of THAT pass (the 256 x 320 ring kernel holds
 // 160 accumulator registers through the epilogue: all passes' rows up front would spill)
-template <typename T, int NT, bool TR, int RPP, bool RES_EARLY = true>
+// LEAKY: MOBI_EPI_LEAKY_RELU -- out = leaky_0.1(scale acc + bias + rowvec) + residual, one rounding (row-major output only)
+template <typename T, int NT, bool TR, int RPP, bool RES_EARLY = true, bool LEAKY = false>
 __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, float* stage, f32x4 (&acc)[NT][4], int lane,
                                                int group, int nw0, int mw0) {
   constexpr int WAVE_N = NT * 16;
@@ -328,6 +329,10 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, float* stage,
             ld8f(a.rowvec + gi * a.rowvec_stride + n, rv);
 #pragma unroll
             for (int j = 0; j < 8; ++j) o[j] += rv[j];
+          }
+          if constexpr (LEAKY) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] = o[j] > 0.0f ? o[j] : 0.1f * o[j];
           }
           if (resid) {
             float rf[8];
@@ -1997,7 +2002,8 @@ __device__ __forceinline__ void ln_fold_acc(const IgemmArgs& a, f32x4 (&acc)[NT]
 //   NW 8, MT 8  256 x (4 WAVE_N) tile, wave tile 128 x WAVE_N, one block per CU: 29 % fewer operand bytes per FLOP than
 //               the 256 x 160 tile of the ping-pong kernel (the LDS-DMA path accepts ~42 B per clock and CU, which is
 //               exactly what that tile needs at full matrix rate) and 13 instead of 18 fragment reads per 40 MFMAs
-template <typename T, int NT, bool TR, int NW, int MT, bool LNF = false>
+// LEAKY: the MOBI_EPI_LEAKY_RELU instances (LDS-staged epilogue only: the host clears sm_direct / ring_direct for them)
+template <typename T, int NT, bool TR, int NW, int MT, bool LNF = false, bool LEAKY = false>
 __global__ __launch_bounds__(NW * 64, 2) void igemm_ring_kernel(const IgemmArgs a) {
   typedef typename Vec8<T>::type frag_t;
   constexpr bool WIDE = NW == 8;                             // eight waves: the two halves run half a step apart
@@ -2315,7 +2321,7 @@ __global__ __launch_bounds__(NW * 64, 2) void igemm_ring_kernel(const IgemmArgs 
     ln_fold_acc<NT, MT, SPW>(a, acc, ls_sum, ls_sq, s_rowstat, lane, wm, wave_s >> 1, n0 + wn * WAVE_N,
                              WIDE && MT == 8 && a.ring_direct);
   }
-  if constexpr (MT == 4 && !TR) {
+  if constexpr (MT == 4 && !TR && !LEAKY) {
     if (a.sm_direct) {                                       // wave-uniform
       // 128-pixel tiles, full: the wave tile is the ping-pong kernel's (64 pixels x NT * 16 channels), so are its register
       // epilogue and its slab stores; no LDS staging, no block barrier
@@ -2344,7 +2350,7 @@ __global__ __launch_bounds__(NW * 64, 2) void igemm_ring_kernel(const IgemmArgs 
       return;
     }
   }
-  if constexpr (WIDE && MT == 8 && !TR) {
+  if constexpr (WIDE && MT == 8 && !TR && !LEAKY) {
     if (a.ring_direct) {                                     // wave-uniform
       // register epilogue: no LDS staging, no block barrier (the waves leave at their own pace); the accumulator layout is the
       // ping-pong kernel's (channels x pixels), 64 pixels of the wave's 128 at a time.  Every request of the ring (also the
@@ -2381,7 +2387,7 @@ __global__ __launch_bounds__(NW * 64, 2) void igemm_ring_kernel(const IgemmArgs 
     for (int i = 0; i < NT; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) part[i][j] = acc[i][4 * h + j];
-    igemm_epilogue<T, NT, TR, 32, MT == 4>(a, stage, part, lane, group, n0 + wn * WAVE_N, m0 + wm * MT * 16 + 64 * h);
+    igemm_epilogue<T, NT, TR, 32, MT == 4, LEAKY>(a, stage, part, lane, group, n0 + wn * WAVE_N, m0 + wm * MT * 16 + 64 * h);
   }
   if constexpr (!TR) {
     if (a.split_ws && a.sync) {                              // split-K finished inside the launch by the tile's last block
@@ -2734,7 +2740,17 @@ static int launch_igemm(const mobi_igemm_params* p, const IgemmArgs& a, int grou
 #endif
 #define MOBI_IGEMM_BY_TR(NT_, WM_) \
   do { if (tr) MOBI_IGEMM_BY_FAST(NT_, true, WM_); else MOBI_IGEMM_BY_FAST(NT_, false, WM_); } while (0)
-  if (a.wide == 2) {
+  if (a.epilogue == MOBI_EPI_LEAKY_RELU) {
+    // (igemm_prepare has put every such launch on the ring kernels' staged epilogue: 256- or 128-pixel tiles)
+    if (a.wide == 2) {
+      if (nt5) hipLaunchKernelGGL((igemm_ring_kernel<T, 5, false, 8, 8, false, true>), grid, dim3(512), 0, st, a);
+      else     hipLaunchKernelGGL((igemm_ring_kernel<T, 4, false, 8, 8, false, true>), grid, dim3(512), 0, st, a);
+    } else {
+      if (nt5) hipLaunchKernelGGL((igemm_ring_kernel<T, 5, false, 4, 4, false, true>), grid, dim3(256), 0, st, a);
+      else     hipLaunchKernelGGL((igemm_ring_kernel<T, 4, false, 4, 4, false, true>), grid, dim3(256), 0, st, a);
+    }
+  }
+  else if (a.wide == 2) {
 #define MOBI_W2_LAUNCH(NT_, TR_) hipLaunchKernelGGL((igemm_ring_kernel<T, NT_, TR_, 8, 8>), grid, dim3(512), 0, st, a)
     if (a.ln_svec) {                                         // LayerNorm folded into the launch: instantiations of their own
       if (nt5) hipLaunchKernelGGL((igemm_ring_kernel<T, 5, false, 8, 8, true>), grid, dim3(512), 0, st, a);
@@ -2888,6 +2904,7 @@ extern "C" int mobi_debug_set_phases(void* buf) {
 #endif
 
 extern "C" int mobi_igemm_plan_splits(const mobi_igemm_params* p) {
+  // (GEGLU and MOBI_EPI_LEAKY_RELU launches never split)
   if (!p || p->groups != 1 || p->epilogue != MOBI_EPI_NONE || p->out_mode == MOBI_OUT_TRANSPOSED || p->ln_svec) return 1;
   {
     mobi_igemm_params q = *p;
@@ -2921,7 +2938,11 @@ static int igemm_prepare(const mobi_igemm_params* p, mobi::IgemmArgs& a) {
   if (p->cout <= 0 || p->n_packed <= 0) return MOBI_ERR_ARG;
   if (p->upsample != 0 && p->upsample != 1) return MOBI_ERR_ARG;
   const bool geglu = p->epilogue == MOBI_EPI_GEGLU;
-  if (p->epilogue != MOBI_EPI_NONE && !geglu) return MOBI_ERR_ARG;
+  const bool leaky = p->epilogue == MOBI_EPI_LEAKY_RELU;
+  if (p->epilogue != MOBI_EPI_NONE && !geglu && !leaky) return MOBI_ERR_ARG;
+  // leaky ReLU: row-major output, one pass, no LayerNorm fold, tap-major k (the ring kernels' staged epilogue applies it)
+  if (leaky && (p->out_mode == MOBI_OUT_TRANSPOSED || p->ln_svec || p->split_k > 1 || p->k_order != 0))
+    return MOBI_ERR_UNSUPPORTED;
   if (p->out_mode < 0 || p->out_mode > 2) return MOBI_ERR_ARG;
   if (p->out_mode != MOBI_OUT_TRANSPOSED && (p->cout & 7)) return MOBI_ERR_UNSUPPORTED;
   if (geglu && (p->out_mode != MOBI_OUT_ROWS || p->rowvec || p->residual)) return MOBI_ERR_UNSUPPORTED;
@@ -3111,7 +3132,28 @@ static int igemm_prepare(const mobi_igemm_params* p, mobi::IgemmArgs& a) {
         (!p->rowvec || (!p->bias && a.hw_out % 128 == 0)) && a.M % 256 == 0 && p->n_packed % bnw == 0 && p->scale == 1.0f)
       a.ring_direct = 1;
   }
-  a.small = lnf ? 0 : small_tile(p);
+  if (leaky) {
+    // MOBI_EPI_LEAKY_RELU lives in the ring kernels' LDS-staged epilogue only: 256 x 256 (320) tiles for launches of the
+    // 256-pixel geometry with at least 256 output channels, 128 x 128 (160) tiles otherwise; the register epilogues, the
+    // ping-pong / direct / small kernels and the 64-deep ring never see it.  Operands beyond the ring's 2 GB: unsupported.
+    if (!ring_ok) return MOBI_ERR_UNSUPPORTED;
+    a.pp = 0; a.epi_direct = 0; a.sm_direct = 0; a.ring_direct = 0; a.sm64 = 0; a.n_major = 0;
+    if (a.wm == 4 && p->n_packed >= 256) {
+      const int bnw = (p->n_packed % 160) == 0 ? 320 : 256;
+      a.wide = 2; a.sm = 0;
+      a.tiles_m = (a.M + 255) / 256;
+      a.tiles_n = (p->n_packed + bnw - 1) / bnw;
+    } else {
+      a.wide = 0; a.wm = 2; a.sm = 1;
+      a.tiles_m = (a.M + 127) / 128;
+      a.tiles_n = (p->n_packed + bn - 1) / bn;
+    }
+    a.w_tiled = (p->weight_tiled && (p->groups == 1 || p->w_group_stride == (long long)p->n_packed * a.ktot) &&
+                 p->n_packed % 16 == 0 && a.ktot % 32 == 0 && !(reinterpret_cast<uintptr_t>(p->weight_tiled) & 15) &&
+                 tuning().w_tiled != 0) ? p->weight_tiled : nullptr;
+    if ((long long)a.tiles_m * a.tiles_n > 0x7fffffffLL) return MOBI_ERR_UNSUPPORTED;
+  }
+  a.small = lnf || leaky ? 0 : small_tile(p);
   if (lnf && !(a.wide || a.sm)) return MOBI_ERR_UNSUPPORTED;  // (operands beyond the ring kernels' 2 GB: LayerNorm as a launch)
   // split-K finished inside the launch: the LDS-DMA kernels (ring tiles of every geometry; the ping-pong kernel when every
   // block owns exactly one output tile -- its epilogue is deferred into the next tile's loop otherwise); the register-staged

@@ -15,7 +15,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import (ACT_GELU, ACT_NONE, ACT_SILU, EPI_GEGLU, EPI_NONE, MOBI_BF16, MOBI_F16, OUT_ROWS, OUT_ROWS_F32,
+from ._lib import (ACT_GELU, ACT_NONE, ACT_SILU, EPI_GEGLU, EPI_LEAKY_RELU, EPI_NONE, MOBI_BF16, MOBI_F16, OUT_ROWS, OUT_ROWS_F32,
                    OUT_TRANSPOSED)
 
 
@@ -710,7 +710,7 @@ def finished(x):
 
 def igemm(x, pw: Packed, *, x2=None, stride=1, pad=None, upsample=False, hout=None, wout=None, rowvec=None,
           rowvec_has_bias=False, residual=None, out=None, out_mode=OUT_ROWS, scale=1.0, weight_per_image=False,
-          w_group_stride=0, split_k=None, groups=1, defer=None):
+          w_group_stride=0, split_k=None, groups=1, defer=None, leaky=False):
     """x: [N,H,W,C0] (tokens: [N,T,1,C]); x2: optional second source concatenated on channels.
     defer: None, or "keep" / "drop" -- the caller promises that the result's FIRST reader is a GroupNorm over it: a launch that
     splits k then returns a `Deferred` (no reduce launch; "keep": the GroupNorm also writes the summed tensor, "drop": nobody
@@ -718,7 +718,8 @@ def igemm(x, pw: Packed, *, x2=None, stride=1, pad=None, upsample=False, hout=No
     rowvec: fp32 [N, cout] added per image; rowvec_has_bias: its producer already added this layer's bias (the
     launch then passes no bias, which keeps it on the register-epilogue kernels).
     groups = g > 1: `pw` holds g stacked matrices [g * cout][k]; image i is multiplied by matrix i // (N / g) (ONE launch for
-    the camera images' and the lidar images' projections of a [camera ; lidar] batch); no bias."""
+    the camera images' and the lidar images' projections of a [camera ; lidar] batch); no bias.
+    leaky: MOBI_EPI_LEAKY_RELU, out = leaky_0.1(conv + bias + rowvec) + residual (RangeNet++'s BN-folded layers)."""
     lib = _lib.load()
     x, x2, residual = finished(x), finished(x2), finished(residual)
     n, hin, win, c0 = x.shape
@@ -766,7 +767,8 @@ def igemm(x, pw: Packed, *, x2=None, stride=1, pad=None, upsample=False, hout=No
     p.out = _ptr(out)
     p.out_img_stride = 0 if s == dense_out else s
     p.out_mode = out_mode
-    p.epilogue = EPI_GEGLU if pw.geglu else EPI_NONE
+    assert not (leaky and pw.geglu)
+    p.epilogue = EPI_GEGLU if pw.geglu else (EPI_LEAKY_RELU if leaky else EPI_NONE)
     p.scale = scale
     p.k_order = pw.k_order
     if pw.svec is not None:                                  # LayerNorm folded into this launch: never split (a block sweeps all of k)
@@ -1456,4 +1458,39 @@ def row_cosine(a, b, eps=1e-8, scale=1.0):
     assert a.dtype == b.dtype == torch.float32 and a.shape == b.shape and a.dim() == 2 and a.is_contiguous() and b.is_contiguous()
     out = torch.empty((a.shape[0],), device=a.device, dtype=torch.float32)
     _lib.check(lib.mobi_row_cosine(_ptr(a), _ptr(b), _ptr(out), a.shape[0], a.shape[1], eps, scale, _stream()), "mobi_row_cosine")
+    return out
+
+
+# --------------------------------------------------------------------------------------
+# Fréchet realism metrics (mobi_amd/realism.py)
+# --------------------------------------------------------------------------------------
+def feature_moments(feat, shift, sum_, cross=None):
+    """sum_ f64 [D] += sum_r (feat_r - shift); cross f64 [D, D] (optional) += the centred cross products; feat f32 [R, D]."""
+    lib = _lib.load()
+    r, d = feat.shape
+    assert feat.dtype == torch.float32 and feat.is_contiguous() and sum_.dtype == torch.float64 and sum_.numel() == d
+    assert shift is None or (shift.dtype == torch.float64 and shift.is_contiguous() and shift.numel() == d)
+    assert cross is None or (cross.dtype == torch.float64 and cross.is_contiguous() and cross.numel() == d * d)
+    _lib.check(lib.mobi_feature_moments(_ptr(feat), r, d, _ptr(shift), _ptr(sum_), _ptr(cross), _stream()),
+               "mobi_feature_moments")
+
+
+def frd_input(raw, dtype, hout=64, wout=1024, cpad=32, depth_min=1.4, depth_max=54.0):
+    """f32 [N, 4, h, w] range views -> T [N, hout, wout, cpad]: RangeNet++'s 5 input channels, zero-padded."""
+    lib = _lib.load()
+    n, four, h, w = raw.shape
+    assert four == 4 and raw.dtype == torch.float32 and raw.is_contiguous()
+    out = torch.empty((n, hout, wout, cpad), device=raw.device, dtype=dtype)
+    _lib.check(lib.mobi_frd_input(_ptr(raw), _ptr(out), n, h, w, hout, wout, cpad, depth_min, depth_max, _dt(dtype), _stream()),
+               "mobi_frd_input")
+    return out
+
+
+def band_mean(x, skip=None, bands=16):
+    """T [N, H, W, C] (+ skip of the same shape) -> f32 [N, C * bands]: the mean of band b of channel c at c * bands + b."""
+    lib = _lib.load()
+    n, h, w, c = x.shape
+    assert x.is_contiguous() and (skip is None or (skip.shape == x.shape and skip.dtype == x.dtype and skip.is_contiguous()))
+    out = torch.empty((n, c * bands), device=x.device, dtype=torch.float32)
+    _lib.check(lib.mobi_band_mean(_ptr(x), _ptr(skip), _ptr(out), n, h, w, c, bands, _dt(x.dtype), _stream()), "mobi_band_mean")
     return out

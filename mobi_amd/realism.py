@@ -8,13 +8,20 @@
              mean_hw sum_c lin_c (unit-normalised a - unit-normalised b)^2 (mobi_lpips_distance, fp32), summed over layers.
   CLIP       OpenAI ViT-B/32 `encode_image` on CLIPVisionTower (the conditioning producer's tower at another config) ->
              768 -> 512 projection (mobi_linear_f32) -> 100 cos (mobi_row_cosine).
+  FID        `eval_tool/camera/fid_score.py`: the Fréchet distance of raw CLIP `encode_image` embeddings of two un-paired
+             image sets (CLIPScore.embed), moments in fp64 on the device (mobi_feature_moments), distance on the host.
+  FRD        `eval_tool/lidar/frd_score.py`: the same distance on RangeNet++ 'depth' features of 64 x 1024 range views:
+             mobi_frd_input -> 67 mobi_igemm launches (BN folded, MOBI_EPI_LEAKY_RELU; stride-(1, 2) and transposed
+             convolutions rewritten on the paired-width view) -> mobi_band_mean (with the last decoder skip).
 
 Storage type: fp16 unless asked otherwise (bf16 accepted), whatever `set_engine_dtype` says; norms, sums and the
 projection are fp32.
 
     python -m mobi_amd.realism lpips --path_target A --path_pred B --alexnet alexnet-owt-7be5be79.pth --lin alex.pth
     python -m mobi_amd.realism clip --path_ref A --path_pred B --weights ViT-B-32.pt
-print `LPIPS:  <mean>` / `CLIP:  <mean>`, the reference tools' lines.
+    python -m mobi_amd.realism fid --path_target A --path_pred B --weights ViT-B-32.pt
+    python -m mobi_amd.realism frd --path-target A --path-pred B --weights-dir DIR
+print `LPIPS:  <mean>` / `CLIP:  <mean>` / `FID:  <v>` / `FRD:  <v>`, the reference tools' lines.
 """
 import argparse
 import contextlib
@@ -249,6 +256,317 @@ class CLIPScore:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Fréchet distance (FID, FRD): fp64 moments on the device, the distance on the host
+# ---------------------------------------------------------------------------------------------------------------------
+def frechet_distance(mu1, sigma1, mu2, sigma2):
+    """|mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr sqrtm(S1 S2), fp64 numpy, without scipy: tr sqrtm(S1 S2) is the sum of
+    sqrt(max(lambda, 0)) over the eigenvalues of the symmetric S1^1/2 S2 S1^1/2 (S1^1/2 from eigh(S1), eigenvalues clamped
+    at 0), which has the eigenvalues of S1 S2.  Intended differences to the reference's scipy.linalg.sqrtm form: no complex
+    branch (the eigenvalues of a product of two PSD matrices are real and >= 0; rounding below 0 is clamped), hence no
+    'Imaginary component' error, and no eps-offset retry."""
+    mu1, mu2 = np.atleast_1d(np.asarray(mu1, np.float64)), np.atleast_1d(np.asarray(mu2, np.float64))
+    s1, s2 = np.atleast_2d(np.asarray(sigma1, np.float64)), np.atleast_2d(np.asarray(sigma2, np.float64))
+    if mu1.shape != mu2.shape or s1.shape != s2.shape:
+        raise ValueError(f"Fréchet distance of mismatched statistics: {mu1.shape} / {mu2.shape}, {s1.shape} / {s2.shape}")
+    w, v = np.linalg.eigh((s1 + s1.T) / 2)
+    r = (v * np.sqrt(np.clip(w, 0.0, None))) @ v.T
+    m = r @ s2 @ r
+    lam = np.linalg.eigvalsh((m + m.T) / 2)
+    diff = mu1 - mu2
+    return float(diff.dot(diff) + np.trace(s1) + np.trace(s2) - 2.0 * np.sqrt(np.clip(lam, 0.0, None)).sum())
+
+
+class FrechetStats:
+    """Streaming mean / covariance (ddof 1) of f32 [rows, dim] feature batches: sum and cross products of rows minus a shift
+    (the first batch's mean) accumulated in fp64 on the device by mobi_feature_moments, in a fixed order (bit-reproducible);
+    nothing goes to the host before `mu_sigma`."""
+
+    def __init__(self, dim, device="cuda"):
+        self.dim, self.device, self.n = dim, torch.device(device), 0
+        self.shift = None
+        self.sum = torch.zeros((dim,), device=self.device, dtype=torch.float64)
+        self.cross = torch.zeros((dim, dim), device=self.device, dtype=torch.float64)
+
+    def update(self, feat):
+        feat = feat.to(device=self.device, dtype=torch.float32).contiguous()
+        if feat.dim() != 2 or feat.shape[1] != self.dim:
+            raise ValueError(f"feature batch {tuple(feat.shape)}, expected [rows, {self.dim}]")
+        if feat.shape[0] == 0:
+            return self
+        if self.shift is None:
+            s = torch.zeros((self.dim,), device=self.device, dtype=torch.float64)
+            ops.feature_moments(feat, None, s)
+            self.shift = s / feat.shape[0]
+        ops.feature_moments(feat, self.shift, self.sum, self.cross)
+        self.n += feat.shape[0]
+        return self
+
+    def mu_sigma(self):
+        if self.n < 2:
+            raise ValueError(f"a Fréchet distance needs at least 2 feature rows per set, got {self.n}")
+        s, c, shift = (t.cpu().numpy() for t in (self.sum, self.cross, self.shift))
+        mu = shift + s / self.n
+        sigma = (c - np.outer(s, s) / self.n) / (self.n - 1)
+        return mu, (sigma + sigma.T) / 2
+
+
+def _stats_of_batches(batches, embed, dim, device):
+    st = FrechetStats(dim, device)
+    for b in batches:
+        st.update(embed(b))
+    return st.mu_sigma()
+
+
+def _batches(x, batch_size):
+    return [x[i:i + batch_size] for i in range(0, x.shape[0], batch_size)]
+
+
+class FID:
+    """FID as eval_tool/camera/fid_score.py computes it: the Fréchet distance of raw CLIP ViT-B/32 `encode_image` embeddings
+    (512-d, not L2-normalised; its InceptionV3 wrapper returns the CLIP embedding), over two un-paired image sets."""
+
+    def __init__(self, clip, batch_size=64):
+        self.clip, self.batch_size = clip, batch_size
+
+    @classmethod
+    def from_openai(cls, path, dtype=torch.float16, device="cuda", batch_size=64):
+        return cls(CLIPScore.from_openai(path, dtype=dtype, device=device), batch_size)
+
+    def stats(self, images):
+        """f32 [N, 3, 224, 224] in [0, 1] (or an iterable of such batches) -> (mu, sigma), fp64 numpy."""
+        batches = _batches(images, self.batch_size) if torch.is_tensor(images) else images
+        return _stats_of_batches(batches, self.clip.embed, self.clip.proj.shape[0], self.clip.device)
+
+    def __call__(self, set_a, set_b):
+        return frechet_distance(*self.stats(set_a), *self.stats(set_b))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# RangeNet++ (Darknet-53 backbone + decoder, OS 32, eval_tool/lidar/rangenet/model.py) on mobi_igemm
+# ---------------------------------------------------------------------------------------------------------------------
+RANGENET_BLOCKS = (1, 2, 8, 8, 4)                 # Darknet-53 BasicBlocks per encoder stage
+RANGENET_ENC = ((32, 64), (64, 128), (128, 256), (256, 512), (512, 1024))
+RANGENET_DEC = ((1024, 512), (512, 256), (256, 128), (128, 64), (64, 32))
+RANGENET_H, RANGENET_W, RANGENET_BANDS = 64, 1024, 16
+FRD_DEPTH = (1.4, 54.0)
+BN_EPS = 1e-5
+BN_KEYS = ("weight", "bias", "running_mean", "running_var", "num_batches_tracked")
+RANGENET_MAX_BATCH = 128        # every operand of the heaviest launches below 2 GB (the ring kernels' buffer offsets)
+
+
+def rangenet_keys():
+    """(backbone keys, decoder keys) of the reference's two state dicts (312 and 95)."""
+    bn = lambda pre: [f"{pre}.{k}" for k in BN_KEYS]
+    block = lambda pre: [f"{pre}.conv1.weight", *bn(f"{pre}.bn1"), f"{pre}.conv2.weight", *bn(f"{pre}.bn2")]
+    bb = ["conv1.weight", *bn("bn1")]
+    for i, nb in enumerate(RANGENET_BLOCKS, 1):
+        bb += [f"enc{i}.conv.weight", *bn(f"enc{i}.bn")]
+        for r in range(nb):
+            bb += block(f"enc{i}.residual_{r}")
+    dec = []
+    for i in range(5, 0, -1):
+        dec += [f"dec{i}.upconv.weight", f"dec{i}.upconv.bias", *bn(f"dec{i}.bn"), *block(f"dec{i}.residual")]
+    return bb, dec
+
+
+def _check_keys(sd, want, what):
+    have, want = set(sd.keys()), set(want)
+    missing, extra = sorted(want - have), sorted(have - want)
+    if missing or extra:
+        raise KeyError(f"RangeNet {what} state dict: missing keys {missing[:8]}{' ...' if len(missing) > 8 else ''}, "
+                       f"unexpected keys {extra[:8]}{' ...' if len(extra) > 8 else ''}")
+
+
+def fold_bn(weight, sd, pre, bias=None, eps=BN_EPS):
+    """Conv weight [O, ...] (+ bias) followed by eval-mode BatchNorm `pre` -> (weight, bias) with the BN folded, fp64."""
+    w = weight.double()
+    s = sd[f"{pre}.weight"].double() / torch.sqrt(sd[f"{pre}.running_var"].double() + eps)
+    b = sd[f"{pre}.bias"].double() - sd[f"{pre}.running_mean"].double() * s
+    if bias is not None:
+        b = b + bias.double() * s
+    return w * s.reshape(-1, *([1] * (w.dim() - 1))), b
+
+
+def stride2_weight(w):
+    """3 x 3 conv, stride (1, 2), pad 1 on [H][W][C] == 3 x 2 conv, stride 1, pad (1, 1 left) on the paired view [H][W/2][2C]:
+    tap 0 (pair x - 1) = [0 | W[..., 0]], tap 1 (pair x) = [W[..., 1] | W[..., 2]].  [O, C, 3, 3] -> [O, 2C, 3, 2]."""
+    o, c, kh, kw = w.shape
+    assert (kh, kw) == (3, 3)
+    out = w.new_zeros((o, 2 * c, 3, 2))
+    out[:, c:, :, 0] = w[:, :, :, 0]
+    out[:, :c, :, 1] = w[:, :, :, 1]
+    out[:, c:, :, 1] = w[:, :, :, 2]
+    return out
+
+
+def upconv_weight(w, bias):
+    """ConvTranspose2d(k [1, 4], stride [1, 2], pad [0, 1]) weight [Cin, Cout, 1, 4] (+ bias [Cout]) == 1 x 3 conv, pad (0, 1),
+    with 2 Cout outputs whose [H][W][2 Cout] result IS the [H][2W][Cout] one: even half taps (W3^T, W1^T, 0), odd half
+    (0, W2^T, W0^T), bias duplicated.  -> ([2 Cout, Cin, 1, 3], [2 Cout])."""
+    cin, cout, kh, kw = w.shape
+    assert (kh, kw) == (1, 4)
+    t = w[:, :, 0, :].permute(1, 0, 2)                     # [Cout, Cin, 4]
+    out = w.new_zeros((2 * cout, cin, 1, 3))
+    out[:cout, :, 0, 0], out[:cout, :, 0, 1] = t[:, :, 3], t[:, :, 1]
+    out[cout:, :, 0, 1], out[cout:, :, 0, 2] = t[:, :, 2], t[:, :, 0]
+    return out, torch.cat([bias, bias])
+
+
+def rangenet_layers(bb, dec):
+    """The 67 convolutions in launch order: (name, weight OIHW fp64, bias fp64, kind) with BN folded and the stride / transpose
+    rewrites applied.  kind: 'stem' (5 -> 32, input padded to 32), 'down' (3 x 2 on the paired view), '1x1', '3x3', 'up'."""
+    out = [("conv1", *fold_bn(bb["conv1.weight"], bb, "bn1"), "stem")]
+    for i, nb in enumerate(RANGENET_BLOCKS, 1):
+        w, b = fold_bn(bb[f"enc{i}.conv.weight"], bb, f"enc{i}.bn")
+        out.append((f"enc{i}.conv", stride2_weight(w), b, "down"))
+        for r in range(nb):
+            pre = f"enc{i}.residual_{r}"
+            out.append((f"{pre}.conv1", *fold_bn(bb[f"{pre}.conv1.weight"], bb, f"{pre}.bn1"), "1x1"))
+            out.append((f"{pre}.conv2", *fold_bn(bb[f"{pre}.conv2.weight"], bb, f"{pre}.bn2"), "3x3"))
+    for i in range(5, 0, -1):
+        w, b = fold_bn(dec[f"dec{i}.upconv.weight"].transpose(0, 1), dec, f"dec{i}.bn", bias=dec[f"dec{i}.upconv.bias"])
+        w, b = upconv_weight(w.transpose(0, 1), b)            # (the BN scales the transpose's output channels: axis 1)
+        out.append((f"dec{i}.upconv", w, b, "up"))
+        pre = f"dec{i}.residual"
+        out.append((f"{pre}.conv1", *fold_bn(dec[f"{pre}.conv1.weight"], dec, f"{pre}.bn1"), "1x1"))
+        out.append((f"{pre}.conv2", *fold_bn(dec[f"{pre}.conv2.weight"], dec, f"{pre}.bn2"), "3x3"))
+    return out
+
+
+def rangenet_shapes(batch, h=RANGENET_H, w=RANGENET_W):
+    """[(batch, hin, win, cin, hout, wout, cout, kh, kw, pad_h, pad_w)] of the 67 launches (cin / cout as mobi_igemm sees them)."""
+    out = [(batch, h, w, CIN_PAD, h, w, 32, 3, 3, 1, 1)]
+    for (ci, co), nb in zip(RANGENET_ENC, RANGENET_BLOCKS):
+        out.append((batch, h, w // 2, 2 * ci, h, w // 2, co, 3, 2, 1, 1))
+        w //= 2
+        out += [(batch, h, w, co, h, w, ci, 1, 1, 0, 0), (batch, h, w, ci, h, w, co, 3, 3, 1, 1)] * nb
+    for ci, co in RANGENET_DEC:
+        out.append((batch, h, w, ci, h, w, 2 * co, 1, 3, 0, 1))
+        w *= 2
+        out += [(batch, h, w, co, h, w, ci, 1, 1, 0, 0), (batch, h, w, ci, h, w, co, 3, 3, 1, 1)]
+    return out
+
+
+def rangenet_igemm_plan(batch=64, dtype=torch.float16):
+    """(mobi_igemm_kernel_variant, mobi_igemm_plan_splits) of the 67 MOBI_EPI_LEAKY_RELU launches of a batch, computed by the
+    library's host logic without a launch (no device needed)."""
+    lib = _lib.load()
+    plans = []
+    for j, (n, hi, wi, ci, ho, wo, co, kh, kw, ph, pw) in enumerate(rangenet_shapes(batch)):
+        q = _lib.IgemmParams()
+        q.src0 = q.weight = q.out = q.bias = q.weight_tiled = 4096                  # placeholders: nothing is launched
+        q.c0, q.batch, q.hin, q.win, q.hout, q.wout = ci, n, hi, wi, ho, wo
+        q.kh, q.kw, q.stride, q.pad_h, q.pad_w, q.groups = kh, kw, 1, ph, pw, 1
+        q.n_packed = q.cout = co
+        q.scale, q.dtype, q.epilogue = 1.0, ops._dt(dtype), _lib.EPI_LEAKY_RELU
+        if kh == 3 and kw == 3 and j > 0:
+            q.residual = 4096
+        plans.append((lib.mobi_igemm_kernel_variant(C.byref(q)), lib.mobi_igemm_plan_splits(C.byref(q))))
+    return plans
+
+
+class RangeNet:
+    """RangeNet++ (Darknet-53, OS 32) features for FRD: Model(x, return_final_logits=True, agg_type='depth') in eval mode.
+    Every convolution is one mobi_igemm launch with BatchNorm folded into weights and bias and MOBI_EPI_LEAKY_RELU (the
+    BasicBlock's residual in the same epilogue, after the activation); decoder skips by mobi_add, the last one inside
+    mobi_band_mean."""
+
+    def __init__(self, layers, dtype=torch.float16, device="cuda"):
+        self.dtype, self.device = _check_dtype(dtype), torch.device(device)
+        self.packed = {}
+        for name, w, b, kind in layers:
+            w = w.float()
+            if kind == "stem":
+                self.packed[name] = ops.pack_conv_padded_cin(w, b.float(), dtype, self.device, CIN_PAD)
+            else:
+                self.packed[name] = ops.pack_conv(w, b.float(), dtype, self.device)
+
+    @classmethod
+    def from_state_dicts(cls, backbone_sd, decoder_sd, dtype=torch.float16, device="cuda"):
+        bb_keys, dec_keys = rangenet_keys()
+        _check_keys(backbone_sd, bb_keys, "backbone")
+        _check_keys(decoder_sd, dec_keys, "segmentation_decoder")
+        bb = {k: v.detach().cpu() for k, v in backbone_sd.items()}
+        dec = {k: v.detach().cpu() for k, v in decoder_sd.items()}
+        return cls(rangenet_layers(bb, dec), dtype=dtype, device=device)
+
+    def _conv(self, x, name, residual=None, **kw):
+        return ops.igemm(x, self.packed[name], residual=residual, leaky=True, **kw)
+
+    def _block(self, x, pre):
+        t = self._conv(x, f"{pre}.conv1")
+        return self._conv(t, f"{pre}.conv2", residual=x)
+
+    def forward_prepared(self, x):
+        """T [B, 64, 1024, 32] (mobi_frd_input) -> f32 [B, 512]."""
+        n, h, w, _ = x.shape
+        x = self._conv(x, "conv1")
+        skips = [x]
+        for i, nb in enumerate(RANGENET_BLOCKS, 1):
+            n, h, w, c = x.shape
+            x = self._conv(x.view(n, h, w // 2, 2 * c), f"enc{i}.conv", hout=h, wout=w // 2)
+            for r in range(nb):
+                x = self._block(x, f"enc{i}.residual_{r}")
+            skips.append(x)
+        skips.pop()                                          # the last encoder output is the decoder's input, not a skip
+        for i in range(5, 0, -1):
+            u = self._conv(x, f"dec{i}.upconv")
+            n, h, w, c2 = u.shape
+            u = u.view(n, h, 2 * w, c2 // 2)                 # [H][W][2C] is [H][2W][C]
+            x = self._block(u, f"dec{i}.residual")
+            skip = skips.pop()
+            if i > 1:
+                x = ops.add(x, skip)
+        return ops.band_mean(x, skip, RANGENET_BANDS)
+
+    def prepare(self, raw):
+        """f32 [B, 4, h, w] range views -> T [B, 64, 1024, 32] (mobi_frd_input)."""
+        raw = raw.to(device=self.device, dtype=torch.float32).contiguous()
+        return ops.frd_input(raw, self.dtype, RANGENET_H, RANGENET_W, CIN_PAD, *FRD_DEPTH)
+
+    def features(self, raw, batch_size=64):
+        """f32 [B, 4, h, w] range views (normalised depth, intensity, pitch, yaw) -> f32 [B, 512]."""
+        if raw.dim() != 4 or raw.shape[1] != 4:
+            raise ValueError(f"RangeNet takes [B, 4, h, w] range views, got {tuple(raw.shape)}")
+        bs = max(1, min(batch_size, RANGENET_MAX_BATCH))
+        outs = []
+        with torch.no_grad():
+            for i in range(0, raw.shape[0], bs):
+                outs.append(self.forward_prepared(self.prepare(raw[i:i + bs])))
+        return torch.cat(outs) if outs else torch.zeros((0, 512), device=self.device)
+
+
+class FRD:
+    """FRD as eval_tool/lidar/frd_score.py computes it: the Fréchet distance of RangeNet++ 'depth' features (512-d)."""
+
+    def __init__(self, net, batch_size=64):
+        self.net, self.batch_size = net, batch_size
+
+    @classmethod
+    def from_state_dicts(cls, backbone_sd, decoder_sd, dtype=torch.float16, device="cuda", batch_size=64):
+        return cls(RangeNet.from_state_dicts(backbone_sd, decoder_sd, dtype=dtype, device=device), batch_size)
+
+    @classmethod
+    def from_folder(cls, path, dtype=torch.float16, device="cuda", batch_size=64):
+        """The reference's model folder: `<path>/backbone` and `<path>/segmentation_decoder` state dicts."""
+        path = pathlib.Path(path)
+        bb = torch.load(path / "backbone", map_location="cpu", weights_only=True)
+        dec = torch.load(path / "segmentation_decoder", map_location="cpu", weights_only=True)
+        return cls.from_state_dicts(bb, dec, dtype=dtype, device=device, batch_size=batch_size)
+
+    def features(self, raw):
+        return self.net.features(raw, self.batch_size)
+
+    def stats(self, views):
+        """f32 [N, 4, h, w] (or an iterable of such batches) -> (mu, sigma), fp64 numpy."""
+        batches = _batches(views, self.batch_size) if torch.is_tensor(views) else views
+        return _stats_of_batches(batches, self.features, RANGENET_BANDS * 32, self.net.device)
+
+    def __call__(self, set_a, set_b):
+        return frechet_distance(*self.stats(set_a), *self.stats(set_b))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # files (the reference tools' data path)
 # ---------------------------------------------------------------------------------------------------------------------
 def image_files(path):
@@ -323,6 +641,44 @@ def clip_score_paths(path_ref, path_pred, model, batch_size=64):
     return per.mean().item(), per
 
 
+def range_files(path):
+    """Sorted `*.npy` range views of a directory (the reference globs them unsorted: the statistics do not depend on order)."""
+    return sorted(pathlib.Path(path).glob("*.npy"))
+
+
+def load_range_view(path):
+    """[4, h, w] (normalised depth, intensity, pitch, yaw) -> f32 [4, h, w]."""
+    a = np.load(path)
+    if a.ndim != 3 or a.shape[0] != 4:
+        raise ValueError(f"{path}: range view of shape {a.shape}, expected [4, h, w]")
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+
+
+def _need_two(files, path):
+    if len(files) < 2:
+        raise ValueError(f"a Fréchet distance needs at least 2 files per set, found {len(files)} in {path}")
+    return files
+
+
+def _load_batches(files, load, batch_size):
+    for i in range(0, len(files), batch_size):
+        yield torch.stack([load(f) for f in files[i:i + batch_size]])
+
+
+def fid_paths(path_target, path_pred, model, batch_size=64):
+    """FID between the (un-paired, any count >= 2) images of two directories."""
+    files = [_need_two(image_files(p), p) for p in (path_target, path_pred)]
+    stats = [model.stats(_load_batches(f, clip_image, batch_size)) for f in files]
+    return frechet_distance(*stats[0], *stats[1])
+
+
+def frd_paths(path_target, path_pred, model, batch_size=64):
+    """FRD between the (un-paired, any count >= 2) `*.npy` range views of two directories."""
+    files = [_need_two(range_files(p), p) for p in (path_target, path_pred)]
+    stats = [model.stats(_load_batches(f, load_range_view, batch_size)) for f in files]
+    return frechet_distance(*stats[0], *stats[1])
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m mobi_amd.realism", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     sub = ap.add_subparsers(dest="metric", required=True)
@@ -335,7 +691,15 @@ def main(argv=None):
     cp.add_argument("--path_ref", required=True)
     cp.add_argument("--path_pred", required=True)
     cp.add_argument("--weights", required=True, help="OpenAI ViT-B-32.pt")
-    for p in (lp, cp):
+    fp = sub.add_parser("fid", help="FID on CLIP ViT-B/32 embeddings between two image sets")
+    fp.add_argument("--path_target", required=True)
+    fp.add_argument("--path_pred", required=True)
+    fp.add_argument("--weights", required=True, help="OpenAI ViT-B-32.pt")
+    rp = sub.add_parser("frd", help="FRD on RangeNet++ features between two sets of *.npy range views")
+    rp.add_argument("--path-target", required=True)
+    rp.add_argument("--path-pred", required=True)
+    rp.add_argument("--weights-dir", required=True, help="folder with the RangeNet++ `backbone` and `segmentation_decoder`")
+    for p in (lp, cp, fp, rp):
         p.add_argument("--batch-size", type=int, default=64)
         p.add_argument("--dtype", choices=("fp16", "bf16"), default="fp16")
     args = ap.parse_args(argv)
@@ -344,10 +708,18 @@ def main(argv=None):
         model = LPIPS.from_files(args.alexnet, args.lin, dtype=dtype)
         v, _ = lpips_score_paths(args.path_target, args.path_pred, model, args.batch_size)
         print("LPIPS: ", v)
-    else:
+    elif args.metric == "clip":
         model = CLIPScore.from_openai(args.weights, dtype=dtype)
         v, _ = clip_score_paths(args.path_ref, args.path_pred, model, args.batch_size)
         print("CLIP: ", v)
+    elif args.metric == "fid":
+        model = FID.from_openai(args.weights, dtype=dtype, batch_size=args.batch_size)
+        v = fid_paths(args.path_target, args.path_pred, model, args.batch_size)
+        print("FID: ", v)
+    else:
+        model = FRD.from_folder(args.weights_dir, dtype=dtype, batch_size=args.batch_size)
+        v = frd_paths(args.path_target, args.path_pred, model, args.batch_size)
+        print("FRD: ", v)
     return v
 
 
