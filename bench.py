@@ -2,8 +2,8 @@
 """Benchmark of the MObI sampling hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload mobi_nusc_512|mobi_nusc_256]
-                    [--objects B] [--dtype bf16|fp16] [--cfg-scale S] [--e2e] [--no-cpu-baseline]
-                    [--dump-outputs DIR]
+                    [--objects B] [--dtype bf16|fp16] [--cfg-scale S] [--dump-outputs DIR]
+                    [--full [--no-e2e] [--no-cpu-baseline] [--no-roofline] [--dump-launches FILE] ...]
 
 A "step" is one DDIM denoising step of the whole per-GPU batch: UNet forward on
 2*B interleaved camera/lidar elements (4*B with classifier-free guidance) plus the fp32
@@ -11,10 +11,15 @@ latent update.  Synthetic inputs already resident in HBM, random-init weights of
 mobi_nusc_512 architecture (1.04 B parameters); there is no checkpoint / dataset offline.
 
 Prints ONE JSON line (rank 0): metric = UNet element-forwards per second over all GPUs
-(= denoising steps/s x UNet batch elements), with `steps_per_s`, `roofline` (dominant
+(= denoising steps/s x UNet batch elements), with `steps_per_s`.  A plain run does only what
+that figure needs: set-up, warm-up, the timed steps, `--dump-outputs`, the line.  `--full`
+adds everything else to the same line, each part after the timed steps: `roofline` (dominant
 kernel = the implicit-GEMM conv/linear kernel, algorithmic FLOPs / measured launch time
-against the 2.5 PFLOP/s dense bf16 MFMA peak) and `cpu_baseline` (the CPU oracle --
-the reference graph in PyTorch CPU fp32 -- timed on this host on a bounded sample).
+against the 2.5 PFLOP/s dense bf16 MFMA peak), `cpu_baseline` (the CPU oracle -- the
+reference graph in PyTorch CPU fp32 -- timed on this host on a bounded sample), the
+end-to-end pass, the PLMS + CFG 5 leg, the fp16 sub-record, the sub-records of BASELINE
+configs 2 and 5 and the committed parity record; `--no-roofline`, `--no-e2e` and the like
+drop single parts of it.
 Multi-GPU: `--gpus N` with no WORLD_SIZE in the environment spawns N ranks itself
 (`python -m torch.distributed.run`, one process per GPU, RCCL) BEFORE this process touches the
 GPU, and exits with the child's code; under an external torchrun the ranks run directly.  Objects
@@ -138,12 +143,23 @@ def build_model(workload, seed=0):
     """LatentDiffusion (UNet + camera VAE + lidar VAE) from configs/<workload>.yaml with random-init weights of
     the real architecture (also overwrites the zero-initialised layers).  No checkpoint exists offline: the lidar
     VAE's `ckpt_path` is cleared.  The conditioning producer (CLIP ViT-L/14 tower + mapper + box embedder) is built
-    too: it is not part of a denoising step, but the end-to-end pass runs it as the harness does."""
+    too: it is not part of a denoising step, but the end-to-end pass runs it as the harness does.  Every parameter is
+    drawn below, so the layers' own random init (a third of this function's time) is skipped while they are built:
+    the weights come out the same bit for bit."""
     from mobi_amd.ldm.util import instantiate_from_config, load_config
     cfg = load_config(os.path.join(ROOT, "configs", f"{workload}.yaml"),
                       ["model.params.lidar_stage_config.params.ckpt_path=null"])
     assert cfg["latent_size"] == WORKLOADS[workload]["latent"]
-    model = instantiate_from_config(cfg["model"])
+    random_inits = ("uniform_", "normal_", "trunc_normal_", "kaiming_uniform_", "kaiming_normal_", "xavier_uniform_",
+                    "xavier_normal_", "orthogonal_", "sparse_")
+    saved = {n: getattr(torch.nn.init, n) for n in random_inits}
+    try:
+        for n in random_inits:
+            setattr(torch.nn.init, n, lambda tensor, *a, **k: tensor)
+        model = instantiate_from_config(cfg["model"])
+    finally:
+        for n, f in saved.items():
+            setattr(torch.nn.init, n, f)
     g = torch.Generator().manual_seed(seed)
     with torch.no_grad():
         for name, p in model.named_parameters():
@@ -229,6 +245,10 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16"])
     ap.add_argument("--cfg-scale", type=float, default=1.0, help="1.0 = harness default (no CFG)")
     ap.add_argument("--ddim-steps", type=int, default=50)
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run and report the roofline pass, the CPU "
+                    "baseline, the end-to-end pass, the PLMS, fp16 and BASELINE-config sub-records and the parity record "
+                    "(--no-roofline, --no-cpu-baseline, --no-e2e, --no-plms-line, --no-fp16-line and --no-config-lines drop "
+                    "single parts of it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--dump-launches", default=None, help="write per-launch (kind, GFLOP, us) records of one step")
@@ -246,6 +266,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_launches and not args.full:
+        ap.error("--dump-launches records the roofline pass, which runs with --full only")
 
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
@@ -284,7 +306,12 @@ def main():
     cfg = args.cfg_scale != 1.0
     elems = N * (2 if cfg else 1)
 
-    model = build_model(args.workload).to(device)
+    model = build_model(args.workload)
+    # the host copies are released after the move, all at once: .to() frees each one right after its copy is queued, and
+    # unmapping host memory while copies are in flight made the 6.3 GB move take 1-13 s instead of 0.4 s (+ 0.8 s release)
+    host = [t.data for t in (*model.parameters(), *model.buffers())]
+    model.to(device)
+    del host
     net = model.model.diffusion_model
     sampler = DDIMSampler(model, graph=not args.no_graph)
     sampler.make_schedule(args.ddim_steps, ddim_eta=0.0, verbose=False)
@@ -352,7 +379,7 @@ def main():
 
     # ---- the shipped invocation (scripts/realism_test_bench.sh:95-102): PLMS, classifier-free guidance 5 -------
     plms_line = None
-    if not args.no_plms_line:
+    if args.full and not args.no_plms_line:
         from mobi_amd.ldm.models.diffusion.plms import PLMSSampler
         psampler = PLMSSampler(model, graph=not args.no_graph)
         psteps = 5 if args.steps >= 5 else 4             # S with 1000 % S == 0: exactly S sampler steps
@@ -385,7 +412,7 @@ def main():
     # encodes, CLIP tower + mapper + box embedder for both modalities, the two reconstructions) -> DDIM -> decode_sample
     # -> log_data (post-processing + collages on the device) -> all-gather of the decoded samples -----------------
     objects_per_s = None
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         from mobi_amd import dist as mdist
         R = side * 8
         hole = torch.ones(B, 1, R, R)
@@ -500,7 +527,7 @@ def main():
 
     roofline = None
     kinds = {}
-    if not args.no_roofline and rank == 0:
+    if args.full and not args.no_roofline and rank == 0:
         sink = []
         for rep in range(2):                     # first pass warms the event pool / allocator; the second is kept
             sink.clear()
@@ -621,7 +648,7 @@ def main():
                 roofline["traffic_by_kernel"] = traffic
 
     cpu_baseline = None
-    if not args.no_cpu_baseline and rank == 0 and world == 1:
+    if args.full and not args.no_cpu_baseline and rank == 0 and world == 1:
         from oracle import unet as ounet
         ncpu = max(1, min(os.cpu_count() or 1, args.cpu_threads))   # more threads than this slows torch's CPU convs down
         torch.set_num_threads(ncpu)
@@ -641,7 +668,7 @@ def main():
 
     # ---- the same step with fp16 storage: the storage type that meets the 1e-3 end-to-end tolerance ----------
     fp16_line = None
-    if args.dtype == "bf16" and not args.no_fp16_line:
+    if args.full and args.dtype == "bf16" and not args.no_fp16_line:
         mobi_amd.set_engine_dtype(torch.float16)
         s16 = DDIMSampler(model, graph=not args.no_graph)
         s16.make_schedule(args.ddim_steps, ddim_eta=0.0, verbose=False)
@@ -680,7 +707,7 @@ def main():
     # dataset's classes), 8 objects per rank, the [1, 5, ..., 997] table; the step time does not depend on the timestep, so a
     # handful of steps of the 250 are timed.
     config_lines = {}
-    if args.workload == "mobi_nusc_512" and not args.no_config_lines and not cfg:
+    if args.full and args.workload == "mobi_nusc_512" and not args.no_config_lines and not cfg:
         from mobi_amd.ldm.util import load_config
 
         def unet_params(name):
@@ -848,7 +875,7 @@ def main():
         out.update(config_lines)
         # end-to-end parity at production width, from the committed measurement of the GPU suite (never re-measured here: the
         # oracle run behind it takes minutes of CPU): both storage types, the benched one first
-        par = parity_record(side, args.dtype)
+        par = parity_record(side, args.dtype) if args.full else None
         if par:
             out["parity"] = par["parity"]
             out["meets_north_star_tolerance"] = par["meets"]

@@ -76,6 +76,18 @@ def test_single_process_default():
     assert _line(r.stdout)["n_gpus"] == 1
 
 
+def test_full_option(tmp_path):
+    """`--full` (everything beyond the headline) is an option of its own; `--dump-launches` records a pass that only a
+    --full run makes, and is refused without it rather than silently writing nothing."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "0", "--full"], env=_env(),
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert _line(r.stdout)["steps"] == 2
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--dump-launches", str(tmp_path / "l.tsv")],
+                       env=_env(), capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--full" in r.stderr
+
+
 def test_dump_outputs_and_step_count(tmp_path):
     """`--dump-outputs DIR` writes the last timed step's result as float32 .npy files, the same from run to run (seeded
     inputs); `--steps` is the number of timed steps the line's ms_per_step divides by, and fewer than one is refused."""
