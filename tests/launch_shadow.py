@@ -1,9 +1,12 @@
-"""Launch shadow (TEST INFRASTRUCTURE, not a conftest): every launch of a UNet forward checked on its own against a float64
-restatement of its entry point's contract (include/mobi_engine.h, the docstrings of mobi_amd/ops.py).
+"""Launch shadow (TEST INFRASTRUCTURE, not a conftest): every launch of a UNet forward or a VAE encode / decode checked on its
+own against a float64 restatement of its entry point's contract (include/mobi_engine.h, the docstrings of mobi_amd/ops.py).
 
 `LaunchShadow(monkeypatch)` wraps the `mobi_amd.ops` entry points the model files call as `ops.<name>(...)`: igemm (and with it
-`linear`, which calls the module's igemm), Deferred.finish, groupnorm, layernorm, attention, ctx_attention, ff_geglu and
-two_key_adapter.  Per call it snapshots the operands, runs the original with the same arguments, synchronises, computes the
+`linear`, which calls the module's igemm), Deferred.finish, groupnorm, layernorm, attention, ctx_attention, ff_geglu,
+two_key_adapter and the VAEs' softmax_rows, split_f32, trunk_add, lincomb4, conv_small_cout, conv_small_cin and pack_sources.
+An igemm with per-image weights (the VAEs' mid attention) multiplies image i by slab i of the weight tensor's own shape; a
+`w_group_stride` that disagrees with it is a failure.  The elementwise entry points are bit-exact where their contract is
+(split_f32's hi and third part, trunk_add, the two-term coefficient-1 lincomb4, pack_sources).  Per call it snapshots the operands, runs the original with the same arguments, synchronises, computes the
 fp64 reference on the device from the snapshots (the storage-rounded packed weights, the fp32 bias / rowvec / svec the launch
 read) and compares:
   * whole-tensor rel-L2 within the bound the form's own unit test asserts (tests/test_gpu_ops.py);
@@ -15,6 +18,10 @@ A split-K launch that returns an `ops.Deferred` stashes its fp64 product on it: 
 against fp64 GroupNorm of that product (and, with `keep`, the tensor it writes against the product), a reduce launch
 (`finish`) like any launch.  The first launch of every distinct variant tag also has 64 of its rows recomputed on the CPU
 in fp64, which must agree with the device reference to 1e-9 (the device BLAS is not trusted blindly).
+
+While a shadow runs, `mobi_amd._lib.load` returns a LibCensus that counts every `mobi_*` entry point called:
+`census_failures()` lists a launching entry point called more often than the shadow judged its kind, and any entry point that
+is neither shadowed nor query-only (LAUNCH_KINDS, QUERY_SUFFIXES): a new unwrapped launch cannot slip past.
 
 Nothing here calls a `mobi_*` entry point: the references are torch float64 (matmul per tap, attention per image and head).
 """
@@ -44,8 +51,50 @@ def bound_gn_f32(dtype):
 
 
 def bound_gn_split(dtype):
-    """hi + lo of GN_OUT_SPLIT / SPLIT3: test_groupnorm_fp32_source_and_precise_outputs."""
+    """hi + lo of GN_OUT_SPLIT / SPLIT3 (and of split_f32): test_groupnorm_fp32_source_and_precise_outputs."""
     return 2e-6 if dtype == torch.float16 else 2e-5
+
+
+BOUND_LINCOMB = 1e-6            # test_sampler_arithmetic_bit_exact: lincomb4 against fp64
+BOUND_SMALL_COUT = 2e-5         # test_conv_small_cout_matrix_core_form: fp32 NCHW output of 16-bit operands
+BOUND_SMALL_CIN_F32 = 2e-6      # test_small_convs: conv_small_cin with out_f32_nchw
+
+# entry points of the library that launch a kernel -> the shadow kind that judges each call
+LAUNCH_KINDS = {"mobi_igemm": "igemm", "mobi_igemm_finish": "split_finish", "mobi_groupnorm": "groupnorm",
+                "mobi_layernorm": "layernorm", "mobi_attention": "attention", "mobi_ctx_attention": "ctx_attention",
+                "mobi_ff_geglu": "ff_geglu", "mobi_two_key_adapter": "two_key_adapter", "mobi_softmax_rows": "softmax_rows",
+                "mobi_split_f32": "split_f32", "mobi_trunk_add": "trunk_add", "mobi_lincomb4": "lincomb4",
+                "mobi_conv_small_cout": "conv_small_cout", "mobi_conv_small_cin": "conv_small_cin",
+                "mobi_pack_nchw_sources": "pack_sources"}
+# entry points that answer a question and launch nothing (mobi_tile_weights: the load-time weight image of a pack)
+QUERY_SUFFIXES = ("_workspace_bytes", "_plan_splits", "_slab_count", "_kernel_variant", "_takes_split", "_sync_bytes",
+                  "_supported", "_fuses_ln", "_packed_bytes", "_weight_bytes")
+QUERY_NAMES = ("mobi_tile_weights", "mobi_error_string", "mobi_build_info", "mobi_abi_version", "mobi_struct_size")
+
+
+def is_query_only(name):
+    return name in QUERY_NAMES or name.endswith(QUERY_SUFFIXES)
+
+
+class LibCensus:
+    """Stands in for the loaded library while a shadow runs: counts every `mobi_*` entry point called through it."""
+
+    def __init__(self, lib, calls):
+        self._lib, self._calls, self._fns = lib, calls, {}
+
+    def __getattr__(self, name):
+        fn = self._fns.get(name)
+        if fn is None:
+            real = getattr(self._lib, name)
+            if not name.startswith("mobi_") or not callable(real):
+                return real
+            calls = self._calls
+
+            def fn(*a):
+                calls[name] = calls.get(name, 0) + 1
+                return real(*a)
+            self._fns[name] = fn
+        return fn
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -100,6 +149,52 @@ class OutsideView:
 
     def unchanged(self):
         return not self.any or torch.equal(_bits(self.flat)[self.mask], self.before)
+
+
+def softmax_row_sums(got):
+    """max over rows of |sum of the row - 1| of a softmax output [rows, cols] (fp64 on its device)."""
+    return float((got.double().sum(dim=-1) - 1.0).abs().max())
+
+
+def check_split(x32, out, parts, dtype):
+    """split_f32's contract -> failure strings: hi == T(x) bit for bit, hi + lo within bound_gn_split, part 3 == hi bit for bit."""
+    c = x32.shape[-1]
+    bad = []
+    if tuple(out.shape) != tuple(x32.shape[:-1]) + (parts * c,) or out.dtype != dtype:
+        return [f"shape / dtype {tuple(out.shape)} {out.dtype}"]
+    hi, lo = out[..., :c], out[..., c:2 * c]
+    if not _same(hi, x32.to(dtype)):
+        bad.append("hi is not the rounded input")
+    res = compare((hi.double() + lo.double()).reshape(1, -1, c), x32.double().reshape(1, -1, c))
+    if not passes(res, bound_gn_split(dtype)):
+        bad.append(f"hi + lo rel-L2 {res['rel']:.3e} tile {res['tile']:.3e} (bound {bound_gn_split(dtype):.1e})")
+    if parts == 3 and not _same(out[..., 2 * c:], hi):
+        bad.append("the third part is not hi")
+    return bad
+
+
+def check_trunk_add(before, inc, after, x16, dtype):
+    """trunk_add's contract -> failure strings: the fp32 trunk is before + inc (fp32 add, bit for bit; unchanged for inc None)
+    and the returned copy is the updated trunk rounded to the storage type, bit for bit."""
+    want = before if inc is None else before + inc.float()
+    bad = []
+    if not _same(after, want):
+        bad.append("the fp32 trunk is not trunk + inc" if inc is not None else "the trunk changed without an increment")
+    if x16.dtype != dtype or not _same(x16, want.to(dtype)):
+        bad.append("the 16-bit copy is not the updated trunk rounded")
+    return bad
+
+
+def per_image_weights(w, n, n_packed, k, w_group_stride):
+    """The slabs an igemm with weight_per_image multiplies image i by, taken from the weight tensor's own shape
+    ([n, n_packed, k]); raises ValueError if the launch's w_group_stride says otherwise."""
+    if w.numel() != n * n_packed * k:
+        raise ValueError(f"per-image weights: {w.numel()} elements, not {n} images x {n_packed} x {k}")
+    if w.dim() == 3 and w.stride(0) != n_packed * k:
+        raise ValueError(f"per-image weights: the tensor's image stride {w.stride(0)} is not {n_packed * k}")
+    if w_group_stride != n_packed * k:
+        raise ValueError(f"per-image weights: w_group_stride {w_group_stride} disagrees with the tensor's slabs ({n_packed * k})")
+    return w.reshape(n, n_packed, k)
 
 
 def _snap(t):
@@ -333,20 +428,69 @@ def two_key_adapter_op_reference(op, rows=None, dev=None):
     return y.reshape(-1, ch)
 
 
+def softmax_reference(op, rows=None, dev=None):
+    """Row softmax of fp32 scores [rows, cols], spelled out in fp64 (see attention_reference) -> [rows, cols] (rows: those)."""
+    dev = op["s"].device if dev is None else dev
+    s = op["s"].to(dev)
+    outs = []
+    for r in _chunks(s.shape[0], None if rows is None else rows.to(dev), 4096):
+        v = s[r.to(dev)].double()
+        e = torch.exp(v - v.amax(dim=-1, keepdim=True))
+        outs.append(e / e.sum(dim=-1, keepdim=True))
+    return torch.cat(outs)
+
+
+def conv_small_cout_reference(op, rows=None, dev=None):
+    """mobi_conv_small_cout's contract: the convolution of the operands it read (T channels-last, T [cout][tap * C + c]) plus
+    the fp32 bias in fp64, then the clamp -> [images, h * w, cout] (rows: flattened (image, pixel) rows)."""
+    y = igemm_reference(op, rows, dev)
+    return y if op["clamp"] is None else y.clamp(*op["clamp"])
+
+
+def conv_small_cin_op(srcs, weight, bias, kh, kw, pad):
+    """The operand record of a conv_small_cin launch as an igemm_reference form: the fp32 NCHW sources concatenated on channels
+    as channels-last, the OIHW-flattened fp32 weight reordered to k = tap * C + c."""
+    x = torch.cat(srcs, dim=1).permute(0, 2, 3, 1)
+    n, h, w, cin = x.shape
+    cout = weight.shape[0]
+    wt = weight.reshape(cout, cin, kh, kw).permute(0, 2, 3, 1).reshape(cout, kh * kw * cin)
+    return dict(x=x, x2=None, w=wt, bias=bias, kh=kh, kw=kw, stride=1, pad_h=pad[0], pad_w=pad[1], upsample=False,
+                hout=h + 2 * pad[0] - kh + 1, wout=w + 2 * pad[1] - kw + 1, cout=cout, n_packed=cout, groups=1, geglu=False,
+                ln=False, ln_eps=0.0, scale=1.0, rowvec=None, rowvec_has_bias=False, residual=None)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # the shadow
 # ------------------------------------------------------------------------------------------------------------------
 class LaunchShadow:
     """Context manager: `with LaunchShadow(monkeypatch) as sh: net(...)`; then `sh.failures` (strings), `sh.records` (one
-    dict per compared launch), `sh.counts` (launches shadowed per profiler kind)."""
+    dict per compared launch), `sh.counts` (launches shadowed per profiler kind), `sh.calls` (every `mobi_*` entry point called
+    through the library while the shadow ran) and `sh.census_failures()`."""
+
+    WRAPPED = ("igemm", "groupnorm", "layernorm", "attention", "ctx_attention", "ff_geglu", "two_key_adapter", "softmax_rows",
+               "split_f32", "trunk_add", "lincomb4", "conv_small_cout", "conv_small_cin", "pack_sources")
 
     def __init__(self, monkeypatch, verbose=False, label="", cpu_check=True, seed=0):
         from mobi_amd import ops
         self.ops, self.mp, self.verbose, self.label, self.cpu_check = ops, monkeypatch, verbose, label, cpu_check
-        self.records, self.failures, self.counts = [], [], {}
+        self.records, self.failures, self.counts, self.calls = [], [], {}, {}
         self.cpu_checked = set()
         self.pending = {}
+        self.thin = {}                  # data_ptr of a pack_sources output -> its number of sources
         self.gen = torch.Generator().manual_seed(seed)
+
+    def census_failures(self):
+        """Every launching entry point called as often as the shadow judged its kind; no call of an entry point that is
+        neither shadowed nor query-only."""
+        bad = []
+        for name, cnt in sorted(self.calls.items()):
+            kind = LAUNCH_KINDS.get(name)
+            if kind is not None:
+                if self.counts.get(kind, 0) != cnt:
+                    bad.append(f"{name}: {cnt} calls, {self.counts.get(kind, 0)} judged by the shadow")
+            elif not is_query_only(name):
+                bad.append(f"{name}: {cnt} launches no wrapper of the shadow saw")
+        return bad
 
     # -- plumbing ------------------------------------------------------------------------------------------------------
     def __enter__(self):
@@ -356,19 +500,16 @@ class LaunchShadow:
             self.mp.setattr(ops, "_PROFILE", self.sink)
         else:
             self.sink = ops._PROFILE
-        orig = {k: getattr(ops, k) for k in ("igemm", "groupnorm", "layernorm", "attention", "ctx_attention", "ff_geglu",
-                                               "two_key_adapter")}
+        from mobi_amd import _lib
+        orig = {k: getattr(ops, k) for k in self.WRAPPED}
         orig_finish = ops.Deferred.finish
         self.orig = orig
         sh = self
-        self.mp.setattr(ops, "igemm", lambda *a, **k: sh._igemm(orig["igemm"], *a, **k))
-        self.mp.setattr(ops, "groupnorm", lambda *a, **k: sh._groupnorm(orig["groupnorm"], *a, **k))
-        self.mp.setattr(ops, "layernorm", lambda *a, **k: sh._layernorm(orig["layernorm"], *a, **k))
-        self.mp.setattr(ops, "attention", lambda *a, **k: sh._attention(orig["attention"], *a, **k))
-        self.mp.setattr(ops, "ctx_attention", lambda *a, **k: sh._ctx_attention(orig["ctx_attention"], *a, **k))
-        self.mp.setattr(ops, "ff_geglu", lambda *a, **k: sh._ff_geglu(orig["ff_geglu"], *a, **k))
-        self.mp.setattr(ops, "two_key_adapter", lambda *a, **k: sh._two_key_adapter(orig["two_key_adapter"], *a, **k))
+        for k in self.WRAPPED:
+            self.mp.setattr(ops, k, (lambda name: lambda *a, **kw: getattr(sh, "_" + name)(orig[name], *a, **kw))(k))
         self.mp.setattr(ops.Deferred, "finish", lambda d: sh._finish(orig_finish, d))
+        census = LibCensus(_lib.load(), self.calls)
+        self.mp.setattr(_lib, "load", lambda: census)
         return self
 
     def __exit__(self, *exc):
@@ -408,10 +549,10 @@ class LaunchShadow:
         if not err <= CPU_AGREE:
             self._fail(f"{key}: device fp64 reference disagrees with the CPU on {rows.numel()} rows: {err:.3e}")
 
-    def _judge(self, kind, tag, got, ref, bound, extra=""):
+    def _judge(self, kind, tag, got, ref, bound, extra="", form=None):
         res = compare(got, ref)
         ok = passes(res, bound)
-        rec = dict(kind=kind, tag=tag, bound=bound, extra=extra, **res)
+        rec = dict(kind=kind, tag=tag, bound=bound, extra=extra, form=form or {}, **res)
         self.records.append(rec)
         name = f"{kind} {tag} {extra}".strip()
         record(f"shadow {self.label} {name}", res["rel"], bound)
@@ -430,16 +571,26 @@ class LaunchShadow:
                w_group_stride=0, split_k=None, groups=1, defer=None):
         ops = self.ops
         x, x2, residual = ops.finished(x), ops.finished(x2), ops.finished(residual)
-        if weight_per_image or w_group_stride or pw.k_order:
-            raise NotImplementedError("launch shadow: per-image weights / chunk-major k order are not forms of the UNet step")
+        if pw.k_order:
+            raise NotImplementedError("launch shadow: the chunk-major k order exists in the development build only")
+        if w_group_stride and not weight_per_image and groups == 1:
+            raise NotImplementedError("launch shadow: a weight group stride without per-image weights or groups")
         n, hin, win, _ = x.shape
         ph, pw_ = (pw.kh // 2, pw.kw // 2) if pad is None else pad
         hl, wl = (hin * 2, win * 2) if upsample else (hin, win)
         ho = (hl + 2 * ph - pw.kh) // stride + 1 if hout is None else hout
         wo = (wl + 2 * pw_ - pw.kw) // stride + 1 if wout is None else wout
         cout, npk = (pw.cout // groups, pw.n_packed // groups) if groups > 1 else (pw.cout, pw.n_packed)
-        op = dict(x=_snap(x), x2=_snap(x2), w=pw.w, bias=pw.bias, kh=pw.kh, kw=pw.kw, stride=stride, pad_h=ph, pad_w=pw_,
-                  upsample=upsample, hout=ho, wout=wo, cout=cout, n_packed=npk, groups=groups, geglu=pw.geglu,
+        w, ref_groups = pw.w, groups
+        if weight_per_image:                 # image i times slab i of the tensor's own shape, not of the stride argument
+            ref_groups = n
+            try:
+                w = per_image_weights(pw.w, n, npk, pw.kh * pw.kw * pw.cin, w_group_stride)
+            except ValueError as e:
+                self._fail(str(e))
+                w = pw.w.reshape(n, npk, -1)
+        op = dict(x=_snap(x), x2=_snap(x2), w=w, bias=pw.bias, kh=pw.kh, kw=pw.kw, stride=stride, pad_h=ph, pad_w=pw_,
+                  upsample=upsample, hout=ho, wout=wo, cout=cout, n_packed=npk, groups=ref_groups, geglu=pw.geglu,
                   ln=pw.svec is not None, ln_eps=pw.ln_eps, scale=scale, rowvec=_snap(rowvec), rowvec_has_bias=rowvec_has_bias,
                   residual=None if residual is None else residual.detach().reshape(n, ho * wo, cout).clone())
         ins = [("x", x, op["x"]), ("x2", x2, op["x2"]), ("rowvec", rowvec, op["rowvec"])]
@@ -451,10 +602,10 @@ class LaunchShadow:
         n0 = len(self.sink)
         y = orig(x, pw, x2=x2, stride=stride, pad=pad, upsample=upsample, hout=hout, wout=wout, rowvec=rowvec,
                  rowvec_has_bias=rowvec_has_bias, residual=residual, out=out, out_mode=out_mode, scale=scale, split_k=split_k,
-                 groups=groups, defer=defer)
+                 groups=groups, defer=defer, weight_per_image=weight_per_image, w_group_stride=w_group_stride)
         torch.cuda.synchronize()
         self._count("igemm")
-        tag = self._tag(n0, "igemm")
+        tag = self._tag(n0, "igemm") + (" per_image" if weight_per_image else "")
         self._inputs_unchanged(tag, ins + [("weight", pw.w, wsnap[0]), ("bias", pw.bias, wsnap[1]), ("svec", pw.svec, wsnap[2])])
         if outside is not None and not outside.unchanged():
             self._fail(f"{tag}: wrote outside its out view")
@@ -467,7 +618,9 @@ class LaunchShadow:
             self.pending[id(y)] = y
             return y
         got = y.transpose(1, 2) if out_mode == ops.OUT_TRANSPOSED else y.reshape(n, ho * wo, cout)
-        self._judge("igemm", tag, got, ref, bound)
+        form = dict(per_image=weight_per_image, out_mode=out_mode, upsample=upsample, stride=stride, pad=(ph, pw_), hin=hin,
+                    win=win, hout=ho, wout=wo, cin=pw.cin, kh=pw.kh, kw=pw.kw, thin=self.thin.pop(x.data_ptr(), 0))
+        self._judge("igemm", tag, got, ref, bound, form=form)
         return y
 
     def _finish(self, orig, d):
@@ -521,14 +674,15 @@ class LaunchShadow:
         self._cpu_agree(f"groupnorm {tag} {out_mode} {silu}", groupnorm_reference, op, ref, ref.shape[0] * ref.shape[1])
         n, c = ref.shape[0], ref.shape[2]
         y3 = y.reshape(n, ref.shape[1], -1)
+        form = dict(out_mode=out_mode)
         if out_mode == ops.GN_OUT_T:
-            self._judge("groupnorm", tag, y3, ref, TOL[t_dtype], extra)
+            self._judge("groupnorm", tag, y3, ref, TOL[t_dtype], extra, form=form)
         elif out_mode == ops.GN_OUT_F32:
-            self._judge("groupnorm", tag, y3, ref, bound_gn_f32(t_dtype), extra + " f32")
+            self._judge("groupnorm", tag, y3, ref, bound_gn_f32(t_dtype), extra + " f32", form=form)
         else:
             self._judge("groupnorm", tag, y3[..., :c].double() + y3[..., c:2 * c].double(), ref, bound_gn_split(t_dtype),
-                        extra + " hi+lo")
-            self._judge("groupnorm", tag, y3[..., :c], ref, TOL[t_dtype], extra + " hi")
+                        extra + " hi+lo", form=form)
+            self._judge("groupnorm", tag, y3[..., :c], ref, TOL[t_dtype], extra + " hi", form=form)
             if out_mode == ops.GN_OUT_SPLIT3 and not torch.equal(y3[..., 2 * c:], y3[..., :c]):
                 self._fail(f"groupnorm {tag}: SPLIT3's third part is not hi")
         return y
@@ -620,3 +774,116 @@ class LaunchShadow:
                 want = layernorm_rows(ref[i::2], g, bb, ln_eps)
                 self._judge("two_key_adapter", tag, got, want, TOL[x.dtype], extra=f"ln_pair[{i}]")
         return r
+
+    # -- the VAEs' entry points ------------------------------------------------------------------------------------------
+    def _softmax_rows(self, orig, s, dtype):
+        snap = _snap(s)
+        y = orig(s, dtype)
+        torch.cuda.synchronize()
+        self._count("softmax_rows")
+        rows, cols = snap.numel() // snap.shape[-1], snap.shape[-1]
+        tag = f"rows={rows} cols={cols}"
+        self._inputs_unchanged("softmax_rows " + tag, [("s", s, snap)])
+        op = dict(s=snap.reshape(rows, cols))
+        ref = softmax_reference(op)
+        self._cpu_agree("softmax_rows " + tag, softmax_reference, op, ref, rows)
+        got = y.reshape(rows, cols)
+        self._judge("softmax_rows", tag, got.reshape(1, rows, cols), ref.reshape(1, rows, cols), TOL[dtype])
+        dev = softmax_row_sums(got)
+        if not dev < TOL[dtype]:
+            self._fail(f"softmax_rows {tag}: a row sums to 1 +- {dev:.3e} (bound {TOL[dtype]:.1e})")
+        return y
+
+    def _split_f32(self, orig, x32, dtype, parts=2):
+        snap = _snap(x32)
+        y = orig(x32, dtype, parts)
+        torch.cuda.synchronize()
+        self._count("split_f32")
+        c = snap.shape[-1]
+        tag = f"rows={snap.numel() // c} c={c} parts={parts}"
+        self._inputs_unchanged("split_f32 " + tag, [("x", x32, snap)])
+        for msg in check_split(snap, y, parts, dtype):
+            self._fail(f"split_f32 {tag}: {msg}")
+        self._judge("split_f32", tag, (y[..., :c].double() + y[..., c:2 * c].double()).reshape(1, -1, c), snap.reshape(1, -1, c),
+                    bound_gn_split(dtype), extra="hi+lo", form=dict(parts=parts))
+        return y
+
+    def _trunk_add(self, orig, trunk, inc, dtype):
+        before, incs = _snap(trunk), _snap(inc)
+        y = orig(trunk, inc, dtype)
+        torch.cuda.synchronize()
+        self._count("trunk_add")
+        c = trunk.shape[-1]
+        tag = f"n={trunk.numel()} inc={int(inc is not None)}"
+        self._inputs_unchanged("trunk_add " + tag, [("inc", inc, incs)])
+        for msg in check_trunk_add(before, incs, trunk, y, dtype):
+            self._fail(f"trunk_add {tag}: {msg}")
+        want = before.double() if incs is None else before.double() + incs.double()
+        self._judge("trunk_add", tag, y.reshape(1, -1, c), want.reshape(1, -1, c), TOL[dtype], extra="16-bit copy")
+        return y
+
+    def _lincomb4(self, orig, es, cs):
+        snaps = [_snap(e) for e in es]
+        y = orig(es, cs)
+        torch.cuda.synchronize()
+        self._count("lincomb4")
+        terms = [(e, float(c)) for e, c in zip(snaps, cs) if e is not None]
+        tag = f"n={y.numel()} terms={len(terms)}"
+        self._inputs_unchanged("lincomb4 " + tag, [(f"e{i}", e, s) for i, (e, s) in enumerate(zip(es, snaps))])
+        if len(terms) == 2 and terms[0][1] == 1.0 and terms[1][1] == 1.0 and not _same(y, terms[0][0] + terms[1][0]):
+            self._fail(f"lincomb4 {tag}: e0 + e1 is not the fp32 sum bit for bit")
+        ref = sum(e.double() * c for e, c in terms)
+        c = y.shape[-1]
+        self._judge("lincomb4", tag, y.reshape(1, -1, c), ref.reshape(1, -1, c), BOUND_LINCOMB)
+        return y
+
+    def _conv_small_cout(self, orig, x, pw, pad=None, clamp=None):
+        xs, ws, bs = _snap(x), pw.w.clone(), _snap(pw.bias)
+        y = orig(x, pw, pad=pad, clamp=clamp)
+        torch.cuda.synchronize()
+        self._count("conv_small_cout")
+        n, h, w, cin = x.shape
+        ph, pw_ = (pw.kh // 2, pw.kw // 2) if pad is None else pad
+        taps = ws.reshape(pw.cout, pw.kh * pw.kw, cin)
+        dup = cin % 2 == 0 and torch.equal(taps[..., :cin // 2], taps[..., cin // 2:])
+        tag = f"n={n} h={h} w={w} cin={cin} cout={pw.cout} tap={pw.kh}x{pw.kw} clamp={int(clamp is not None)} dup={int(dup)}"
+        self._inputs_unchanged("conv_small_cout " + tag, [("x", x, xs), ("weight", pw.w, ws), ("bias", pw.bias, bs)])
+        op = dict(x=xs, x2=None, w=ws, bias=bs, kh=pw.kh, kw=pw.kw, stride=1, pad_h=ph, pad_w=pw_, upsample=False, hout=h, wout=w,
+                  cout=pw.cout, n_packed=pw.cout, groups=1, geglu=False, ln=False, ln_eps=0.0, scale=1.0, rowvec=None,
+                  rowvec_has_bias=False, residual=None, clamp=clamp)
+        ref = conv_small_cout_reference(op)
+        self._cpu_agree("conv_small_cout " + tag, conv_small_cout_reference, op, ref, n * h * w)
+        self._judge("conv_small_cout", tag, y.reshape(n, pw.cout, h * w).transpose(1, 2), ref, BOUND_SMALL_COUT,
+                    form=dict(dup=dup, kh=pw.kh, kw=pw.kw, clamp=clamp is not None))
+        return y
+
+    def _conv_small_cin(self, orig, srcs, weight, bias, kh, kw, pad, dtype, out_f32_nchw=False):
+        snaps = [_snap(s) for s in srcs]
+        y = orig(srcs, weight, bias, kh, kw, pad, dtype, out_f32_nchw=out_f32_nchw)
+        torch.cuda.synchronize()
+        self._count("conv_small_cin")
+        op = conv_small_cin_op(snaps, _snap(weight), _snap(bias), kh, kw, pad)
+        n, h, w = op["x"].shape[:3]
+        cout = weight.shape[0]
+        tag = f"n={n} h={h} w={w} cin={op['x'].shape[3]} cout={cout} tap={kh}x{kw} f32_nchw={int(out_f32_nchw)}"
+        self._inputs_unchanged("conv_small_cin " + tag, [(f"src{i}", s, t) for i, (s, t) in enumerate(zip(srcs, snaps))])
+        ref = igemm_reference(op)
+        self._cpu_agree("conv_small_cin " + tag, igemm_reference, op, ref, n * op["hout"] * op["wout"])
+        got = y.reshape(n, cout, -1).transpose(1, 2) if out_f32_nchw else y.reshape(n, -1, cout)
+        self._judge("conv_small_cin", tag, got, ref, BOUND_SMALL_CIN_F32 if out_f32_nchw else TOL[dtype])
+        return y
+
+    def _pack_sources(self, orig, srcs, dtype, c_pad=32):
+        snaps = [_snap(s) for s in srcs]
+        y = orig(srcs, dtype, c_pad)
+        torch.cuda.synchronize()
+        self._count("pack_sources")
+        cat = torch.cat(snaps, dim=1).permute(0, 2, 3, 1)
+        c = cat.shape[3]
+        tag = f"n={cat.shape[0]} hw={cat.shape[1] * cat.shape[2]} sources={len(srcs)} c={c} c_pad={c_pad}"
+        self._inputs_unchanged("pack_sources " + tag, [(f"src{i}", s, t) for i, (s, t) in enumerate(zip(srcs, snaps))])
+        if not (_same(y[..., :c], cat.to(dtype)) and not bool(y[..., c:].any())):
+            self._fail(f"pack_sources {tag}: not the rounded sources followed by zeros, bit for bit")
+        self.thin[y.data_ptr()] = len(srcs)
+        self._judge("pack_sources", tag, y.reshape(1, -1, c_pad), F.pad(cat, (0, c_pad - c)).reshape(1, -1, c_pad), TOL[dtype])
+        return y

@@ -297,6 +297,78 @@ def test_igemm_per_image_weights(ops, dtype):
     assert rel(p.float().view(n, t, t), torch.softmax(s.view(n, t, t).cpu(), dim=-1)) < TOL[dtype]
 
 
+def _softmax64(s):
+    """row softmax in fp64, spelled out (torch.softmax in fp64 on the device is off by ~5e-8 over 4,096 columns)"""
+    s = s.double()
+    e = torch.exp(s - s.amax(dim=-1, keepdim=True))
+    return e / e.sum(dim=-1, keepdim=True)
+
+
+@pytest.mark.parametrize("dtype", DT)
+@pytest.mark.parametrize("n,t,c", [(8, 4096, 512), (3, 1024, 512)])
+def test_igemm_per_image_weights_production_shape(ops, dtype, n, t, c):
+    """The VAE mid attention at the product's shapes (512 x 512 decode of 8 objects: T = 4,096, c = 512; an odd batch at 256 x 256):
+    S = q k^T / sqrt(c) (fp32 rows) and O = P v^T (storage type) with one weight matrix per image, each image against fp64 on
+    its own (a stride or image-index error for image >= 1 cannot hide in the batch's norm)."""
+    from mobi_amd._lib import OUT_ROWS_F32
+    qf, qd = rnd(f"pip.q.{n}.{t}", (n, t, 1, c), dtype)
+    kf, kd = rnd(f"pip.k.{n}.{t}", (n, t, c), dtype)
+    vf, vd = rnd(f"pip.v.{n}.{t}", (n, c, t), dtype)
+    s = ops.igemm(qd, ops.Packed(kd, None, 1, 1, c, t, t), weight_per_image=True, w_group_stride=t * c, out_mode=OUT_ROWS_F32,
+                  scale=c ** -0.5).view(n, t, t)
+    p = ops.softmax_rows(s.reshape(n * t, t), dtype).view(n, t, 1, t)
+    o = ops.igemm(p, ops.Packed(vd, None, 1, 1, t, c, c), weight_per_image=True, w_group_stride=c * t).view(n, t, c)
+    s_tol = 2e-5 * (100 if dtype == torch.bfloat16 else 1) + 1e-6
+    for i in range(n):
+        q64, k64, v64 = qf[i, :, 0].double().cuda(), kf[i].double().cuda(), vf[i].double().cuda()
+        ref_s = q64 @ k64.T * c ** -0.5
+        assert rel(s[i], ref_s) < s_tol, i
+        ref_o = p[i, :, 0].double() @ v64.T
+        assert rel(o[i], ref_o) < TOL[dtype], i
+
+
+@pytest.mark.parametrize("dtype", DT)
+@pytest.mark.parametrize("cols", [4096, 1024, 1000])
+def test_softmax_rows_wide(ops, dtype, cols):
+    """mobi_softmax_rows at the VAE attention's widths (4,096 / 1,024 keys) and a ragged one, against the fp64 softmax;
+    every row sums to 1 within the bound."""
+    rows = 300
+    s = (W.synth_input(f"smr.{cols}", (rows, cols)) * 4.0).cuda()
+    s[7] = 0.0                                                  # a flat row
+    s[11, 3] = 60.0                                             # a row with one dominant key
+    p = ops.softmax_rows(s.contiguous(), dtype)
+    ref = _softmax64(s)
+    assert p.dtype == dtype and rel(p, ref) < TOL[dtype]
+    assert float((p.double().sum(-1) - 1.0).abs().max()) < TOL[dtype]
+    worst_row = float(((p.double() - ref).norm(dim=-1) / ref.norm(dim=-1)).max())
+    assert worst_row < 4 * TOL[dtype], worst_row
+
+
+@pytest.mark.parametrize("dtype", DT)
+@pytest.mark.parametrize("kh,kw,cout", [(3, 3, 3), (1, 5, 2)])
+def test_conv_small_cout_packed_dup_production_shape(ops, dtype, kh, kw, cout):
+    """The decoders' output convolution as the precise routing runs it: a hi | lo pair of 128 channels (cin = 256) against
+    duplicated weights [W ; W], batch 8, width 512, 3 x 3 (camera) and 1 x 5 (range view) taps, clamped to [-1, 1]; against fp64
+    on the operands, each image on its own."""
+    n, h, w, c = 8, 12, 512, 128
+    y32 = (W.synth_input(f"cscd.{kh}{kw}.x", (n, h, w, c)) * 1.3).cuda()
+    hi = y32.to(dtype)
+    lo = (y32 - hi.float()).to(dtype)
+    x = torch.cat([hi, lo], dim=-1).contiguous()
+    wt = torch.from_numpy(W.synth_param(f"cscd.{kh}{kw}.weight", (cout, c, kh, kw))) * 0.7
+    bias = torch.from_numpy(W.synth_param(f"cscd.{kh}{kw}.bias", (cout,)))
+    pw = ops.pack_conv(torch.cat([wt, wt], dim=1), bias, dtype, "cuda")
+    y = ops.conv_small_cout(x, pw, pad=(kh // 2, kw // 2), clamp=(-1.0, 1.0))
+    w64 = wt.to(dtype).double().cuda()
+    with torch.backends.cudnn.flags(enabled=False):
+        ref = F.conv2d((hi.double() + lo.double()).permute(0, 3, 1, 2), w64, bias.double().cuda(),
+                       padding=(kh // 2, kw // 2)).clamp(-1.0, 1.0)
+    assert 0.01 < float((ref.abs() == 1.0).double().mean()) < 0.5        # the clamp is exercised, not everywhere
+    assert y.shape == ref.shape
+    for i in range(n):
+        assert rel(y[i], ref[i]) < 2e-5, i
+
+
 # ---------------------------------------------------------------------------------------------
 ATTN_CASES = [(8, 8, 64, 64), (8, 16, 100, 100), (8, 40, 256, 256), (8, 80, 64, 64), (8, 160, 64, 64),
               (4, 32, 1, 1), (8, 8, 4, 4), (8, 40, 4096, 4096), (2, 64, 70, 130), (8, 24, 16, 16)]

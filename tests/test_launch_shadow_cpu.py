@@ -250,3 +250,139 @@ def test_outside_view_write_is_caught(dtype):
     ov2 = ls.OutsideView(base2[::2])
     base2[1, 0] = float("nan")                                  # the partner image's first row
     assert not ov2.unchanged()
+
+
+# ---- the VAEs' entry points -------------------------------------------------------------------------------------------
+def _per_image_op(x, w, n, npk, k, stride, scale=1.0):
+    return dict(x=x, x2=None, w=ls.per_image_weights(w, n, npk, k, stride), bias=None, kh=1, kw=1, stride=1, pad_h=0, pad_w=0,
+                upsample=False, hout=x.shape[1], wout=1, cout=npk, n_packed=npk, groups=n, geglu=False, ln=False, ln_eps=0.0,
+                scale=scale, rowvec=None, rowvec_has_bias=False, residual=None)
+
+
+def test_per_image_weight_reference_is_einsum():
+    """S = q k^T * scale with the keys as per-image weights, and O = P v from the transposed v, against fp64 einsum; image i
+    multiplies slab i of the tensor's own shape."""
+    n, t, c = 3, 40, 16
+    q, k, vt = _rand((n, t, 1, c), 60), _rand((n, t, c), 61), _rand((n, c, t), 62)
+    s = ls.igemm_reference(_per_image_op(q, k, n, t, c, t * c, scale=c ** -0.5))
+    want_s = torch.einsum("ntc,nsc->nts", q[:, :, 0], k) * c ** -0.5
+    assert torch.allclose(s, want_s, rtol=1e-12, atol=1e-12)
+    p = torch.softmax(want_s, dim=-1)
+    o = ls.igemm_reference(_per_image_op(p.unsqueeze(2), vt, n, c, t, c * t))
+    assert torch.allclose(o, torch.einsum("nts,ncs->ntc", p, vt), rtol=1e-12, atol=1e-12)
+    rows = torch.tensor([0, t - 1, t, 2 * t + 5, 3 * t - 1])
+    sub = ls.igemm_reference(_per_image_op(q, k, n, t, c, t * c, scale=c ** -0.5), rows=rows)
+    assert torch.allclose(sub, want_s.reshape(n * t, t)[rows], rtol=1e-12, atol=1e-12)
+
+
+def test_per_image_weights_reject_a_disagreeing_stride():
+    n, t, c = 3, 8, 16
+    k = _rand((n, t, c), 63)
+    assert ls.per_image_weights(k, n, t, c, t * c).shape == (n, t, c)
+    for bad in (0, c, 2 * t * c):                               # every image reading image 0's keys; a row stride; past the end
+        with pytest.raises(ValueError, match="w_group_stride"):
+            ls.per_image_weights(k, n, t, c, bad)
+    with pytest.raises(ValueError):
+        ls.per_image_weights(k[:, :, :8], n, t, c, t * c)       # not the tensor's own slabs
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_metric_fails_image_read_with_image_0_weights(dtype):
+    """The fp32 scores of a batch where image 1 multiplied image 0's keys (w_group_stride 0): whole rel-L2 and tiles fail."""
+    n, t, c = 3, 256, 64
+    q, k = _rand((n, t, c), 64).to(dtype).double(), _rand((n, t, c), 65).to(dtype).double()
+    ref = torch.einsum("ntc,nsc->nts", q, k) * c ** -0.5
+    got = ref.float().clone()
+    got[1] = (q[1] @ k[0].T * c ** -0.5).float()
+    assert ls.passes(ls.compare(ref.float(), ref), ls.bound_f32_rows(dtype))
+    res = ls.compare(got, ref)
+    assert not ls.passes(res, ls.bound_f32_rows(dtype)) and res["where"][0] == 1, res
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_split_check(dtype):
+    x = _rand((2, 5, 7, 64), 66).float() * 3.0
+    hi = x.to(dtype)
+    lo = (x - hi.float()).to(dtype)
+    assert ls.check_split(x, torch.cat([hi, lo], -1), 2, dtype) == []
+    assert ls.check_split(x, torch.cat([hi, lo, hi], -1), 3, dtype) == []
+    assert any("third part" in m for m in ls.check_split(x, torch.cat([hi, lo, lo], -1), 3, dtype))
+    assert any("hi + lo" in m for m in ls.check_split(x, torch.cat([hi, torch.zeros_like(lo)], -1), 2, dtype))
+    bumped = hi.clone()
+    bumped[1, 2, 3, 4] = bumped[1, 2, 3, 4] * 2
+    assert any("hi is not" in m for m in ls.check_split(x, torch.cat([bumped, lo], -1), 2, dtype))
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_trunk_add_check(dtype):
+    trunk, inc = _rand((2, 4, 4, 64), 67).float(), _rand((2, 4, 4, 64), 68).to(dtype)
+    after = trunk + inc.float()
+    assert ls.check_trunk_add(trunk, inc, after, after.to(dtype), dtype) == []
+    assert ls.check_trunk_add(trunk, None, trunk.clone(), trunk.to(dtype), dtype) == []
+    assert ls.check_trunk_add(trunk, inc, trunk.clone(), trunk.to(dtype), dtype)                   # the update was lost
+    assert ls.check_trunk_add(trunk, inc, after, trunk.to(dtype), dtype)                           # copy of the old trunk
+    assert ls.check_trunk_add(trunk, None, after, after.to(dtype), dtype)                          # trunk written with no inc
+
+
+def test_softmax_reference_and_row_sums():
+    s = _rand((70, 1000), 69) * 5.0
+    s[3] = 0.0
+    ref = ls.softmax_reference(dict(s=s))
+    assert torch.allclose(ref, torch.softmax(s, dim=-1), rtol=1e-13, atol=1e-16)
+    rows = torch.tensor([0, 3, 69])
+    assert torch.equal(ls.softmax_reference(dict(s=s), rows=rows), ref[rows])
+    assert ls.softmax_row_sums(ref) < 1e-12
+    for dtype in DT:
+        got = ref.to(dtype)
+        assert ls.softmax_row_sums(got) < TOL[dtype] and ls.passes(ls.compare(got[None], ref[None]), TOL[dtype])
+        bad = got.clone()
+        bad[17] = (bad[17].double() * 1.01).to(dtype)                  # one row that sums to 1.01
+        assert ls.softmax_row_sums(bad) > TOL[dtype]
+
+
+@pytest.mark.parametrize("k,clamp", [((3, 3), (-0.5, 0.5)), ((1, 5), None)])
+def test_conv_small_cout_reference_is_conv2d(k, clamp):
+    kh, kw = k
+    x, w, b = _rand((2, 64, 6, 20), 70), _rand((3, 64, kh, kw), 71, 0.1), _rand((3,), 72)
+    op = _op(_nhwc(x), w, bias=b)
+    op["clamp"] = clamp
+    want = F.conv2d(x, w, b, padding=(kh // 2, kw // 2))
+    if clamp:
+        want = want.clamp(*clamp)
+    got = ls.conv_small_cout_reference(op)
+    assert torch.allclose(got, _flat(_nhwc(want)), rtol=1e-12, atol=1e-12)
+
+
+def test_conv_small_cin_op_is_conv2d():
+    """The OIHW-flattened fp32 weight and the NCHW sources of conv_small_cin, through the igemm reference."""
+    a, z = _rand((2, 3, 5, 9), 73), _rand((2, 1, 5, 9), 74)
+    w, b = _rand((6, 4, 1, 5), 75, 0.2), _rand((6,), 76)
+    op = ls.conv_small_cin_op([a, z], w.reshape(6, -1), b, 1, 5, (0, 2))
+    got = ls.igemm_reference(op)
+    assert torch.allclose(got, _flat(_nhwc(F.conv2d(torch.cat([a, z], 1), w, b, padding=(0, 2)))), rtol=1e-12, atol=1e-12)
+    op = ls.conv_small_cin_op([z], _rand((8, 1, 1, 1), 77).reshape(8, -1), None, 1, 1, (0, 0))
+    assert torch.allclose(ls.igemm_reference(op), _flat(z.permute(0, 2, 3, 1)) * op["w"].reshape(1, 1, 8), rtol=1e-12)
+
+
+def test_census_reports_an_unshadowed_launch():
+    """A launch the shadow did not judge, or an entry point that is neither shadowed nor query-only, is a census failure."""
+    class Lib:
+        def __getattr__(self, name):
+            return lambda *a: 0
+
+    class Shadow(ls.LaunchShadow):
+        def __init__(self):
+            self.calls, self.counts = {}, {}
+
+    sh = Shadow()
+    lib = ls.LibCensus(Lib(), sh.calls)
+    lib.mobi_igemm_plan_splits(None)
+    lib.mobi_igemm_workspace_bytes(None, 2)
+    lib.mobi_tile_weights(None)
+    lib.mobi_igemm(None)
+    sh.counts["igemm"] = 1
+    assert sh.census_failures() == []
+    lib.mobi_igemm(None)
+    lib.mobi_nearest_resize(None)
+    bad = sh.census_failures()
+    assert any(m.startswith("mobi_igemm:") for m in bad) and any(m.startswith("mobi_nearest_resize:") for m in bad), bad
