@@ -668,7 +668,8 @@ int mobi_q_sample(const float* x0, const float* noise, const int64_t* t, const f
  *            iff x nx + y ny + z nz + d < 0 for all six surfaces; planes = f32 [batch][6][4] = (nx, ny, nz, d), computed
  *            on the host from the 8 corners as surface_equ_3d does, :712-732)
  *   final = where(pred_mask | gt_mask, un-cropped sample, original)
- * sample_int / int_orig / int_unc / int_final may all be NULL (depth only); any output may be NULL. */
+ * sample_int / int_orig / int_unc / int_final may all be NULL (depth only); any output may be NULL.
+ * width_crop[b] should divide wc; one wider than the sample or the sweep is clamped to them, one <= 0 pastes nothing. */
 typedef struct mobi_range_paste_params {
   const float* sample_depth; const float* sample_int;       /* [batch][hc][wc] */
   const float* depth_orig; const float* int_orig;           /* [batch][h0][w0] */
@@ -688,7 +689,9 @@ int mobi_range_paste(const mobi_range_paste_params* p, void* stream);
  * (pool_resize, lidar_converter.py:8-19); over the cells whose pooled mask == 1,
  *   out[b][region][0] = sqrt(mean((pred - gt)^2)),  [1] = lower median of |pred - gt| (torch.median),  [2] = cell count
  * region 0 = instance mask, 1 = box mask; an empty region gives NaN scores (the reference drops / propagates NaN).
- * pred / gt / inst_mask / box_mask: f32 [batch][h][w]; max_width = max over b of width_crop[b] (sizes the sort space). */
+ * pred / gt / inst_mask / box_mask: f32 [batch][h][w]; max_width = max over b of width_crop[b] (sizes the sort space;
+ * <= w, and pool_h * max_width <= 16384).  width_crop[b] should divide w (the reference's avg_pool2d kernel is w / width_crop[b]);
+ * a width_crop[b] > max_width is clamped to max_width, one <= 0 gives the empty-region row (NaN, NaN, 0). */
 typedef struct mobi_lidar_metrics_params {
   const float* pred; const float* gt; const float* inst_mask; const float* box_mask;
   const int32_t* width_crop;

@@ -36,7 +36,11 @@ __global__ void range_paste_kernel(const mobi_range_paste_params a) {
     const int y = p / a.w0, x = p - y * a.w0;
     // LidarConverter.undo_default_transforms (lidar_converter.py:436-485): the crop window [crop_left, crop_left + wc)
     // wraps around the sweep; inside it the sample is avg-pooled from (hc, wc_in) to (h0, wc)
-    const int wc = a.width_crop[b];
+    // (the wrappers validate host-resident windows; a device-resident one is clamped to what the sample and the sweep
+    // hold, and an empty one pastes nothing, rather than dividing by it)
+    int wc = a.width_crop[b];
+    wc = wc > a.wc ? a.wc : wc;
+    wc = wc > a.w0 ? a.w0 : wc;
     int cl = a.crop_left[b] % a.w0;
     if (cl < 0) cl += a.w0;                                   // Python's % is non-negative
     int rel = x - cl;
@@ -80,9 +84,12 @@ __global__ __launch_bounds__(1024) void lidar_metrics_kernel(const mobi_lidar_me
   __shared__ unsigned n_vals;
   __shared__ double red[1024];
   const int b = blockIdx.x, region = blockIdx.y, tid = threadIdx.x;
-  const int wc = a.width_crop[b];
-  const int kh = a.h / a.pool_h, kw = a.w / wc;
-  const int cells = a.pool_h * wc;
+  // (a device-resident window the wrapper could not validate: clamped to the sort space the launch was sized for;
+  // an empty one selects no cell -> NaN, NaN, 0)
+  int wc = a.width_crop[b];
+  wc = wc > a.max_width ? a.max_width : wc;
+  const int kh = a.h / a.pool_h, kw = wc > 0 ? a.w / wc : 1;
+  const int cells = wc > 0 ? a.pool_h * wc : 0;
   const float* pred = a.pred + (long long)b * a.h * a.w;
   const float* gt = a.gt + (long long)b * a.h * a.w;
   const float* msk = (region == 0 ? a.inst_mask : a.box_mask) + (long long)b * a.h * a.w;
@@ -369,6 +376,7 @@ extern "C" int mobi_range_paste(const mobi_range_paste_params* p, void* stream) 
 extern "C" int mobi_lidar_metrics(const mobi_lidar_metrics_params* p, void* stream) {
   if (!p || !p->pred || !p->gt || !p->inst_mask || !p->box_mask || !p->width_crop || !p->out) return MOBI_ERR_ARG;
   if (p->batch <= 0 || p->h <= 0 || p->w <= 0 || p->pool_h <= 0 || p->h % p->pool_h || p->max_width <= 0) return MOBI_ERR_ARG;
+  if (p->max_width > p->w) return MOBI_ERR_ARG;                                      // a window wider than the view
   if ((long long)p->pool_h * p->max_width > 16384) return MOBI_ERR_UNSUPPORTED;      // the sort space in LDS
   hipLaunchKernelGGL(lidar_metrics_kernel, dim3(p->batch, 2), dim3(1024), 0, ST(stream), *p);
   MOBI_CHECK_LAUNCH();

@@ -1248,6 +1248,19 @@ def _i32(t, device):
     return torch.as_tensor(t).to(device=device, dtype=torch.int32).reshape(-1).contiguous()
 
 
+def _check_windows(name, width_crop, width, *more):
+    """Host-resident crop windows must be what the reference's pool_resize can produce: 0 < wc <= width, width % wc == 0
+    (F.avg_pool2d with kernel width // wc yields wc columns only then).  Device-resident windows are not read back: the
+    kernels clamp them."""
+    wc = torch.as_tensor(width_crop)
+    if wc.is_cuda or wc.numel() == 0:
+        return None
+    wc = wc.reshape(-1).to(torch.int64)
+    if bool(((wc <= 0) | (wc > min((width,) + more)) | (width % wc.clamp_min(1) != 0)).any()):
+        raise ValueError(f"{name}: crop windows must be 1 ... {min((width,) + more)} columns wide and divide {width}")
+    return int(wc.max())
+
+
 def range_paste(sample_depth, depth_orig, crop_left, width_crop, sample_int=None, int_orig=None, pitch=None, yaw=None,
                 planes=None, gt_mask=None, depth_interval=(1.4, 54.0)):
     """sample_*: fp32 [B, Hc, Wc] (de-normalised range sample), *_orig: fp32 [B, H0, W0]; crop_left / width_crop: [B] ints.
@@ -1256,6 +1269,7 @@ def range_paste(sample_depth, depth_orig, crop_left, width_crop, sample_int=None
     dev = sample_depth.device
     b, hc, wc = sample_depth.shape
     _, h0, w0 = depth_orig.shape
+    _check_windows("range_paste", width_crop, wc, w0)
     f = lambda t: None if t is None else _dev(t).to(torch.float32).contiguous()
     sample_depth, sample_int, depth_orig, int_orig, pitch, yaw, planes = map(
         f, (sample_depth, sample_int, depth_orig, int_orig, pitch, yaw, planes))
@@ -1366,13 +1380,15 @@ def lidar_metrics(pred, gt, inst_mask, box_mask, width_crop, pool_h=32):
     lib = _lib.load()
     dev = pred.device
     b, h, w = pred.shape
+    widest = _check_windows("lidar_metrics", width_crop, w)
     f = lambda t: _dev(t).to(torch.float32).reshape(b, h, w).contiguous()
     pred, gt, inst_mask, box_mask = map(f, (pred, gt, inst_mask, box_mask))
     wcr = _i32(width_crop, dev)
     out = torch.empty((b, 2, 3), device=dev, dtype=torch.float32)
     p = _lib.LidarMetricsParams()
     p.pred, p.gt, p.inst_mask, p.box_mask, p.width_crop, p.out = _ptr(pred), _ptr(gt), _ptr(inst_mask), _ptr(box_mask), _ptr(wcr), _ptr(out)
-    p.batch, p.h, p.w, p.pool_h, p.max_width = b, h, w, pool_h, w       # width_crop <= w: sort space for the widest case
+    # the sort space is sized for the widest window: the batch's own when it is known on the host, else the view's
+    p.batch, p.h, p.w, p.pool_h, p.max_width = b, h, w, pool_h, (widest or w)
     _lib.check(lib.mobi_lidar_metrics(C.byref(p), _stream()), "mobi_lidar_metrics")
     return out
 
