@@ -48,7 +48,9 @@ extern "C" {
  *      GroupNorm that consumes them instead of by a reduce launch of their own; later, without a layout change (an
  *      addition only), mobi_dpm_step and its mobi_dpm_step_params (struct id 20); likewise the realism metrics' kernels
  *      mobi_maxpool3s2, mobi_lpips_distance + mobi_lpips_distance_ws_floats (mobi_lpips_distance_params, struct id 21),
- *      mobi_image_normalize (mobi_image_normalize_params, struct id 22) and mobi_row_cosine */
+ *      mobi_image_normalize (mobi_image_normalize_params, struct id 22) and mobi_row_cosine; likewise the multi-tensor
+ *      passes mobi_grad_stats / mobi_adamw_multi + mobi_multi_tensor_workspace_bytes (mobi_mt_tensor 23, mobi_mt_chunk 24,
+ *      mobi_grad_stats_record 25) */
 #define MOBI_ABI_VERSION 6
 
 enum { MOBI_OK = 0, MOBI_ERR_ARG = -1, MOBI_ERR_UNSUPPORTED = -2, MOBI_ERR_LAUNCH = -3, MOBI_ERR_ALIGN = -4 };
@@ -61,7 +63,7 @@ const char* mobi_error_string(int code);
  * 3 attention, 4 ctx_attention, 5 skinny_linear, 6 conv_small_cin, 7 conv_small_cout,
  * 8 ddim_step, 9 two_key_adapter, 10 range_paste, 11 lidar_metrics, 12 range_prepare, 13 image_prepare, 14 ff_geglu,
  * 15 row_chain, 16 chain_op, 17 layernorm_bwd, 18 attention_bwd, 19 split_source, 20 dpm_step, 21 lpips_distance,
- * 22 image_normalize.  Returns 0 for an unknown id. */
+ * 22 image_normalize, 23 mt_tensor, 24 mt_chunk, 25 grad_stats_record.  Returns 0 for an unknown id. */
 size_t mobi_struct_size(int id);
 /* Development hook: the library reads its MOBI_* A/B environment variables once, at the first launch
  * (mobi_amd/csrc/tuning.h lists them); this re-reads them.  Not needed by a product caller. */
@@ -443,6 +445,31 @@ int mobi_silu_bwd_f32(const float* z, const float* dy, float* dx, int64_t n, voi
  * decay, bias-corrected moments; step counts from 1. */
 int mobi_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
                     float beta2, float eps, float weight_decay, int32_t step, void* stream);
+
+/* Multi-tensor passes (the fp16 training step's gradient statistics and optimizer update: one launch over EVERY listed tensor
+ * instead of one per tensor).  Both walk a DEVICE-resident table of tensors through a DEVICE-resident chunk map: every tensor is
+ * cut into chunks of `chunk_elems` elements (mobi_multi_tensor_workspace_bytes reports it; the last chunk of a tensor is
+ * shorter), chunk k = {offset = k * chunk_elems, tensor}, in any order.  Tensors are dense fp32 at any 4-byte boundary; entries
+ * that do not lie inside their tensor are skipped.  Additions to ABI 6 (struct ids 23, 24, 25). */
+typedef struct mobi_mt_tensor {
+  float* param; const float* grad; float* exp_avg; float* exp_avg_sq;    /* mobi_grad_stats reads `grad` and `n` only */
+  int64_t n;
+} mobi_mt_tensor;
+typedef struct mobi_mt_chunk { int64_t offset; int32_t tensor; int32_t reserved; } mobi_mt_chunk;
+typedef struct mobi_grad_stats_record { double sumsq; int32_t nonfinite; int32_t reserved; } mobi_grad_stats_record;
+/* Bytes of the workspace mobi_grad_stats needs (per-block fp64 partials; independent of the list); *chunk_elems (may be
+ * NULL) receives the chunk length the map must be cut to. */
+size_t mobi_multi_tensor_workspace_bytes(int32_t* chunk_elems);
+/* out (device) <- {sum over all listed gradients of g^2, 1 if any g is inf or nan else 0}.  Squares and sums are fp64 from the
+ * first add (a finite fp32 value's square cannot overflow), in a fixed order without atomics: per-block partials in `workspace`,
+ * summed in ascending order by a one-block finish pass -- bit-reproducible run to run on one device. */
+int mobi_grad_stats(const mobi_mt_tensor* tensors, int32_t n_tensors, const mobi_mt_chunk* chunks, int32_t n_chunks,
+                    void* workspace, mobi_grad_stats_record* out, void* stream);
+/* mobi_adamw_step of every listed tensor on grad * grad_mul (1 / loss scale times the clip coefficient).  The same fp32
+ * operations per element as mobi_adamw_step: with grad_mul == 1 the results are bit-identical to the per-tensor launches. */
+int mobi_adamw_multi(const mobi_mt_tensor* tensors, int32_t n_tensors, const mobi_mt_chunk* chunks, int32_t n_chunks,
+                     float grad_mul, float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step, void* stream);
+
 typedef struct mobi_attention_bwd_params {
   const void* q; int64_t q_img_stride, q_row_stride;       /* T [image][tq][>= heads*dh], strides in elements */
   const void* k; int64_t k_img_stride, k_row_stride;       /* T [image][tk][..] */

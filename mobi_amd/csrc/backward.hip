@@ -7,6 +7,7 @@
 // un-fused projection, attention backward (log-sum-exp and row dots, dQ, dK | dV) for any head dim <= 160 and any token
 // counts (self / cross-modal attention; two context tokens for the bbox adapter), column sums (bias gradients), a 16-bit
 // transpose, the reduction of per-block partials (fixed order: bit-reproducible).
+#include "adamw.h"
 #include "common.h"
 #include "tuning.h"
 
@@ -998,13 +999,10 @@ __global__ __launch_bounds__(256) void silu_bwd_f32_kernel(const float* __restri
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                     long long n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const float gi = g[i];
-    float pi = p[i] * (1.0f - lr * wd);
-    const float mi = b1 * m[i] + (1.0f - b1) * gi;
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+    float pi = p[i], mi = m[i], vi = v[i];
+    adamw_update(pi, g[i], mi, vi, lr, b1, b2, eps, wd, bc1, bc2_sqrt);      // (adamw.h: shared with mobi_adamw_multi)
     m[i] = mi;
     v[i] = vi;
-    pi -= (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
     p[i] = pi;
   }
 }

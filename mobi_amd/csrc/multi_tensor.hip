@@ -1,0 +1,197 @@
+// Multi-tensor passes of the fp16 training step (include/mobi_engine.h, "Multi-tensor passes"; mobi_amd/train.py GradScaler /
+// AdamW.step_scaled): the gradient statistics (sum of squares + non-finite flag) and the AdamW update of EVERY listed tensor in one
+// launch each, instead of one launch per tensor (432 adapter tensors + the conditioning stage's: ~880 launches of a few hundred KB
+// to a few MB each).  Both kernels walk a device-resident table of tensors through a device-resident chunk map: every tensor is cut
+// into chunks of kMtChunk elements, one 256-thread block takes chunks in a grid-stride walk, the grid follows the CU count.  Pure
+// streaming: 16-byte accesses on the 16-byte-aligned body of a chunk, 4-byte accesses on its head and tail (a tensor may start at
+// any 4-byte boundary); no atomics, LDS only for the block reduction of the statistics.
+#include "adamw.h"
+#include "common.h"
+
+namespace mobi {
+
+constexpr int kMtChunk = 8192;        // elements per chunk (a multiple of 4: every chunk of a tensor has the tensor's alignment phase)
+constexpr int kMtBlock = 256;
+constexpr int kMtMaxBlocks = 2048;    // the workspace holds one fp64 partial per block
+constexpr int kMtBlocksPerCu = 4;
+
+// elements in front of the next 16-byte boundary (0 .. 3; the pointer is 4-byte aligned)
+__device__ __forceinline__ int mt_phase(const void* p) { return (int)((16u - (unsigned)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) >> 2; }
+
+// chunk c of the map -> (tensor entry, element offset, length); false for an entry that does not lie inside its tensor (a map that
+// does not belong to the table must never turn into an out-of-bounds access)
+__device__ __forceinline__ bool mt_chunk(const mobi_mt_tensor* __restrict__ tensors, int n_tensors, const mobi_mt_chunk* __restrict__ chunks,
+                                         int c, mobi_mt_tensor& t, long long& off, int& len) {
+  const mobi_mt_chunk ch = chunks[c];
+  if (ch.tensor < 0 || ch.tensor >= n_tensors) return false;
+  t = tensors[ch.tensor];
+  off = ch.offset;
+  if (off < 0 || off >= t.n) return false;
+  const long long left = t.n - off;
+  len = left < kMtChunk ? (int)left : kMtChunk;
+  return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Gradient statistics.  Squares and sums in fp64 from the first add upward: the square of a finite fp32 value (up to 1.2e77) is
+// exact in fp64 and a sum of them cannot overflow, so the sum is non-finite exactly when some gradient is inf or nan -- the flag
+// is read off the sum, no per-element test.  Fixed order: a thread adds its elements in ascending order into four accumulators
+// (one per lane of the 16-byte access), lanes and waves are combined by a fixed tree, every block writes one partial and the
+// finish pass adds the partials in ascending block order.  Bit-reproducible for a given grid (= for a given device).
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kMtBlock) void grad_stats_kernel(const mobi_mt_tensor* __restrict__ tensors, int n_tensors,
+                                                              const mobi_mt_chunk* __restrict__ chunks, int n_chunks,
+                                                              double* __restrict__ partial) {
+  __shared__ double wave_part[kMtBlock / 64];
+  const int tid = threadIdx.x;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+  for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+    mobi_mt_tensor t;
+    long long off;
+    int len;
+    if (!mt_chunk(tensors, n_tensors, chunks, c, t, off, len)) continue;
+    const float* __restrict__ g = t.grad + off;
+    const int ph = mt_phase(g), head = ph < len ? ph : len;
+    const int nvec = (len - head) >> 2, tail0 = head + (nvec << 2);
+    if (tid < head) {
+      const double x = (double)g[tid];
+      a0 = fma(x, x, a0);
+    }
+    if (tid < len - tail0) {
+      const double x = (double)g[tail0 + tid];
+      a1 = fma(x, x, a1);
+    }
+    const f32x4* __restrict__ gv = reinterpret_cast<const f32x4*>(g + head);
+#pragma unroll 4
+    for (int i = tid; i < nvec; i += kMtBlock) {
+      const f32x4 x = gv[i];
+      const double x0 = (double)x[0], x1 = (double)x[1], x2 = (double)x[2], x3 = (double)x[3];
+      a0 = fma(x0, x0, a0);
+      a1 = fma(x1, x1, a1);
+      a2 = fma(x2, x2, a2);
+      a3 = fma(x3, x3, a3);
+    }
+  }
+  double s = (a0 + a1) + (a2 + a3);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((tid & 63) == 0) wave_part[tid >> 6] = s;
+  __syncthreads();
+  if (tid == 0) partial[blockIdx.x] = (wave_part[0] + wave_part[1]) + (wave_part[2] + wave_part[3]);
+}
+
+__global__ __launch_bounds__(kMtBlock) void grad_stats_finish_kernel(const double* __restrict__ partial, int blocks,
+                                                                     mobi_grad_stats_record* __restrict__ out) {
+  __shared__ double part[kMtMaxBlocks];
+  for (int i = threadIdx.x; i < blocks; i += kMtBlock) part[i] = partial[i];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int i = 0; i < blocks; ++i) s += part[i];
+    out->sumsq = s;
+    out->nonfinite = ((__double_as_longlong(s) >> 52) & 0x7ff) == 0x7ff ? 1 : 0;      // exponent all ones: inf or nan
+    out->reserved = 0;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// AdamW over the whole list: g * grad_mul (1 / loss scale times the clip coefficient), then the update of adamw.h.  The 16-byte
+// path needs param, grad and both moments at the same alignment phase; a tensor whose four pointers disagree takes the 4-byte
+// path for all of its elements.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kMtBlock) void adamw_multi_kernel(const mobi_mt_tensor* __restrict__ tensors, int n_tensors,
+                                                               const mobi_mt_chunk* __restrict__ chunks, int n_chunks, float grad_mul,
+                                                               float lr, float b1, float b2, float eps, float wd, float bc1,
+                                                               float bc2_sqrt) {
+  const int tid = threadIdx.x;
+  for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+    mobi_mt_tensor t;
+    long long off;
+    int len;
+    if (!mt_chunk(tensors, n_tensors, chunks, c, t, off, len)) continue;
+    float* __restrict__ p = t.param + off;
+    const float* __restrict__ g = t.grad + off;
+    float* __restrict__ m = t.exp_avg + off;
+    float* __restrict__ v = t.exp_avg_sq + off;
+    const int ph = mt_phase(g);
+    const bool same = ph == mt_phase(p) && ph == mt_phase(m) && ph == mt_phase(v);
+    const int head = same && ph < len ? ph : len;
+    const int nvec = (len - head) >> 2, tail0 = head + (nvec << 2);
+    // head [0, head) and tail [tail0, len): at most 3 elements each, or the whole chunk where the pointers disagree
+    auto one = [&](int i) {
+      float pi = p[i], mi = m[i], vi = v[i];
+      adamw_update(pi, g[i] * grad_mul, mi, vi, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+      m[i] = mi;
+      v[i] = vi;
+      p[i] = pi;
+    };
+    for (int i = tid; i < head; i += kMtBlock) one(i);
+    for (int i = tail0 + tid; i < len; i += kMtBlock) one(i);
+    f32x4* __restrict__ pv = reinterpret_cast<f32x4*>(p + head);
+    const f32x4* __restrict__ gv = reinterpret_cast<const f32x4*>(g + head);
+    f32x4* __restrict__ mv = reinterpret_cast<f32x4*>(m + head);
+    f32x4* __restrict__ vv = reinterpret_cast<f32x4*>(v + head);
+#pragma unroll 2
+    for (int i = tid; i < nvec; i += kMtBlock) {
+      f32x4 pq = pv[i], mq = mv[i], vq = vv[i];
+      const f32x4 gq = gv[i];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float pi = pq[j], mi = mq[j], vi = vq[j];
+        adamw_update(pi, gq[j] * grad_mul, mi, vi, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+        pq[j] = pi;
+        mq[j] = mi;
+        vq[j] = vi;
+      }
+      mv[i] = mq;
+      vv[i] = vq;
+      pv[i] = pq;
+    }
+  }
+}
+
+static int mt_grid(int n_chunks) {
+  static int cus = 0;
+  if (!cus) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cus = n;
+  }
+  int g = cus * kMtBlocksPerCu;
+  if (g > kMtMaxBlocks) g = kMtMaxBlocks;
+  return n_chunks < g ? n_chunks : g;
+}
+
+}  // namespace mobi
+
+using namespace mobi;
+#define ST(stream) reinterpret_cast<hipStream_t>(stream)
+
+extern "C" size_t mobi_multi_tensor_workspace_bytes(int32_t* chunk_elems) {
+  if (chunk_elems) *chunk_elems = kMtChunk;
+  return (size_t)kMtMaxBlocks * sizeof(double);
+}
+
+extern "C" int mobi_grad_stats(const mobi_mt_tensor* tensors, int32_t n_tensors, const mobi_mt_chunk* chunks, int32_t n_chunks,
+                               void* workspace, mobi_grad_stats_record* out, void* stream) {
+  if (!tensors || !chunks || !workspace || !out || n_tensors <= 0 || n_chunks <= 0) return MOBI_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(workspace) & 7) || (reinterpret_cast<uintptr_t>(out) & 7)) return MOBI_ERR_ALIGN;
+  const int blocks = mt_grid(n_chunks);
+  hipLaunchKernelGGL(grad_stats_kernel, dim3(blocks), dim3(kMtBlock), 0, ST(stream), tensors, n_tensors, chunks, n_chunks,
+                     static_cast<double*>(workspace));
+  MOBI_CHECK_LAUNCH();
+  hipLaunchKernelGGL(grad_stats_finish_kernel, dim3(1), dim3(kMtBlock), 0, ST(stream), static_cast<const double*>(workspace), blocks, out);
+  MOBI_CHECK_LAUNCH();
+  return MOBI_OK;
+}
+
+extern "C" int mobi_adamw_multi(const mobi_mt_tensor* tensors, int32_t n_tensors, const mobi_mt_chunk* chunks, int32_t n_chunks,
+                                float grad_mul, float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step,
+                                void* stream) {
+  if (!tensors || !chunks || n_tensors <= 0 || n_chunks <= 0 || step <= 0) return MOBI_ERR_ARG;
+  const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
+  hipLaunchKernelGGL(adamw_multi_kernel, dim3(mt_grid(n_chunks)), dim3(kMtBlock), 0, ST(stream), tensors, n_tensors, chunks, n_chunks,
+                     grad_mul, lr, beta1, beta2, eps, weight_decay, bc1, sqrtf(bc2));
+  MOBI_CHECK_LAUNCH();
+  return MOBI_OK;
+}

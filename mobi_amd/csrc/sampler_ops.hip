@@ -271,6 +271,9 @@ extern "C" size_t mobi_struct_size(int id) {
     case 20: return sizeof(mobi_dpm_step_params);
     case 21: return sizeof(mobi_lpips_distance_params);
     case 22: return sizeof(mobi_image_normalize_params);
+    case 23: return sizeof(mobi_mt_tensor);
+    case 24: return sizeof(mobi_mt_chunk);
+    case 25: return sizeof(mobi_grad_stats_record);
     default: return 0;
   }
 }

@@ -13,7 +13,6 @@ from contextlib import contextmanager
 from functools import partial
 
 import numpy as np
-import math
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -390,7 +389,7 @@ class LatentDiffusion(DDPM):
         return {**loss_dict, **{k + "_ema": v for k, v in loss_dict_ema.items()}}
 
     @torch.no_grad()
-    def training_step(self, batch, batch_idx=0, t=None, noise=None, loss_scale=None, allreduce=True):
+    def training_step(self, batch, batch_idx=0, t=None, noise=None, loss_scale=None, allreduce=True, scaler=None):
         """ddpm.py:356-370 of the reference + what Lightning does around it (autograd backward, DDP's gradient all-reduce,
         main.py:510): returns the loss and leaves `self.adapter_grads` = {`model.diffusion_model.<name>`: fp32 gradient} for
         every UNet tensor the reference's optimizer filter selects (ddpm.py:1616-1629: `cond_adapter*`, `cross_modal*` --
@@ -398,7 +397,15 @@ class LatentDiffusion(DDPM):
         (mobi_amd.dist.allreduce_gradients).  FIRST SLICE of SURVEY 8(f) row 4: l2 loss with the default weights
         (`learn_logvar=False`, `original_elbo_weight=0`: the gradient of mean(loss_simple)); the conditioning stage's
         trainable tensors (the 3-D box embedder's four Linear layers, or `bbox_uncond_vector` on an unconditional draw) get
-        theirs too when `cond_stage_trainable`; `configure_optimizers()` returns the engine's AdamW to step with them."""
+        theirs too when `cond_stage_trainable`; `configure_optimizers()` returns the engine's AdamW to step with them.
+
+        scaler (a `train.GradScaler`): dynamic loss scaling.  The loss scale is `scaler.scale` (fixed at this first use from the
+        output's element count where the scaler was built with init_scale=None) and `self.adapter_grads` is left MULTIPLIED by it
+        -- the UNet tensors, the box embedder's eight tensors and `bbox_uncond_vector` all descend from the same scaled
+        gradient of the loss -- with the factor in `self.adapter_grads_scale`; `AdamW.step_scaled(self.adapter_grads, scaler=...)`
+        divides it out inside its update launch.  The gradient all-reduce runs on the scaled values and the overflow statistics
+        are taken after it (in `step_scaled`), on data every rank holds identically: all ranks take the same skip decision
+        without a collective of their own.  Without a scaler nothing changes (`adapter_grads_scale` is 1.0)."""
         from .... import dist as mdist, engine_dtype, train
         if self.loss_type != "l2" or self.parameterization != "eps" or self.learn_logvar or self.original_elbo_weight != 0:
             raise NotImplementedError("the engine's training step covers the eps / l2 simple loss MObI trains with")
@@ -420,16 +427,20 @@ class LatentDiffusion(DDPM):
         uncond = c is not cond_was_given and self.u_cond_prop < self.u_cond_percent
         t = t_draw if t is None else t
         x_noisy, target = self._noised_input(x, t, noise)
+        if scaler is not None:
+            assert loss_scale is None, "loss_scale and scaler are two ways to say the same thing"
+            loss_scale = scaler.first_use(target.numel())
         if loss_scale is None:
             # fp16 gradients underflow without it; bf16 has the range.  The gradient that enters the network is
             # 2 (eps - target) / numel, so the scale follows numel (a power of two near numel / 4: the entering gradient is
             # O(1) at every batch size) -- measured on the full-width network at 64 x 64, one pair: all 432 gradients 1.6e-2
             # off with a fixed 256, 1.7e-3 with 8,192 (tests/test_gpu_backward.py, full width)
-            loss_scale = 2.0 ** round(math.log2(max(4, target.numel()) / 4)) if engine_dtype() == torch.float16 else 1.0
+            loss_scale = train.static_loss_scale(target.numel()) if engine_dtype() == torch.float16 else 1.0
         logvar_t = self.logvar[t].to(self.device)                      # (zeros unless a checkpoint says otherwise)
         if bool((logvar_t != 0).any()):
             raise NotImplementedError("per-timestep logvar weights in the backward pass")
-        mse, grads = train.loss_and_gradients(self.model.diffusion_model, x_noisy, t, c, target, loss_scale=loss_scale)
+        mse, grads = train.loss_and_gradients(self.model.diffusion_model, x_noisy, t, c, target, loss_scale=loss_scale,
+                                              unscale=scaler is None)
         if self.l_simple_weight != 1.0:
             grads = {k: ops.lincomb4([g.contiguous()], [float(self.l_simple_weight)]) for k, g in grads.items()}
         dctx = grads.pop("__dcontext__", None)                         # fp32 [N, 2, ctx_dim]
@@ -451,6 +462,7 @@ class LatentDiffusion(DDPM):
         if allreduce and mdist.world()[1] > 1:
             mdist.allreduce_gradients(self._complete_cond_stage_grads(named, x.device, across_ranks=True))
         self.adapter_grads = named
+        self.adapter_grads_scale = 1.0 if scaler is None else float(loss_scale)
         return self.l_simple_weight * mse
 
     def _cond_stage_trainables(self):

@@ -595,6 +595,91 @@ def adamw_step(param, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), e
                                    weight_decay, step, _stream()), "mobi_adamw_step")
 
 
+def multi_tensor_chunk():
+    """Elements per chunk of the multi-tensor kernels' chunk map (a constant of the library)."""
+    c = C.c_int32(0)
+    _lib.load().mobi_multi_tensor_workspace_bytes(C.byref(c))
+    return c.value
+
+
+class MultiTensorList:
+    """The device-resident tables `grad_stats` / `adamw_multi` walk: {param, grad, exp_avg, exp_avg_sq, n} per tensor and the
+    chunk map {element offset, tensor index}.  Parameters and moments are fixed at construction (stable pointers, uploaded once
+    with the chunk map); `set_grads` writes this step's gradient pointers into a pinned host table and copies it on the current
+    stream.  The host table is not rewritten before that copy has completed: `set_grads` waits on the copy's event first (already
+    signalled where a step read the statistics record back, `read_grad_stats`, as `AdamW.step_scaled` does)."""
+
+    def __init__(self, params, exp_avgs, exp_avg_sqs):
+        import numpy as np
+        lib = _lib.load()
+        assert len(params) > 0 and len(params) == len(exp_avgs) == len(exp_avg_sqs)
+        for p, m, v in zip(params, exp_avgs, exp_avg_sqs):
+            for t_ in (p, m, v):
+                assert _dev(t_).dtype == torch.float32 and t_.is_contiguous() and t_.numel() == p.numel() > 0
+        self.device, self.count = params[0].device, len(params)
+        self._keep = (list(params), list(exp_avgs), list(exp_avg_sqs))
+        self.numels = [p.numel() for p in params]
+        chunk = multi_tensor_chunk()
+        self._host = torch.empty(self.count * C.sizeof(_lib.MtTensor), dtype=torch.uint8).pin_memory()
+        self._rows = self._host.numpy().view(np.int64).reshape(self.count, 5)      # MtTensor: four pointers and n, 8 bytes each
+        for col, ts in enumerate((params, None, exp_avgs, exp_avg_sqs)):
+            self._rows[:, col] = 0 if ts is None else [t_.data_ptr() for t_ in ts]
+        self._rows[:, 4] = self.numels
+        cmap = np.zeros(sum((n + chunk - 1) // chunk for n in self.numels),
+                        dtype=np.dtype([("offset", "<i8"), ("tensor", "<i4"), ("reserved", "<i4")]))
+        assert cmap.dtype.itemsize == C.sizeof(_lib.MtChunk)
+        at = 0
+        for i, n in enumerate(self.numels):
+            k = (n + chunk - 1) // chunk
+            cmap["offset"][at:at + k] = np.arange(k, dtype=np.int64) * chunk
+            cmap["tensor"][at:at + k] = i
+            at += k
+        self.n_chunks = len(cmap)
+        self.chunks = torch.from_numpy(cmap.view(np.uint8)).to(self.device)        # (a blocking copy, once)
+        self.tensors = torch.empty(self._host.numel(), dtype=torch.uint8, device=self.device)
+        self.workspace = torch.empty(lib.mobi_multi_tensor_workspace_bytes(None) // 8, dtype=torch.float64, device=self.device)
+        self.record = torch.zeros(C.sizeof(_lib.GradStatsRecord) // 8, dtype=torch.int64, device=self.device)
+        self._grads, self._copied = None, None
+
+    def set_grads(self, grads):
+        """grads: one fp32 tensor per listed parameter, of its numel (kept alive until the next call)."""
+        assert len(grads) == self.count
+        grads = [g.contiguous() for g in grads]
+        for g, n in zip(grads, self.numels):
+            assert _dev(g).dtype == torch.float32 and g.numel() == n
+        if self._copied is not None:
+            self._copied.synchronize()
+        self._rows[:, 1] = [g.data_ptr() for g in grads]
+        self.tensors.copy_(self._host, non_blocking=True)
+        self._copied = torch.cuda.Event()
+        self._copied.record()
+        self._grads = grads
+
+
+def grad_stats(mt):
+    """Sum of squares (fp64) and non-finite flag over every gradient of `mt` (one launch + its one-block finish pass) -> the device
+    record (`mt.record`); `read_grad_stats` brings it to the host."""
+    lib = _lib.load()
+    assert mt._grads is not None, "set_grads() first"
+    _lib.check(lib.mobi_grad_stats(_ptr(mt.tensors), mt.count, _ptr(mt.chunks), mt.n_chunks, _ptr(mt.workspace), _ptr(mt.record),
+                                   _stream()), "mobi_grad_stats")
+    return mt.record
+
+
+def read_grad_stats(record):
+    """The device record of `grad_stats` -> (sumsq: float, nonfinite: bool).  One blocking 16-byte copy: the host sync of a step."""
+    host = record.cpu()
+    return float(host.view(torch.float64)[0]), bool(int(host[1]) & 0xffffffff)
+
+
+def adamw_multi(mt, grad_mul, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    """`adamw_step` of every tensor of `mt` IN PLACE on grad * grad_mul, one launch (the caller bumps the tensors' versions)."""
+    lib = _lib.load()
+    assert mt._grads is not None, "set_grads() first"
+    _lib.check(lib.mobi_adamw_multi(_ptr(mt.tensors), mt.count, _ptr(mt.chunks), mt.n_chunks, grad_mul, lr, betas[0], betas[1], eps,
+                                    weight_decay, step, _stream()), "mobi_adamw_multi")
+
+
 def geglu_fwd(pre):
     """pre: T [..., 2 inner] = [value | gate] dense -> value * gelu_erf(gate): T [..., inner]."""
     lib = _lib.load()

@@ -18,6 +18,8 @@ Also here: the conditioning stage's trainable part (the 3-D box embedder, `bbox_
 Not built: `logvar`, LR schedulers, activation checkpointing (the tape of a full-width step at 64 x 64 x 4 is 17 GB: fine in 288 GB).
 `mobi_amd.dist.allreduce_gradients` is the gradient collective (bucketed, RCCL; gloo on CPU in the tests).
 """
+import math
+
 import torch
 
 from . import engine_dtype, ops
@@ -338,17 +340,19 @@ def unet_backward(net, tape, deps):
     return grads
 
 
-def loss_and_gradients(net, x_noisy, timesteps, context, target, loss_scale=1.0):
+def loss_and_gradients(net, x_noisy, timesteps, context, target, loss_scale=1.0, unscale=True):
     """The eps-parameterised simple loss of `p_losses` (ddpm.py:1177-1217: mean squared error of the UNet's output against
     the noise) and its gradient w.r.t. every adapter tensor.  loss_scale multiplies the gradient that enters the backward
-    pass and is divided out of the fp32 results (fp16 storage underflows without it at production sizes)."""
+    pass and is divided out of the fp32 results (fp16 storage underflows without it at production sizes); with
+    unscale=False that per-tensor pass is skipped and every gradient (`__dcontext__` too) comes back still multiplied by
+    loss_scale, for `AdamW.step_scaled` to divide out inside its one update launch."""
     eps, tape = unet_forward(net, x_noisy, timesteps, context)
     target = target.float().contiguous()
     loss = torch.mean((eps - target) ** 2)
     k = 2.0 * loss_scale / eps.numel()
     deps = ops.lincomb4([eps.contiguous(), target], [k, -k])
     grads = unet_backward(net, tape, deps)
-    if loss_scale != 1.0:
+    if unscale and loss_scale != 1.0:
         grads = {name: ops.lincomb4([g.contiguous()], [1.0 / loss_scale]) for name, g in grads.items()}
     return loss, grads                            # (grads["__dcontext__"]: the gradient w.r.t. the context tokens)
 
@@ -410,6 +414,73 @@ class LambdaLR:
         return [self.optimizer.lr]
 
 
+def static_loss_scale(numel):
+    """The loss scale `training_step` picks for fp16 from the element count of the UNet's output: a power of two near numel / 4
+    (the gradient that enters the network is 2 (eps - target) / numel)."""
+    return 2.0 ** round(math.log2(max(4, numel) / 4))
+
+
+class GradScaler:
+    """Dynamic loss scaling with the rules of torch.cuda.amp.GradScaler, the scale kept as a host float: `update(found_inf)`
+    multiplies it by `backoff_factor` on an overflow (and restarts the count of clean steps), by `growth_factor` after
+    `growth_interval` consecutive clean steps.  enabled=None: on for fp16 storage only (bf16 has fp32's range: the scale is 1.0
+    and never moves).  init_scale=None: `static_loss_scale(numel)` of the first step (`first_use`), so that a run starts at the
+    scale `training_step` uses without a scaler."""
+
+    def __init__(self, init_scale=None, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, enabled=None):
+        self.enabled = (engine_dtype() == torch.float16) if enabled is None else bool(enabled)
+        self.growth_factor, self.backoff_factor, self.growth_interval = float(growth_factor), float(backoff_factor), int(growth_interval)
+        self._scale = None if init_scale is None else float(init_scale)
+        self._growth_tracker = 0
+
+    def first_use(self, numel):
+        """Fixes the scale left open by init_scale=None from the element count of the UNet's output; returns the scale."""
+        if self.enabled and self._scale is None:
+            self._scale = static_loss_scale(numel)
+        return self.scale
+
+    @property
+    def scale(self):
+        if not self.enabled:
+            return 1.0
+        if self._scale is None:
+            raise RuntimeError("GradScaler(init_scale=None): the scale is set at first use (first_use(numel), training_step)")
+        return self._scale
+
+    def update(self, found_inf):
+        if not self.enabled:
+            return
+        if found_inf:
+            self._scale = self.scale * self.backoff_factor
+            self._growth_tracker = 0
+            return
+        self._growth_tracker += 1
+        if self._growth_tracker >= self.growth_interval:
+            self._scale = self.scale * self.growth_factor
+            self._growth_tracker = 0
+
+    def state_dict(self):
+        return {"scale": self._scale, "growth_tracker": self._growth_tracker, "growth_factor": self.growth_factor,
+                "backoff_factor": self.backoff_factor, "growth_interval": self.growth_interval}
+
+    def load_state_dict(self, sd):
+        self._scale = None if sd["scale"] is None else float(sd["scale"])
+        self._growth_tracker = int(sd["growth_tracker"])
+        self.growth_factor, self.backoff_factor = float(sd["growth_factor"]), float(sd["backoff_factor"])
+        self.growth_interval = int(sd["growth_interval"])
+
+
+class StepResult:
+    """What `AdamW.step_scaled` did: found_inf (the step was skipped), grad_norm (the UNscaled global L2 norm), clip_coef (what
+    the gradients were multiplied by besides 1 / scale), scale (the loss scale the gradients carried)."""
+
+    def __init__(self, found_inf, grad_norm, clip_coef, scale):
+        self.found_inf, self.grad_norm, self.clip_coef, self.scale = found_inf, grad_norm, clip_coef, scale
+
+    def __repr__(self):
+        return f"StepResult(found_inf={self.found_inf}, grad_norm={self.grad_norm}, clip_coef={self.clip_coef}, scale={self.scale})"
+
+
 class AdamW:
     """torch.optim.AdamW's update (what `configure_optimizers` returns, ddpm.py:1649) on the engine: fp32 master parameters
     updated in place by `mobi_adamw_step`, moments kept per parameter name."""
@@ -418,6 +489,7 @@ class AdamW:
         self.params = dict(named_params)
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.state, self.steps = {}, 0
+        self._multi = {}                              # step_scaled's tables, per set of names that had a gradient (built lazily)
 
     def step(self, grads):
         """grads: {name: fp32 tensor}; names without an entry are left alone."""
@@ -434,3 +506,40 @@ class AdamW:
         from .ldm.modules.diffusionmodules.util import WEIGHTS_EPOCH
         WEIGHTS_EPOCH[0] += 1
         return self
+
+    def step_scaled(self, grads, scaler=None, max_norm=None):
+        """`step()` for gradients that are still multiplied by `scaler.scale` (`training_step(..., scaler=s)`), with overflow
+        skipping and gradient-norm clipping, in two launches whatever the number of tensors: `mobi_grad_stats` (fp64 sum of squares
+        + non-finite flag over every gradient), ONE read-back of its 16-byte record -- the single host sync of a step: it keeps
+        `steps`, the bias corrections and the scale on the host, where `step()` keeps them -- then `mobi_adamw_multi` on
+        g * clip_coef / scale.  norm = sqrt(sumsq) / scale (host fp64); clip_coef = min(1, max_norm / (norm + 1e-6)) as
+        torch.nn.utils.clip_grad_norm_.  A non-finite gradient launches nothing more: `steps`, every parameter and both moments
+        stay as they are and the scaler backs off.  Names without an entry in `grads` are left alone.  -> StepResult."""
+        names = tuple(n for n in self.params if n in grads)
+        scale = 1.0 if scaler is None else scaler.scale
+        if not names:
+            return StepResult(False, 0.0, 1.0, scale)
+        mt = self._multi.get(names)
+        if mt is None:
+            for n in names:
+                p = self.params[n]
+                self.state.setdefault(n, (torch.zeros_like(p.data, dtype=torch.float32), torch.zeros_like(p.data, dtype=torch.float32)))
+            mt = self._multi[names] = ops.MultiTensorList([self.params[n].data for n in names], [self.state[n][0] for n in names],
+                                                          [self.state[n][1] for n in names])
+        mt.set_grads([grads[n].reshape(self.params[n].shape) for n in names])
+        sumsq, found_inf = ops.read_grad_stats(ops.grad_stats(mt))
+        if found_inf:
+            if scaler is not None:
+                scaler.update(True)
+            return StepResult(True, float("inf"), 0.0, scale)
+        norm = math.sqrt(sumsq) / scale
+        clip = 1.0 if max_norm is None else min(1.0, float(max_norm) / (norm + 1e-6))
+        self.steps += 1
+        ops.adamw_multi(mt, clip / scale, self.steps, self.lr, self.betas, self.eps, self.weight_decay)
+        for n in names:
+            torch.autograd.graph.increment_version(self.params[n])
+        from .ldm.modules.diffusionmodules.util import WEIGHTS_EPOCH
+        WEIGHTS_EPOCH[0] += 1
+        if scaler is not None:
+            scaler.update(False)
+        return StepResult(False, norm, clip, scale)

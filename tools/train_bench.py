@@ -2,7 +2,10 @@
 """Time one training step of the adapter parameters (mobi_amd/train.py: forward with a tape + the backward pass through the
 whole UNet + AdamW on the 432 adapter tensors) -- informational: the backward kernels are a first slice, not tuned.
 
-    python tools/train_bench.py [--mc 320] [--side 32] [--n 4] [--dtype bf16] [--iters 3]"""
+    python tools/train_bench.py [--mc 320] [--side 32] [--n 4] [--dtype bf16] [--iters 3] [--scaler]
+
+--scaler: the gradients stay multiplied by a `train.GradScaler`'s scale and `AdamW.step_scaled` (two multi-tensor launches + one
+read-back) replaces the per-tensor unscale and update launches; `--max-norm` adds gradient-norm clipping to it."""
 import argparse
 import math
 import os
@@ -25,6 +28,8 @@ def main():
     ap.add_argument("--n", type=int, default=4)
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--scaler", action="store_true")
+    ap.add_argument("--max-norm", type=float, default=None)
     a = ap.parse_args()
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float16
     mobi_amd.set_engine_dtype(dt)
@@ -42,10 +47,19 @@ def main():
     t = torch.full((a.n,), 500, dtype=torch.long, device="cuda")
     opt = train.AdamW({k: p for k, p in net.named_parameters() if any(m in k for m in train.TRAINABLE_MARKERS)}, lr=1e-5)
     sink = []
+    scaler = train.GradScaler() if a.scaler else None
+    if scaler is not None:
+        scaler.first_use(noise.numel())
 
     def step(profile=False):
         if profile:
             ops.set_profiler(sink)
+        if scaler is not None:
+            loss, grads = train.loss_and_gradients(net, x, t, ctx, noise, loss_scale=scaler.scale, unscale=False)
+            grads.pop("__dcontext__", None)
+            opt.step_scaled(grads, scaler=scaler, max_norm=a.max_norm)
+            ops.set_profiler(None)
+            return loss
         loss, grads = train.loss_and_gradients(net, x, t, ctx, noise, loss_scale=1.0 if dt == torch.bfloat16 else 2.0 ** round(math.log2(noise.numel() / 4)))
         grads.pop("__dcontext__", None)
         opt.step(grads)
@@ -63,6 +77,8 @@ def main():
         step()
         torch.cuda.synchronize()
     n_par = sum(p.numel() for p in opt.params.values())
+    if scaler is not None:
+        print(f"--scaler: loss scale {scaler.scale:g}, max_norm {a.max_norm}")
     print(f"training step, UNet model_channels {a.mc}, latent {a.side}x{a.side}, UNet batch {a.n}, {a.dtype}: {dt_s * 1e3:.1f} ms "
           f"(forward with tape + backward + AdamW on {len(opt.params)} tensors / {n_par / 1e6:.1f} M parameters), loss {float(loss):.4f}, "
           f"peak memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")
