@@ -50,7 +50,7 @@ extern "C" {
  *      mobi_maxpool3s2, mobi_lpips_distance + mobi_lpips_distance_ws_floats (mobi_lpips_distance_params, struct id 21),
  *      mobi_image_normalize (mobi_image_normalize_params, struct id 22) and mobi_row_cosine; likewise the multi-tensor
  *      passes mobi_grad_stats / mobi_adamw_multi + mobi_multi_tensor_workspace_bytes (mobi_mt_tensor 23, mobi_mt_chunk 24,
- *      mobi_grad_stats_record 25) */
+ *      mobi_grad_stats_record 25); likewise the EMA / swap pass over tensor pairs, mobi_ema_multi (mobi_mt_pair 26) */
 #define MOBI_ABI_VERSION 6
 
 enum { MOBI_OK = 0, MOBI_ERR_ARG = -1, MOBI_ERR_UNSUPPORTED = -2, MOBI_ERR_LAUNCH = -3, MOBI_ERR_ALIGN = -4 };
@@ -63,7 +63,7 @@ const char* mobi_error_string(int code);
  * 3 attention, 4 ctx_attention, 5 skinny_linear, 6 conv_small_cin, 7 conv_small_cout,
  * 8 ddim_step, 9 two_key_adapter, 10 range_paste, 11 lidar_metrics, 12 range_prepare, 13 image_prepare, 14 ff_geglu,
  * 15 row_chain, 16 chain_op, 17 layernorm_bwd, 18 attention_bwd, 19 split_source, 20 dpm_step, 21 lpips_distance,
- * 22 image_normalize, 23 mt_tensor, 24 mt_chunk, 25 grad_stats_record.  Returns 0 for an unknown id. */
+ * 22 image_normalize, 23 mt_tensor, 24 mt_chunk, 25 grad_stats_record, 26 mt_pair.  Returns 0 for an unknown id. */
 size_t mobi_struct_size(int id);
 /* Development hook: the library reads its MOBI_* A/B environment variables once, at the first launch
  * (mobi_amd/csrc/tuning.h lists them); this re-reads them.  Not needed by a product caller. */
@@ -469,6 +469,17 @@ int mobi_grad_stats(const mobi_mt_tensor* tensors, int32_t n_tensors, const mobi
  * operations per element as mobi_adamw_step: with grad_mul == 1 the results are bit-identical to the per-tensor launches. */
 int mobi_adamw_multi(const mobi_mt_tensor* tensors, int32_t n_tensors, const mobi_mt_chunk* chunks, int32_t n_chunks,
                      float grad_mul, float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step, void* stream);
+/* One launch over a DEVICE-resident table of tensor PAIRS, through the same chunk map (cut by `n`; entries that do not lie inside
+ * their pair are skipped).  Addition to ABI 6 (struct id 26).
+ *   MOBI_MT_EMA   a = the live parameter (read only), b = its EMA shadow: b <- b - one_minus_decay * (b - a), three separately
+ *                 rounded fp32 operations (subtract, multiply, subtract: torch's shadow.sub_(one_minus_decay * (shadow - param)),
+ *                 ldm/modules/ema.py:42 of the reference), bit for bit
+ *   MOBI_MT_SWAP  a[i] <-> b[i] (ema_scope: the module computes with the shadows and gets its weights back, without a copy
+ *                 of either); one_minus_decay is not read */
+enum { MOBI_MT_EMA = 0, MOBI_MT_SWAP = 1 };
+typedef struct mobi_mt_pair { float* a; float* b; int64_t n; } mobi_mt_pair;
+int mobi_ema_multi(const mobi_mt_pair* pairs, int32_t n_pairs, const mobi_mt_chunk* chunks, int32_t n_chunks,
+                   float one_minus_decay, int32_t op, void* stream);
 
 typedef struct mobi_attention_bwd_params {
   const void* q; int64_t q_img_stride, q_row_stride;       /* T [image][tq][>= heads*dh], strides in elements */

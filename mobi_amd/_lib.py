@@ -178,6 +178,13 @@ class MtTensor(C.Structure):
     _fields_ = [("param", vp), ("grad", vp), ("exp_avg", vp), ("exp_avg_sq", vp), ("n", i64)]
 
 
+class MtPair(C.Structure):
+    _fields_ = [("a", vp), ("b", vp), ("n", i64)]
+
+
+MT_EMA, MT_SWAP = 0, 1
+
+
 class MtChunk(C.Structure):
     _fields_ = [("offset", i64), ("tensor", i32), ("reserved", i32)]
 
@@ -191,7 +198,8 @@ STRUCT_IDS = {0: IgemmParams, 1: GroupNormParams, 2: LayerNormParams, 3: Attenti
               10: RangePasteParams, 11: LidarMetricsParams, 12: RangePrepareParams, 13: ImagePrepareParams,
               14: FfGegluParams, 15: RowChainParams, 16: ChainOp,
               17: LayerNormBwdParams, 18: AttentionBwdParams, 19: SplitSource, 20: DpmStepParams,
-              21: LpipsDistanceParams, 22: ImageNormalizeParams, 23: MtTensor, 24: MtChunk, 25: GradStatsRecord}
+              21: LpipsDistanceParams, 22: ImageNormalizeParams, 23: MtTensor, 24: MtChunk, 25: GradStatsRecord,
+              26: MtPair}
 
 # every symbol include/mobi_engine.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -246,6 +254,7 @@ SYMBOLS = {
     "mobi_multi_tensor_workspace_bytes": (C.c_size_t, [C.POINTER(i32)]),
     "mobi_grad_stats": (C.c_int, [vp, i32, vp, i32, vp, vp, vp]),
     "mobi_adamw_multi": (C.c_int, [vp, i32, vp, i32, f32, f32, f32, f32, f32, f32, i32, vp]),
+    "mobi_ema_multi": (C.c_int, [vp, i32, vp, i32, f32, i32, vp]),
     "mobi_quick_gelu": (C.c_int, [vp, vp, i64, i32, vp]),
     "mobi_timestep_embedding": (C.c_int, [vp, vp, vp, i32, i32, vp]),
     "mobi_conv_small_cin": (C.c_int, [C.POINTER(ConvSmallCinParams), vp]),

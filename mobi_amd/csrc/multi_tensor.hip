@@ -1,7 +1,7 @@
 // Multi-tensor passes of the fp16 training step (include/mobi_engine.h, "Multi-tensor passes"; mobi_amd/train.py GradScaler /
 // AdamW.step_scaled): the gradient statistics (sum of squares + non-finite flag) and the AdamW update of EVERY listed tensor in one
 // launch each, instead of one launch per tensor (432 adapter tensors + the conditioning stage's: ~880 launches of a few hundred KB
-// to a few MB each).  Both kernels walk a device-resident table of tensors through a device-resident chunk map: every tensor is cut
+// to a few MB each); and the EMA update / swap of every (parameter, shadow) pair (mobi_amd/ldm/modules/ema.py).  All kernels walk a device-resident table of tensors through a device-resident chunk map: every tensor is cut
 // into chunks of kMtChunk elements, one 256-thread block takes chunks in a grid-stride walk, the grid follows the CU count.  Pure
 // streaming: 16-byte accesses on the 16-byte-aligned body of a chunk, 4-byte accesses on its head and tail (a tensor may start at
 // any 4-byte boundary); no atomics, LDS only for the block reduction of the statistics.
@@ -20,8 +20,10 @@ __device__ __forceinline__ int mt_phase(const void* p) { return (int)((16u - (un
 
 // chunk c of the map -> (tensor entry, element offset, length); false for an entry that does not lie inside its tensor (a map that
 // does not belong to the table must never turn into an out-of-bounds access)
-__device__ __forceinline__ bool mt_chunk(const mobi_mt_tensor* __restrict__ tensors, int n_tensors, const mobi_mt_chunk* __restrict__ chunks,
-                                         int c, mobi_mt_tensor& t, long long& off, int& len) {
+// (Entry: mobi_mt_tensor or mobi_mt_pair -- a table row with its element count in `n`)
+template <class Entry>
+__device__ __forceinline__ bool mt_chunk(const Entry* __restrict__ tensors, int n_tensors, const mobi_mt_chunk* __restrict__ chunks,
+                                         int c, Entry& t, long long& off, int& len) {
   const mobi_mt_chunk ch = chunks[c];
   if (ch.tensor < 0 || ch.tensor >= n_tensors) return false;
   t = tensors[ch.tensor];
@@ -150,6 +152,62 @@ __global__ __launch_bounds__(kMtBlock) void adamw_multi_kernel(const mobi_mt_ten
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Tensor pairs: the EMA update of the shadows (b <- b - omd (b - a): subtract, multiply, subtract, each rounded to fp32 -- what
+// torch's shadow.sub_(omd * (shadow - param)) computes; a contracted b - omd d differs in the last bit) or the exchange of a
+// and b.  The 16-byte path needs both pointers at the same alignment phase, as above.
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float ema_update(float b, float a, float omd) {
+#pragma clang fp contract(off)
+  const float d = b - a;
+  const float s = omd * d;
+  return b - s;
+}
+
+template <int OP>
+__global__ __launch_bounds__(kMtBlock) void ema_multi_kernel(const mobi_mt_pair* __restrict__ pairs, int n_pairs,
+                                                             const mobi_mt_chunk* __restrict__ chunks, int n_chunks, float omd) {
+  const int tid = threadIdx.x;
+  for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+    mobi_mt_pair t;
+    long long off;
+    int len;
+    if (!mt_chunk(pairs, n_pairs, chunks, c, t, off, len)) continue;
+    float* __restrict__ a = t.a + off;
+    float* __restrict__ b = t.b + off;
+    const int ph = mt_phase(b);
+    const bool same = ph == mt_phase(a);
+    const int head = same && ph < len ? ph : len;
+    const int nvec = (len - head) >> 2, tail0 = head + (nvec << 2);
+    auto one = [&](int i) {
+      const float ai = a[i], bi = b[i];
+      if (OP == MOBI_MT_EMA) {
+        b[i] = ema_update(bi, ai, omd);
+      } else {
+        a[i] = bi;
+        b[i] = ai;
+      }
+    };
+    for (int i = tid; i < head; i += kMtBlock) one(i);
+    for (int i = tail0 + tid; i < len; i += kMtBlock) one(i);
+    f32x4* __restrict__ av = reinterpret_cast<f32x4*>(a + head);
+    f32x4* __restrict__ bv = reinterpret_cast<f32x4*>(b + head);
+#pragma unroll 4
+    for (int i = tid; i < nvec; i += kMtBlock) {
+      const f32x4 aq = av[i];
+      f32x4 bq = bv[i];
+      if (OP == MOBI_MT_EMA) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bq[j] = ema_update(bq[j], aq[j], omd);
+        bv[i] = bq;
+      } else {
+        av[i] = bq;
+        bv[i] = aq;
+      }
+    }
+  }
+}
+
 static int mt_grid(int n_chunks) {
   static int cus = 0;
   if (!cus) {
@@ -192,6 +250,19 @@ extern "C" int mobi_adamw_multi(const mobi_mt_tensor* tensors, int32_t n_tensors
   const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
   hipLaunchKernelGGL(adamw_multi_kernel, dim3(mt_grid(n_chunks)), dim3(kMtBlock), 0, ST(stream), tensors, n_tensors, chunks, n_chunks,
                      grad_mul, lr, beta1, beta2, eps, weight_decay, bc1, sqrtf(bc2));
+  MOBI_CHECK_LAUNCH();
+  return MOBI_OK;
+}
+
+extern "C" int mobi_ema_multi(const mobi_mt_pair* pairs, int32_t n_pairs, const mobi_mt_chunk* chunks, int32_t n_chunks,
+                              float one_minus_decay, int32_t op, void* stream) {
+  if (!pairs || !chunks || n_pairs <= 0 || n_chunks <= 0 || (op != MOBI_MT_EMA && op != MOBI_MT_SWAP)) return MOBI_ERR_ARG;
+  if (op == MOBI_MT_EMA)
+    hipLaunchKernelGGL(ema_multi_kernel<MOBI_MT_EMA>, dim3(mt_grid(n_chunks)), dim3(kMtBlock), 0, ST(stream), pairs, n_pairs, chunks,
+                       n_chunks, one_minus_decay);
+  else
+    hipLaunchKernelGGL(ema_multi_kernel<MOBI_MT_SWAP>, dim3(mt_grid(n_chunks)), dim3(kMtBlock), 0, ST(stream), pairs, n_pairs, chunks,
+                       n_chunks, one_minus_decay);
   MOBI_CHECK_LAUNCH();
   return MOBI_OK;
 }

@@ -274,6 +274,7 @@ extern "C" size_t mobi_struct_size(int id) {
     case 23: return sizeof(mobi_mt_tensor);
     case 24: return sizeof(mobi_mt_chunk);
     case 25: return sizeof(mobi_grad_stats_record);
+    case 26: return sizeof(mobi_mt_pair);
     default: return 0;
   }
 }

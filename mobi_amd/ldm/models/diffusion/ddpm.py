@@ -5,8 +5,8 @@ touches (scripts/inference_test_bench.py:403-464): DDPM.register_schedule :127-1
 q_sample :284-287, LatentDiffusion.__init__ :440-531, get_learned_conditioning :610-630,
 get_input :758-834, decode_first_stage :837-901, encode_first_stage :970-1008,
 encode_all_stages :1010-1033, apply_model :1060-1157, decode_sample :1420-1447,
-DiffusionWrapper :1682-1722.  Training (p_losses, optimizers, EMA updates, logging images)
-is out of scope.
+DiffusionWrapper :1682-1722; the training / validation step on the engine's backward pass (mobi_amd/train.py) and the
+EMA shadow weights (`use_ema`, ldm/modules/ema.py).
 """
 import warnings
 from contextlib import contextmanager
@@ -20,6 +20,7 @@ import torch.nn.functional as F
 from .... import ops
 from ...modules.diffusionmodules.util import Linear, extract_into_tensor, make_beta_schedule
 from ...modules.distributions.distributions import DiagonalGaussianDistribution
+from ...modules.ema import LitEma
 from ...util import cat_interleave, default, instantiate_from_config, make_contiguous
 
 
@@ -56,8 +57,9 @@ class DDPM(nn.Module):
         self.u_cond_percent = u_cond_percent
         self.model = DiffusionWrapper(unet_config, conditioning_key)
         self.use_ema = use_ema
-        if use_ema:
-            raise NotImplementedError("EMA shadow weights are a training feature; MObI ships use_ema: False")
+        if self.use_ema:                                       # ddpm.py:98-101
+            self.model_ema = LitEma(self.model)
+            print(f"Keeping EMAs of {len(list(self.model_ema.buffers()))}.")
         self.v_posterior = v_posterior
         self.loss_type, self.l_simple_weight, self.original_elbo_weight = loss_type, l_simple_weight, original_elbo_weight
         if learn_logvar:
@@ -139,7 +141,31 @@ class DDPM(nn.Module):
 
     @contextmanager
     def ema_scope(self, context=None):
-        yield None          # use_ema is False in every MObI config (mobi_nusc_512.yaml:47)
+        """ddpm.py:181-194: inside the scope `self.model` computes with the EMA weights.  The reference clones every parameter,
+        copies the shadows in and copies the clones back; here parameters and shadows trade places in ONE launch on entry and
+        one on exit (`LitEma.swap`: no clone of the UNet), so inside the scope the `model_ema` buffers hold the live weights --
+        do not update or checkpoint the EMA from inside it.  Exit restores both bit for bit, also after an exception.  Each swap
+        bumps the swapped parameters' versions and the weights epoch: packed 16-bit copies and captured step graphs follow.
+        Without `use_ema` (every MObI config, mobi_nusc_512.yaml:47) nothing is launched and nothing is bumped."""
+        if not self.use_ema:
+            yield None
+            return
+        self.model_ema.swap(self.model)
+        if context is not None:
+            print(f"{context}: Switched to EMA weights")
+        try:
+            yield None
+        finally:
+            self.model_ema.swap(self.model)
+            if context is not None:
+                print(f"{context}: Restored training weights")
+
+    def on_train_batch_end(self, *args, **kwargs):
+        """ddpm.py:380-382, the hook Lightning calls after every batch: one EMA update of the shadows (one launch).  Calling it
+        is the training loop's job, after the optimizer step -- also after a step the loss scaler skipped, as under Lightning,
+        where the hook does not know of the skip (the shadows then move towards unchanged weights once more)."""
+        if self.use_ema:
+            self.model_ema(self.model)
 
     def q_sample(self, x_start, t, noise=None):
         """sqrt(ac[t]) * x0 + sqrt(1 - ac[t]) * noise (ddpm.py:284-287): one kernel gathers the tables by the
@@ -382,7 +408,7 @@ class LatentDiffusion(DDPM):
         return self._loss_terms(self.get_loss(model_output, target, mean=False).mean([1, 2, 3]), t)
 
     def validation_step(self, batch, batch_idx=0):
-        """ddpm.py:372-378 without the Lightning logger: the loss dict (and its `_ema` twin: use_ema is False)."""
+        """ddpm.py:372-378 without the Lightning logger: the loss dict and its `_ema` twin, computed inside `ema_scope()`."""
         _, loss_dict = self.shared_step(batch)
         with self.ema_scope():
             _, loss_dict_ema = self.shared_step(batch)

@@ -602,6 +602,23 @@ def multi_tensor_chunk():
     return c.value
 
 
+def multi_tensor_chunk_map(numels, chunk=None):
+    """The chunk map of a list of tensor lengths, as a numpy record array {offset, tensor, reserved}: tensor i cut into
+    ceil(n_i / chunk) entries, in order."""
+    import numpy as np
+    chunk = multi_tensor_chunk() if chunk is None else chunk
+    cmap = np.zeros(sum((n + chunk - 1) // chunk for n in numels),
+                    dtype=np.dtype([("offset", "<i8"), ("tensor", "<i4"), ("reserved", "<i4")]))
+    assert cmap.dtype.itemsize == C.sizeof(_lib.MtChunk)
+    at = 0
+    for i, n in enumerate(numels):
+        k = (n + chunk - 1) // chunk
+        cmap["offset"][at:at + k] = np.arange(k, dtype=np.int64) * chunk
+        cmap["tensor"][at:at + k] = i
+        at += k
+    return cmap
+
+
 class MultiTensorList:
     """The device-resident tables `grad_stats` / `adamw_multi` walk: {param, grad, exp_avg, exp_avg_sq, n} per tensor and the
     chunk map {element offset, tensor index}.  Parameters and moments are fixed at construction (stable pointers, uploaded once
@@ -619,21 +636,12 @@ class MultiTensorList:
         self.device, self.count = params[0].device, len(params)
         self._keep = (list(params), list(exp_avgs), list(exp_avg_sqs))
         self.numels = [p.numel() for p in params]
-        chunk = multi_tensor_chunk()
         self._host = torch.empty(self.count * C.sizeof(_lib.MtTensor), dtype=torch.uint8).pin_memory()
         self._rows = self._host.numpy().view(np.int64).reshape(self.count, 5)      # MtTensor: four pointers and n, 8 bytes each
         for col, ts in enumerate((params, None, exp_avgs, exp_avg_sqs)):
             self._rows[:, col] = 0 if ts is None else [t_.data_ptr() for t_ in ts]
         self._rows[:, 4] = self.numels
-        cmap = np.zeros(sum((n + chunk - 1) // chunk for n in self.numels),
-                        dtype=np.dtype([("offset", "<i8"), ("tensor", "<i4"), ("reserved", "<i4")]))
-        assert cmap.dtype.itemsize == C.sizeof(_lib.MtChunk)
-        at = 0
-        for i, n in enumerate(self.numels):
-            k = (n + chunk - 1) // chunk
-            cmap["offset"][at:at + k] = np.arange(k, dtype=np.int64) * chunk
-            cmap["tensor"][at:at + k] = i
-            at += k
+        cmap = multi_tensor_chunk_map(self.numels)
         self.n_chunks = len(cmap)
         self.chunks = torch.from_numpy(cmap.view(np.uint8)).to(self.device)        # (a blocking copy, once)
         self.tensors = torch.empty(self._host.numel(), dtype=torch.uint8, device=self.device)
@@ -678,6 +686,48 @@ def adamw_multi(mt, grad_mul, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_dec
     assert mt._grads is not None, "set_grads() first"
     _lib.check(lib.mobi_adamw_multi(_ptr(mt.tensors), mt.count, _ptr(mt.chunks), mt.n_chunks, grad_mul, lr, betas[0], betas[1], eps,
                                     weight_decay, step, _stream()), "mobi_adamw_multi")
+
+
+class MultiTensorPairs:
+    """The device-resident tables `ema_multi` / `swap_multi` walk: {a, b, n} per pair of dense fp32 tensors of equal length and
+    the chunk map.  Uploaded once: the pointers are stable (parameters and their EMA shadows never reallocate; `ptrs` is what
+    a caller compares to notice that they did).  `chunk_map`: a map of the caller's own (a numpy record array as
+    `multi_tensor_chunk_map` makes it) in place of the table's."""
+
+    def __init__(self, a_list, b_list, chunk_map=None):
+        import numpy as np
+        assert len(a_list) > 0 and len(a_list) == len(b_list)
+        for a, b in zip(a_list, b_list):
+            for t_ in (a, b):
+                assert _dev(t_).dtype == torch.float32 and t_.is_contiguous() and t_.numel() == a.numel() > 0
+            assert a.device == b.device
+        self.device, self.count = a_list[0].device, len(a_list)
+        self._keep = (list(a_list), list(b_list))
+        self.numels = [a.numel() for a in a_list]
+        self.ptrs = tuple((a.data_ptr(), b.data_ptr()) for a, b in zip(a_list, b_list))
+        rows = np.empty((self.count, 3), dtype=np.int64)                           # MtPair: two pointers and n, 8 bytes each
+        assert rows.itemsize * 3 == C.sizeof(_lib.MtPair)
+        rows[:, :2] = self.ptrs
+        rows[:, 2] = self.numels
+        cmap = multi_tensor_chunk_map(self.numels) if chunk_map is None else chunk_map
+        self.n_chunks = len(cmap)
+        self.chunks = torch.from_numpy(cmap.view(np.uint8)).to(self.device)        # (blocking copies, once)
+        self.pairs = torch.from_numpy(rows.view(np.uint8).reshape(-1)).to(self.device)
+
+
+def ema_multi(pairs, one_minus_decay):
+    """b <- b - one_minus_decay * (b - a) for every pair of `pairs` (a MultiTensorPairs: a = parameter, b = shadow), one launch;
+    three separately rounded fp32 operations per element, as torch's `b.sub_(omd * (b - a))`."""
+    lib = _lib.load()
+    _lib.check(lib.mobi_ema_multi(_ptr(pairs.pairs), pairs.count, _ptr(pairs.chunks), pairs.n_chunks, float(one_minus_decay),
+                                  _lib.MT_EMA, _stream()), "mobi_ema_multi")
+
+
+def swap_multi(pairs):
+    """a <-> b for every pair of `pairs`, one launch, IN PLACE on both (raw-pointer writes: the caller bumps the versions)."""
+    lib = _lib.load()
+    _lib.check(lib.mobi_ema_multi(_ptr(pairs.pairs), pairs.count, _ptr(pairs.chunks), pairs.n_chunks, 0.0, _lib.MT_SWAP,
+                                  _stream()), "mobi_ema_multi")
 
 
 def geglu_fwd(pre):

@@ -2,10 +2,12 @@
 """Time one training step of the adapter parameters (mobi_amd/train.py: forward with a tape + the backward pass through the
 whole UNet + AdamW on the 432 adapter tensors) -- informational: the backward kernels are a first slice, not tuned.
 
-    python tools/train_bench.py [--mc 320] [--side 32] [--n 4] [--dtype bf16] [--iters 3] [--scaler]
+    python tools/train_bench.py [--mc 320] [--side 32] [--n 4] [--dtype bf16] [--iters 3] [--scaler] [--ema]
 
 --scaler: the gradients stay multiplied by a `train.GradScaler`'s scale and `AdamW.step_scaled` (two multi-tensor launches + one
-read-back) replaces the per-tensor unscale and update launches; `--max-norm` adds gradient-norm clipping to it."""
+read-back) replaces the per-tensor unscale and update launches; `--max-norm` adds gradient-norm clipping to it.
+--ema: EMA shadows of every `requires_grad` tensor of the UNet (`ldm.modules.ema.LitEma`, what `LatentDiffusion(use_ema=True)`
+keeps) and their update inside the timed step, after the optimizer's (what `on_train_batch_end` calls: one `mobi_ema_multi` launch)."""
 import argparse
 import math
 import os
@@ -30,6 +32,7 @@ def main():
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--scaler", action="store_true")
     ap.add_argument("--max-norm", type=float, default=None)
+    ap.add_argument("--ema", action="store_true")
     a = ap.parse_args()
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float16
     mobi_amd.set_engine_dtype(dt)
@@ -46,6 +49,10 @@ def main():
     noise = W.synth_input("tb.n", (a.n, 4, a.side, a.side)).cuda()
     t = torch.full((a.n,), 500, dtype=torch.long, device="cuda")
     opt = train.AdamW({k: p for k, p in net.named_parameters() if any(m in k for m in train.TRAINABLE_MARKERS)}, lr=1e-5)
+    ema = None
+    if a.ema:
+        from mobi_amd.ldm.modules.ema import LitEma
+        ema = LitEma(net)
     sink = []
     scaler = train.GradScaler() if a.scaler else None
     if scaler is not None:
@@ -58,11 +65,15 @@ def main():
             loss, grads = train.loss_and_gradients(net, x, t, ctx, noise, loss_scale=scaler.scale, unscale=False)
             grads.pop("__dcontext__", None)
             opt.step_scaled(grads, scaler=scaler, max_norm=a.max_norm)
+            if ema is not None:
+                ema(net)
             ops.set_profiler(None)
             return loss
         loss, grads = train.loss_and_gradients(net, x, t, ctx, noise, loss_scale=1.0 if dt == torch.bfloat16 else 2.0 ** round(math.log2(noise.numel() / 4)))
         grads.pop("__dcontext__", None)
         opt.step(grads)
+        if ema is not None:
+            ema(net)
         ops.set_profiler(None)
         return loss
     with torch.no_grad():
@@ -77,6 +88,10 @@ def main():
         step()
         torch.cuda.synchronize()
     n_par = sum(p.numel() for p in opt.params.values())
+    if ema is not None:
+        n_ema = sum(b.numel() for b in ema.buffers()) - 2
+        print(f"--ema: shadows of {len(list(ema.buffers())) - 2} tensors / {n_ema / 1e6:.1f} M parameters ({n_ema * 4 / 2**30:.2f} GiB), "
+              f"{int(ema.num_updates)} updates")
     if scaler is not None:
         print(f"--scaler: loss scale {scaler.scale:g}, max_norm {a.max_norm}")
     print(f"training step, UNet model_channels {a.mc}, latent {a.side}x{a.side}, UNet batch {a.n}, {a.dtype}: {dt_s * 1e3:.1f} ms "
