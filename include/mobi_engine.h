@@ -50,7 +50,8 @@ extern "C" {
  *      mobi_maxpool3s2, mobi_lpips_distance + mobi_lpips_distance_ws_floats (mobi_lpips_distance_params, struct id 21),
  *      mobi_image_normalize (mobi_image_normalize_params, struct id 22) and mobi_row_cosine; likewise the multi-tensor
  *      passes mobi_grad_stats / mobi_adamw_multi + mobi_multi_tensor_workspace_bytes (mobi_mt_tensor 23, mobi_mt_chunk 24,
- *      mobi_grad_stats_record 25); likewise the EMA / swap pass over tensor pairs, mobi_ema_multi (mobi_mt_pair 26) */
+ *      mobi_grad_stats_record 25); likewise the EMA / swap pass over tensor pairs, mobi_ema_multi (mobi_mt_pair 26); likewise
+ *      the gradient accumulation over the same pair tables, mobi_accum_multi (no new struct) */
 #define MOBI_ABI_VERSION 6
 
 enum { MOBI_OK = 0, MOBI_ERR_ARG = -1, MOBI_ERR_UNSUPPORTED = -2, MOBI_ERR_LAUNCH = -3, MOBI_ERR_ALIGN = -4 };
@@ -480,6 +481,17 @@ enum { MOBI_MT_EMA = 0, MOBI_MT_SWAP = 1 };
 typedef struct mobi_mt_pair { float* a; float* b; int64_t n; } mobi_mt_pair;
 int mobi_ema_multi(const mobi_mt_pair* pairs, int32_t n_pairs, const mobi_mt_chunk* chunks, int32_t n_chunks,
                    float one_minus_decay, int32_t op, void* stream);
+/* Gradient accumulation over a window of micro-batches: one launch over the same pair tables and chunk map.  a = one
+ * micro-batch's gradient (read only), b = the fp32 accumulator, w = the micro-batch's weight (1 / micro-batches).  Addition to
+ * ABI 6 (no new struct; the ops count from 0 on their own: mobi_ema_multi takes none of them, this function none of its).
+ *   MOBI_MT_ACCUM   b <- b + (w * a): the product rounded to fp32, then the sum rounded to fp32 (never contracted into one
+ *                   rounding) -- numpy's / torch's fp32 sequence, bit for bit
+ *   MOBI_MT_ASSIGN  b <- w * a; b is NOT read: a window's first contribution replaces whatever an earlier (possibly skipped)
+ *                   window left behind, nan and inf included
+ * inf and nan in a propagate (inf * w, inf + x, inf - inf = nan), so mobi_grad_stats on the accumulators flags them. */
+enum { MOBI_MT_ACCUM = 0, MOBI_MT_ASSIGN = 1 };
+int mobi_accum_multi(const mobi_mt_pair* pairs, int32_t n_pairs, const mobi_mt_chunk* chunks, int32_t n_chunks, float w,
+                     int32_t op, void* stream);
 
 typedef struct mobi_attention_bwd_params {
   const void* q; int64_t q_img_stride, q_row_stride;       /* T [image][tq][>= heads*dh], strides in elements */

@@ -182,7 +182,8 @@ class MtPair(C.Structure):
     _fields_ = [("a", vp), ("b", vp), ("n", i64)]
 
 
-MT_EMA, MT_SWAP = 0, 1
+MT_EMA, MT_SWAP = 0, 1            # mobi_ema_multi's ops
+MT_ACCUM, MT_ASSIGN = 0, 1        # mobi_accum_multi's ops
 
 
 class MtChunk(C.Structure):
@@ -255,6 +256,7 @@ SYMBOLS = {
     "mobi_grad_stats": (C.c_int, [vp, i32, vp, i32, vp, vp, vp]),
     "mobi_adamw_multi": (C.c_int, [vp, i32, vp, i32, f32, f32, f32, f32, f32, f32, i32, vp]),
     "mobi_ema_multi": (C.c_int, [vp, i32, vp, i32, f32, i32, vp]),
+    "mobi_accum_multi": (C.c_int, [vp, i32, vp, i32, f32, i32, vp]),
     "mobi_quick_gelu": (C.c_int, [vp, vp, i64, i32, vp]),
     "mobi_timestep_embedding": (C.c_int, [vp, vp, vp, i32, i32, vp]),
     "mobi_conv_small_cin": (C.c_int, [C.POINTER(ConvSmallCinParams), vp]),

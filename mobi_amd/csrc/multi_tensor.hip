@@ -1,7 +1,8 @@
 // Multi-tensor passes of the fp16 training step (include/mobi_engine.h, "Multi-tensor passes"; mobi_amd/train.py GradScaler /
 // AdamW.step_scaled): the gradient statistics (sum of squares + non-finite flag) and the AdamW update of EVERY listed tensor in one
 // launch each, instead of one launch per tensor (432 adapter tensors + the conditioning stage's: ~880 launches of a few hundred KB
-// to a few MB each); and the EMA update / swap of every (parameter, shadow) pair (mobi_amd/ldm/modules/ema.py).  All kernels walk a device-resident table of tensors through a device-resident chunk map: every tensor is cut
+// to a few MB each); the EMA update / swap of every (parameter, shadow) pair (mobi_amd/ldm/modules/ema.py); and the gradient
+// accumulation of a window of micro-batches (mobi_amd/train.py GradAccumulator).  All kernels walk a device-resident table of tensors through a device-resident chunk map: every tensor is cut
 // into chunks of kMtChunk elements, one 256-thread block takes chunks in a grid-stride walk, the grid follows the CU count.  Pure
 // streaming: 16-byte accesses on the 16-byte-aligned body of a chunk, 4-byte accesses on its head and tail (a tensor may start at
 // any 4-byte boundary); no atomics, LDS only for the block reduction of the statistics.
@@ -155,8 +156,14 @@ __global__ __launch_bounds__(kMtBlock) void adamw_multi_kernel(const mobi_mt_ten
 // ---------------------------------------------------------------------------------------------------------------------
 // Tensor pairs: the EMA update of the shadows (b <- b - omd (b - a): subtract, multiply, subtract, each rounded to fp32 -- what
 // torch's shadow.sub_(omd * (shadow - param)) computes; a contracted b - omd d differs in the last bit) or the exchange of a
-// and b.  The 16-byte path needs both pointers at the same alignment phase, as above.
+// and b; or one micro-batch's gradient a into the accumulator b (b <- b + w a: multiply, add, each rounded to fp32 -- the
+// numpy / torch fp32 sequence, no contraction into one rounding; or b <- w a WITHOUT reading b: a window's first contribution
+// never meets what an earlier window left in the accumulator, nan included).  One walker for all four (OP, below).  The 16-byte
+// path needs both pointers at the same alignment phase, as above.
 // ---------------------------------------------------------------------------------------------------------------------
+// the walker's OPs: the two of mobi_ema_multi carry their public values, the two of mobi_accum_multi follow
+enum { kPairEma = MOBI_MT_EMA, kPairSwap = MOBI_MT_SWAP, kPairAccum = 2, kPairAssign = 3 };
+
 __device__ __forceinline__ float ema_update(float b, float a, float omd) {
 #pragma clang fp contract(off)
   const float d = b - a;
@@ -164,9 +171,16 @@ __device__ __forceinline__ float ema_update(float b, float a, float omd) {
   return b - s;
 }
 
+__device__ __forceinline__ float accum_update(float b, float a, float w) {
+#pragma clang fp contract(off)
+  const float s = w * a;
+  return b + s;
+}
+
+// `w`: one_minus_decay (EMA), the micro-batch weight (ACCUM, ASSIGN), not read (SWAP).  a is read only except under SWAP.
 template <int OP>
-__global__ __launch_bounds__(kMtBlock) void ema_multi_kernel(const mobi_mt_pair* __restrict__ pairs, int n_pairs,
-                                                             const mobi_mt_chunk* __restrict__ chunks, int n_chunks, float omd) {
+__global__ __launch_bounds__(kMtBlock) void pair_multi_kernel(const mobi_mt_pair* __restrict__ pairs, int n_pairs,
+                                                              const mobi_mt_chunk* __restrict__ chunks, int n_chunks, float w) {
   const int tid = threadIdx.x;
   for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
     mobi_mt_pair t;
@@ -180,11 +194,15 @@ __global__ __launch_bounds__(kMtBlock) void ema_multi_kernel(const mobi_mt_pair*
     const int head = same && ph < len ? ph : len;
     const int nvec = (len - head) >> 2, tail0 = head + (nvec << 2);
     auto one = [&](int i) {
-      const float ai = a[i], bi = b[i];
-      if (OP == MOBI_MT_EMA) {
-        b[i] = ema_update(bi, ai, omd);
+      const float ai = a[i];
+      if (OP == kPairAssign) {
+        b[i] = w * ai;
+      } else if (OP == kPairAccum) {
+        b[i] = accum_update(b[i], ai, w);
+      } else if (OP == kPairEma) {
+        b[i] = ema_update(b[i], ai, w);
       } else {
-        a[i] = bi;
+        a[i] = b[i];
         b[i] = ai;
       }
     };
@@ -195,14 +213,20 @@ __global__ __launch_bounds__(kMtBlock) void ema_multi_kernel(const mobi_mt_pair*
 #pragma unroll 4
     for (int i = tid; i < nvec; i += kMtBlock) {
       const f32x4 aq = av[i];
-      f32x4 bq = bv[i];
-      if (OP == MOBI_MT_EMA) {
+      if (OP == kPairAssign) {                       // b is not read
+        f32x4 bq;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) bq[j] = ema_update(bq[j], aq[j], omd);
+        for (int j = 0; j < 4; ++j) bq[j] = w * aq[j];
         bv[i] = bq;
-      } else {
+      } else if (OP == kPairSwap) {
+        const f32x4 bq = bv[i];
         av[i] = bq;
         bv[i] = aq;
+      } else {
+        f32x4 bq = bv[i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bq[j] = OP == kPairEma ? ema_update(bq[j], aq[j], w) : accum_update(bq[j], aq[j], w);
+        bv[i] = bq;
       }
     }
   }
@@ -258,11 +282,24 @@ extern "C" int mobi_ema_multi(const mobi_mt_pair* pairs, int32_t n_pairs, const 
                               float one_minus_decay, int32_t op, void* stream) {
   if (!pairs || !chunks || n_pairs <= 0 || n_chunks <= 0 || (op != MOBI_MT_EMA && op != MOBI_MT_SWAP)) return MOBI_ERR_ARG;
   if (op == MOBI_MT_EMA)
-    hipLaunchKernelGGL(ema_multi_kernel<MOBI_MT_EMA>, dim3(mt_grid(n_chunks)), dim3(kMtBlock), 0, ST(stream), pairs, n_pairs, chunks,
+    hipLaunchKernelGGL(pair_multi_kernel<kPairEma>, dim3(mt_grid(n_chunks)), dim3(kMtBlock), 0, ST(stream), pairs, n_pairs, chunks,
                        n_chunks, one_minus_decay);
   else
-    hipLaunchKernelGGL(ema_multi_kernel<MOBI_MT_SWAP>, dim3(mt_grid(n_chunks)), dim3(kMtBlock), 0, ST(stream), pairs, n_pairs, chunks,
+    hipLaunchKernelGGL(pair_multi_kernel<kPairSwap>, dim3(mt_grid(n_chunks)), dim3(kMtBlock), 0, ST(stream), pairs, n_pairs, chunks,
                        n_chunks, one_minus_decay);
+  MOBI_CHECK_LAUNCH();
+  return MOBI_OK;
+}
+
+extern "C" int mobi_accum_multi(const mobi_mt_pair* pairs, int32_t n_pairs, const mobi_mt_chunk* chunks, int32_t n_chunks, float w,
+                                int32_t op, void* stream) {
+  if (!pairs || !chunks || n_pairs <= 0 || n_chunks <= 0 || (op != MOBI_MT_ACCUM && op != MOBI_MT_ASSIGN)) return MOBI_ERR_ARG;
+  if (op == MOBI_MT_ACCUM)
+    hipLaunchKernelGGL(pair_multi_kernel<kPairAccum>, dim3(mt_grid(n_chunks)), dim3(kMtBlock), 0, ST(stream), pairs, n_pairs, chunks,
+                       n_chunks, w);
+  else
+    hipLaunchKernelGGL(pair_multi_kernel<kPairAssign>, dim3(mt_grid(n_chunks)), dim3(kMtBlock), 0, ST(stream), pairs, n_pairs, chunks,
+                       n_chunks, w);
   MOBI_CHECK_LAUNCH();
   return MOBI_OK;
 }

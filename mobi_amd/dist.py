@@ -111,3 +111,59 @@ def allreduce_gradients(grads: Dict[str, torch.Tensor], bucket_bytes: int = 256 
             grads[k].copy_(flat[off:off + n].view_as(grads[k]))
             off += n
     return grads
+
+
+def gradient_bucket_layout(numels: Dict[str, int], bucket_bytes: int = 256 << 20):
+    """Where a gradient accumulator keeps every tensor (`train.GradAccumulator`): ({name: (bucket, offset, numel)}, [bucket
+    length]), offsets and lengths in fp32 elements.  Names in sorted order, cut into buckets exactly where `allreduce_gradients`
+    cuts the same names and sizes (a tensor opens a new bucket when the bytes of the tensors already in this one plus its own
+    would exceed `bucket_bytes`; a tensor larger than that has a bucket to itself); inside a bucket every tensor starts on a
+    16-byte boundary (the multi-tensor kernels' 16-byte path), the padding is not counted by the cut.  Pure: no tensors."""
+    layout, lengths = {}, []
+    size = at = 0
+    for name in sorted(numels):
+        n = int(numels[name])
+        assert n > 0, name
+        if lengths and size + n * 4 > bucket_bytes:
+            lengths[-1] = at
+            lengths.append(0)
+            size = at = 0
+        elif not lengths:
+            lengths.append(0)
+        layout[name] = (len(lengths) - 1, at, n)
+        size += n * 4
+        at = (at + n + 3) // 4 * 4
+    if lengths:
+        lengths[-1] = at
+    return layout, lengths
+
+
+def allreduce_accumulated(buckets: List[torch.Tensor], layout: Dict[str, Tuple[int, int, int]], seen, average: bool = True) -> List[str]:
+    """The gradient collective of an ACCUMULATED window, once per optimizer step (DDP's `no_sync` pattern): `buckets` are the
+    accumulator's flat fp32 buffers, `layout` their `gradient_bucket_layout`, `seen` the names THIS rank accumulated a gradient
+    for in the window (draws are per process: a rank whose micro-batches were all conditional never saw `bbox_uncond_vector`).
+    One MAX all-reduce of a presence mask over the sorted names gives every rank the same set; a tensor some rank saw and this
+    one did not is zero-filled here (what DDP sums for a parameter a rank's graph did not reach); then every bucket is ONE
+    all-reduce IN PLACE and is divided by the world size -- the arithmetic of `allreduce_gradients` without its pack and
+    copy-back.  A tensor NO rank saw keeps whatever its region held and is not returned: the caller leaves it out of the step.
+    The layout is a function of the optimizer's names: `check_same_layout` is exchanged where the accumulator is built, not here.
+    -> the globally present names, sorted.  CPU tensors under gloo, device tensors under RCCL."""
+    names = sorted(layout)
+    seen = set(seen)
+    if not seen <= set(names):
+        raise ValueError(f"names outside the layout: {sorted(seen - set(names))[:3]}")
+    rank, ws = world()
+    if ws == 1:
+        return [k for k in names if k in seen]
+    mask = torch.tensor([1 if k in seen else 0 for k in names], dtype=torch.int32, device=buckets[0].device)
+    dist.all_reduce(mask, op=dist.ReduceOp.MAX)
+    present = [k for k, have in zip(names, mask.tolist()) if have]
+    for k in present:
+        if k not in seen:
+            b, off, n = layout[k]
+            buckets[b][off:off + n].zero_()
+    for flat in buckets:
+        dist.all_reduce(flat, op=dist.ReduceOp.SUM)
+        if average:
+            flat /= ws
+    return present

@@ -619,6 +619,28 @@ def multi_tensor_chunk_map(numels, chunk=None):
     return cmap
 
 
+class _PointerTable:
+    """A table of `count` rows of `width` 8-byte fields whose device copy the multi-tensor kernels read and of which ONE column
+    changes from call to call (this step's gradient pointers): the rows live in pinned host memory, `write_column` rewrites the
+    column and copies the table to the device on the current stream.  The host rows are not rewritten before the previous copy
+    has completed: `write_column` waits on that copy's event first (already signalled where a step read a result back)."""
+
+    def __init__(self, count, width, device):
+        import numpy as np
+        self._host = torch.empty(count * width * 8, dtype=torch.uint8).pin_memory()
+        self.rows = self._host.numpy().view(np.int64).reshape(count, width)
+        self.device_rows = torch.empty(self._host.numel(), dtype=torch.uint8, device=device)
+        self._copied = None
+
+    def write_column(self, col, values):
+        if self._copied is not None:
+            self._copied.synchronize()
+        self.rows[:, col] = values
+        self.device_rows.copy_(self._host, non_blocking=True)
+        self._copied = torch.cuda.Event()
+        self._copied.record()
+
+
 class MultiTensorList:
     """The device-resident tables `grad_stats` / `adamw_multi` walk: {param, grad, exp_avg, exp_avg_sq, n} per tensor and the
     chunk map {element offset, tensor index}.  Parameters and moments are fixed at construction (stable pointers, uploaded once
@@ -636,18 +658,18 @@ class MultiTensorList:
         self.device, self.count = params[0].device, len(params)
         self._keep = (list(params), list(exp_avgs), list(exp_avg_sqs))
         self.numels = [p.numel() for p in params]
-        self._host = torch.empty(self.count * C.sizeof(_lib.MtTensor), dtype=torch.uint8).pin_memory()
-        self._rows = self._host.numpy().view(np.int64).reshape(self.count, 5)      # MtTensor: four pointers and n, 8 bytes each
+        assert C.sizeof(_lib.MtTensor) == 5 * 8                                    # MtTensor: four pointers and n, 8 bytes each
+        self._table = _PointerTable(self.count, 5, self.device)
         for col, ts in enumerate((params, None, exp_avgs, exp_avg_sqs)):
-            self._rows[:, col] = 0 if ts is None else [t_.data_ptr() for t_ in ts]
-        self._rows[:, 4] = self.numels
+            self._table.rows[:, col] = 0 if ts is None else [t_.data_ptr() for t_ in ts]
+        self._table.rows[:, 4] = self.numels
         cmap = multi_tensor_chunk_map(self.numels)
         self.n_chunks = len(cmap)
         self.chunks = torch.from_numpy(cmap.view(np.uint8)).to(self.device)        # (a blocking copy, once)
-        self.tensors = torch.empty(self._host.numel(), dtype=torch.uint8, device=self.device)
+        self.tensors = self._table.device_rows
         self.workspace = torch.empty(lib.mobi_multi_tensor_workspace_bytes(None) // 8, dtype=torch.float64, device=self.device)
         self.record = torch.zeros(C.sizeof(_lib.GradStatsRecord) // 8, dtype=torch.int64, device=self.device)
-        self._grads, self._copied = None, None
+        self._grads = None
 
     def set_grads(self, grads):
         """grads: one fp32 tensor per listed parameter, of its numel (kept alive until the next call)."""
@@ -655,12 +677,7 @@ class MultiTensorList:
         grads = [g.contiguous() for g in grads]
         for g, n in zip(grads, self.numels):
             assert _dev(g).dtype == torch.float32 and g.numel() == n
-        if self._copied is not None:
-            self._copied.synchronize()
-        self._rows[:, 1] = [g.data_ptr() for g in grads]
-        self.tensors.copy_(self._host, non_blocking=True)
-        self._copied = torch.cuda.Event()
-        self._copied.record()
+        self._table.write_column(1, [g.data_ptr() for g in grads])
         self._grads = grads
 
 
@@ -728,6 +745,49 @@ def swap_multi(pairs):
     lib = _lib.load()
     _lib.check(lib.mobi_ema_multi(_ptr(pairs.pairs), pairs.count, _ptr(pairs.chunks), pairs.n_chunks, 0.0, _lib.MT_SWAP,
                                   _stream()), "mobi_ema_multi")
+
+
+class MultiTensorAccumPairs:
+    """The tables `accum_multi` walks: {a, b, n} per tensor, b = the accumulator (stable pointers, written into the rows once,
+    like the chunk map), a = one micro-batch's gradient -- a fresh allocation every time, so `set_sources` sends the `a` column
+    through the pinned table of `MultiTensorList.set_grads` (`_PointerTable`)."""
+
+    def __init__(self, b_list):
+        import numpy as np
+        assert len(b_list) > 0
+        for b in b_list:
+            assert _dev(b).dtype == torch.float32 and b.is_contiguous() and b.numel() > 0 and b.device == b_list[0].device
+        self.device, self.count = b_list[0].device, len(b_list)
+        self._keep = list(b_list)
+        self.numels = [b.numel() for b in b_list]
+        assert C.sizeof(_lib.MtPair) == 3 * 8                                      # MtPair: two pointers and n, 8 bytes each
+        self._table = _PointerTable(self.count, 3, self.device)
+        self._table.rows[:, 0] = 0
+        self._table.rows[:, 1] = [b.data_ptr() for b in b_list]
+        self._table.rows[:, 2] = self.numels
+        cmap = multi_tensor_chunk_map(self.numels)
+        self.n_chunks = len(cmap)
+        self.chunks = torch.from_numpy(cmap.view(np.uint8)).to(self.device)        # (a blocking copy, once)
+        self.pairs = self._table.device_rows
+        self._sources = None
+
+    def set_sources(self, a_list):
+        """a_list: one fp32 tensor per accumulator, of its numel (kept alive until the next call)."""
+        assert len(a_list) == self.count
+        a_list = [a.contiguous() for a in a_list]
+        for a, n in zip(a_list, self.numels):
+            assert _dev(a).dtype == torch.float32 and a.numel() == n and a.device == self.device
+        self._table.write_column(0, [a.data_ptr() for a in a_list])
+        self._sources = a_list
+
+
+def accum_multi(table, w, op):
+    """One micro-batch into the accumulators of `table` (a MultiTensorAccumPairs after `set_sources`), one launch, IN PLACE on
+    b: op `_lib.MT_ACCUM` b <- b + (w * a), product and sum each rounded to fp32; `_lib.MT_ASSIGN` b <- w * a, b not read."""
+    lib = _lib.load()
+    assert table._sources is not None, "set_sources() first"
+    _lib.check(lib.mobi_accum_multi(_ptr(table.pairs), table.count, _ptr(table.chunks), table.n_chunks, float(w), int(op),
+                                    _stream()), "mobi_accum_multi")
 
 
 def geglu_fwd(pre):

@@ -543,3 +543,78 @@ class AdamW:
         if scaler is not None:
             scaler.update(False)
         return StepResult(False, norm, clip, scale)
+
+
+class GradAccumulator:
+    """Gradient accumulation over a window of `micro_batches` forward / backward passes per optimizer step (the reference's
+    `lightning.trainer.accumulate_grad_batches`, main.py:675-694): `add` after every `training_step(..., allreduce=False)`, `step`
+    after the last.  The accumulators are views of flat fp32 buffers -- one fp32 copy of `optimizer.params`, laid out by
+    `dist.gradient_bucket_layout` (sorted names, the buckets of `allreduce_gradients`, 16-byte aligned starts) -- and hold the MEAN
+    over the window: every micro-batch enters with the weight w = fp32(1 / micro_batches), in ONE launch (`mobi_accum_multi`), as
+    b <- w g for a name's first gradient of the window (the accumulator is not read: nothing of an earlier window, skipped or
+    not, is seen; no zero-fill) and b <- b + (w g) after -- two launches only where a micro-batch brings both new and known names
+    (a conditional draw after an unconditional one).  With more than one process the collective runs once per window, on the
+    buffers in place (`dist.allreduce_accumulated`).  inf / nan of any micro-batch survive the sums; `step_scaled` finds them."""
+
+    def __init__(self, optimizer, micro_batches, bucket_bytes=256 << 20):
+        import numpy as np
+        from . import dist as mdist
+        if int(micro_batches) != micro_batches or micro_batches < 1:
+            raise ValueError(f"micro_batches must be a positive integer, not {micro_batches!r}")
+        self.optimizer, self.micro_batches = optimizer, int(micro_batches)
+        self.weight = float(np.float32(1.0) / np.float32(self.micro_batches))
+        self.names = sorted(optimizer.params)
+        numels = {k: optimizer.params[k].numel() for k in self.names}
+        self.layout, lengths = mdist.gradient_bucket_layout(numels, bucket_bytes)
+        device = optimizer.params[self.names[0]].device
+        mdist.check_same_layout(self.names, [numels[k] for k in self.names], device)      # once: the layout cannot diverge later
+        self.buckets = [torch.zeros(n, dtype=torch.float32, device=device) for n in lengths]
+        self.views = {k: self.buckets[b][off:off + n].view(optimizer.params[k].shape) for k, (b, off, n) in self.layout.items()}
+        self._tables = {}                             # per tuple of names, as AdamW._multi
+        self._clear()
+
+    def _clear(self):
+        self._seen, self._adds, self._scale = set(), 0, None
+
+    def _launch(self, names, grads, op):
+        if not names:
+            return
+        table = self._tables.get(names)
+        if table is None:
+            table = self._tables[names] = ops.MultiTensorAccumPairs([self.views[k] for k in names])
+        table.set_sources([grads[k].reshape(self.views[k].shape) for k in names])
+        ops.accum_multi(table, self.weight, op)
+
+    def add(self, grads, scale=1.0):
+        """grads: {name: fp32 tensor} of one micro-batch (`model.adapter_grads`: any subset of the optimizer's names), still
+        multiplied by `scale` (`model.adapter_grads_scale`) -- the same for every micro-batch of a window."""
+        from ._lib import MT_ACCUM, MT_ASSIGN
+        if self._adds >= self.micro_batches:
+            raise RuntimeError(f"add() number {self._adds + 1} in a window of {self.micro_batches} micro-batches: step() first")
+        unknown = [k for k in grads if k not in self.views]
+        if unknown:
+            raise KeyError(f"gradients of tensors the optimizer does not hold: {unknown[:3]}")
+        if self._adds and float(scale) != self._scale:
+            raise ValueError(f"this micro-batch's gradients carry the loss scale {scale!r}, the window's first {self._scale!r}")
+        first = tuple(k for k in self.names if k in grads and k not in self._seen)
+        again = tuple(k for k in self.names if k in grads and k in self._seen)
+        self._launch(first, grads, MT_ASSIGN)
+        self._launch(again, grads, MT_ACCUM)
+        self._seen.update(first)
+        self._adds, self._scale = self._adds + 1, float(scale)
+
+    def step(self, scaler=None, max_norm=None):
+        """The optimizer step of the window: `optimizer.step_scaled` on the accumulators of every tensor some rank saw (a tensor
+        nobody saw is left out and so left alone -- no weight decay, no decay of its moments), after the one collective of the
+        window where there is more than one process.  The window is cleared whether or not the step was skipped.  -> StepResult."""
+        from . import dist as mdist
+        if self._adds != self.micro_batches:
+            raise RuntimeError(f"step() after {self._adds} of {self.micro_batches} micro-batches")
+        want = 1.0 if scaler is None else float(scaler.scale)
+        if self._scale != want:
+            raise ValueError(f"the window's gradients carry the loss scale {self._scale!r}, the step would divide by {want!r}")
+        try:
+            present = mdist.allreduce_accumulated(self.buckets, self.layout, self._seen)
+            return self.optimizer.step_scaled({k: self.views[k] for k in present}, scaler=scaler, max_norm=max_norm)
+        finally:
+            self._clear()

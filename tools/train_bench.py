@@ -2,12 +2,15 @@
 """Time one training step of the adapter parameters (mobi_amd/train.py: forward with a tape + the backward pass through the
 whole UNet + AdamW on the 432 adapter tensors) -- informational: the backward kernels are a first slice, not tuned.
 
-    python tools/train_bench.py [--mc 320] [--side 32] [--n 4] [--dtype bf16] [--iters 3] [--scaler] [--ema]
+    python tools/train_bench.py [--mc 320] [--side 32] [--n 4] [--dtype bf16] [--iters 3] [--scaler] [--ema] [--accumulate K]
 
 --scaler: the gradients stay multiplied by a `train.GradScaler`'s scale and `AdamW.step_scaled` (two multi-tensor launches + one
 read-back) replaces the per-tensor unscale and update launches; `--max-norm` adds gradient-norm clipping to it.
 --ema: EMA shadows of every `requires_grad` tensor of the UNet (`ldm.modules.ema.LitEma`, what `LatentDiffusion(use_ema=True)`
-keeps) and their update inside the timed step, after the optimizer's (what `on_train_batch_end` calls: one `mobi_ema_multi` launch)."""
+keeps) and their update inside the timed step, after the optimizer's (what `on_train_batch_end` calls: one `mobi_ema_multi` launch).
+--accumulate K: a timed iteration is K forward / backward passes, each added to a `train.GradAccumulator` (one `mobi_accum_multi`
+launch), plus ONE optimizer step on the accumulated mean (`GradAccumulator.step` -> `AdamW.step_scaled`); the time printed is per
+optimizer step."""
 import argparse
 import math
 import os
@@ -33,6 +36,7 @@ def main():
     ap.add_argument("--scaler", action="store_true")
     ap.add_argument("--max-norm", type=float, default=None)
     ap.add_argument("--ema", action="store_true")
+    ap.add_argument("--accumulate", type=int, default=0)
     a = ap.parse_args()
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float16
     mobi_amd.set_engine_dtype(dt)
@@ -58,9 +62,25 @@ def main():
     if scaler is not None:
         scaler.first_use(noise.numel())
 
+    acc = train.GradAccumulator(opt, a.accumulate) if a.accumulate else None
+    static = 1.0 if dt == torch.bfloat16 else 2.0 ** round(math.log2(noise.numel() / 4))
+
     def step(profile=False):
         if profile:
             ops.set_profiler(sink)
+        if acc is not None:
+            for _ in range(a.accumulate):
+                if scaler is not None:
+                    loss, grads = train.loss_and_gradients(net, x, t, ctx, noise, loss_scale=scaler.scale, unscale=False)
+                else:
+                    loss, grads = train.loss_and_gradients(net, x, t, ctx, noise, loss_scale=static)
+                grads.pop("__dcontext__", None)
+                acc.add(grads, scale=1.0 if scaler is None else scaler.scale)
+            acc.step(scaler=scaler, max_norm=a.max_norm)
+            if ema is not None:
+                ema(net)
+            ops.set_profiler(None)
+            return loss
         if scaler is not None:
             loss, grads = train.loss_and_gradients(net, x, t, ctx, noise, loss_scale=scaler.scale, unscale=False)
             grads.pop("__dcontext__", None)
@@ -69,7 +89,7 @@ def main():
                 ema(net)
             ops.set_profiler(None)
             return loss
-        loss, grads = train.loss_and_gradients(net, x, t, ctx, noise, loss_scale=1.0 if dt == torch.bfloat16 else 2.0 ** round(math.log2(noise.numel() / 4)))
+        loss, grads = train.loss_and_gradients(net, x, t, ctx, noise, loss_scale=static)
         grads.pop("__dcontext__", None)
         opt.step(grads)
         if ema is not None:
@@ -92,6 +112,9 @@ def main():
         n_ema = sum(b.numel() for b in ema.buffers()) - 2
         print(f"--ema: shadows of {len(list(ema.buffers())) - 2} tensors / {n_ema / 1e6:.1f} M parameters ({n_ema * 4 / 2**30:.2f} GiB), "
               f"{int(ema.num_updates)} updates")
+    if acc is not None:
+        print(f"--accumulate: {a.accumulate} micro-batches of {a.n} per optimizer step, accumulators {sum(b.numel() for b in acc.buckets) * 4 / 2**30:.2f} GiB "
+              f"in {len(acc.buckets)} buckets; the time below is per optimizer step")
     if scaler is not None:
         print(f"--scaler: loss scale {scaler.scale:g}, max_norm {a.max_norm}")
     print(f"training step, UNet model_channels {a.mc}, latent {a.side}x{a.side}, UNet batch {a.n}, {a.dtype}: {dt_s * 1e3:.1f} ms "
