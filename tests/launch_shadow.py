@@ -23,6 +23,15 @@ While a shadow runs, `mobi_amd._lib.load` returns a LibCensus that counts every 
 `census_failures()` lists a launching entry point called more often than the shadow judged its kind, and any entry point that
 is neither shadowed nor query-only (LAUNCH_KINDS, QUERY_SUFFIXES): a new unwrapped launch cannot slip past.
 
+`LaunchShadow(monkeypatch, extra=EXTRA_KINDS)` (or a subset) also wraps the entry points the conditioning producer and the
+realism networks add (mobi_amd/ldm/modules/encoders/modules.py, mobi_amd/realism.py): skinny_linear (one ops call makes
+ceil(m / 16) library calls, all counted), layernorm_rows_f32, linear_f32, quick_gelu, image_normalize, maxpool3s2, add,
+lpips_distance, row_cosine, feature_moments, frd_input and band_mean, each against the fp64 (or, where the contract is
+bit-exact, the torch) restatement its own unit test uses and within that test's bound; quick_gelu has no unit test: its output is
+x sigmoid(1.702 x) in fp32 rounded once to T, so its rel-L2 AND its worst tile are bounded by the unit roundoff of T.  Without
+`extra` the wrapped set is the UNet's and the VAEs' (WRAPPED), as before.  An igemm with `leaky` (MOBI_EPI_LEAKY_RELU) is judged
+like any igemm: leaky_relu(., 0.1) after bias and rowvec, before the residual.
+
 Nothing here calls a `mobi_*` entry point: the references are torch float64 (matmul per tap, attention per image and head).
 """
 import math
@@ -59,16 +68,34 @@ BOUND_LINCOMB = 1e-6            # test_sampler_arithmetic_bit_exact: lincomb4 ag
 BOUND_SMALL_COUT = 2e-5         # test_conv_small_cout_matrix_core_form: fp32 NCHW output of 16-bit operands
 BOUND_SMALL_CIN_F32 = 2e-6      # test_small_convs: conv_small_cin with out_f32_nchw
 
+BOUND_SKINNY = 2e-6             # test_skinny_linear_and_timestep_embedding: against fp64, no activation / GELU behind
+BOUND_SKINNY_SILU = 2e-5        # the same test's SiLU form
+BOUND_F32_ROWS = 2e-6           # TOL_F32 of tests/test_gpu_norm_stats.py (layernorm_rows_f32); test_linear_f32
+BOUND_LPIPS_DISTANCE = 1e-6     # test_layer_distance_against_fp64: max relative per pair
+BOUND_ROW_COSINE = 1e-6         # test_row_cosine_against_fp64: |d| / max(|ref|, 1)
+BOUND_MOMENTS = 1e-15           # test_moments_against_fp64_and_reproducible (fp64 sums)
+BOUND_BAND_MEAN = 4.5e-7        # test_band_mean_against_fp64: max |d| / max |ref|
+UNIT_ROUNDOFF = {torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}      # quick_gelu: one rounding of an fp32 value to T
+QUICK_GELU_ALPHA = 1.702
+
 # entry points of the library that launch a kernel -> the shadow kind that judges each call
 LAUNCH_KINDS = {"mobi_igemm": "igemm", "mobi_igemm_finish": "split_finish", "mobi_groupnorm": "groupnorm",
                 "mobi_layernorm": "layernorm", "mobi_attention": "attention", "mobi_ctx_attention": "ctx_attention",
                 "mobi_ff_geglu": "ff_geglu", "mobi_two_key_adapter": "two_key_adapter", "mobi_softmax_rows": "softmax_rows",
                 "mobi_split_f32": "split_f32", "mobi_trunk_add": "trunk_add", "mobi_lincomb4": "lincomb4",
                 "mobi_conv_small_cout": "conv_small_cout", "mobi_conv_small_cin": "conv_small_cin",
-                "mobi_pack_nchw_sources": "pack_sources"}
+                "mobi_pack_nchw_sources": "pack_sources",
+                # the conditioning producer's and the realism networks' (LaunchShadow(extra=...))
+                "mobi_skinny_linear": "skinny_linear", "mobi_layernorm_rows_f32": "layernorm_rows_f32",
+                "mobi_linear_f32": "linear_f32", "mobi_quick_gelu": "quick_gelu", "mobi_image_normalize": "image_normalize",
+                "mobi_maxpool3s2": "maxpool3s2", "mobi_add": "add", "mobi_lpips_distance": "lpips_distance",
+                "mobi_row_cosine": "row_cosine", "mobi_feature_moments": "feature_moments", "mobi_frd_input": "frd_input",
+                "mobi_band_mean": "band_mean"}
+EXTRA_KINDS = ("skinny_linear", "layernorm_rows_f32", "linear_f32", "quick_gelu", "image_normalize", "maxpool3s2", "add",
+               "lpips_distance", "row_cosine", "feature_moments", "frd_input", "band_mean")
 # entry points that answer a question and launch nothing (mobi_tile_weights: the load-time weight image of a pack)
 QUERY_SUFFIXES = ("_workspace_bytes", "_plan_splits", "_slab_count", "_kernel_variant", "_takes_split", "_sync_bytes",
-                  "_supported", "_fuses_ln", "_packed_bytes", "_weight_bytes")
+                  "_supported", "_fuses_ln", "_packed_bytes", "_weight_bytes", "_ws_floats")
 QUERY_NAMES = ("mobi_tile_weights", "mobi_error_string", "mobi_build_info", "mobi_abi_version", "mobi_struct_size")
 
 
@@ -201,6 +228,14 @@ def _snap(t):
     return None if t is None else t.detach().clone()
 
 
+def _tag_int(tag, key, default):
+    """The integer after `key=` in a profiler tag (ops._Timed), or `default`."""
+    for part in tag.split():
+        if part.startswith(key + "="):
+            return int(part[len(key) + 1:])
+    return default
+
+
 def _same(a, b):
     return a.shape == b.shape and torch.equal(_bits(a.contiguous()), _bits(b.contiguous()))
 
@@ -218,7 +253,8 @@ def _chunks(total, rows, per):
 
 def igemm_reference(op, rows=None, dev=None):
     """mobi_igemm's contract: out[m] = epilogue(scale * sum_taps A_tap[m] W_tap^T (+ bias) (+ rowvec[image]) (+ residual[m])),
-    the LayerNorm fold as ((x - mean) rstd) W'^T + bias, GEGLU as value * gelu_erf(gate) of the packed row pairs.
+    the LayerNorm fold as ((x - mean) rstd) W'^T + bias, GEGLU as value * gelu_erf(gate) of the packed row pairs,
+    MOBI_EPI_LEAKY_RELU (op["leaky"]) as leaky_relu(., 0.1) after bias and rowvec and before the residual.
     -> fp64 [len(rows), cout] (or [images, hout * wout, cout] for rows=None)."""
     dev = op["x"].device if dev is None else dev
     to = lambda t: None if t is None else t.to(dev)
@@ -266,6 +302,8 @@ def igemm_reference(op, rows=None, dev=None):
             v = (t[:, :, 0] * F.gelu(t[:, :, 1])).reshape(r.numel(), cout)
         if rowvec is not None:
             v = v + rowvec[img]
+        if op.get("leaky"):
+            v = F.leaky_relu(v, 0.1)
         if res is not None:
             v = v + res[r]
         outs.append(v)
@@ -470,9 +508,13 @@ class LaunchShadow:
     WRAPPED = ("igemm", "groupnorm", "layernorm", "attention", "ctx_attention", "ff_geglu", "two_key_adapter", "softmax_rows",
                "split_f32", "trunk_add", "lincomb4", "conv_small_cout", "conv_small_cin", "pack_sources")
 
-    def __init__(self, monkeypatch, verbose=False, label="", cpu_check=True, seed=0):
+    def __init__(self, monkeypatch, verbose=False, label="", cpu_check=True, seed=0, extra=()):
         from mobi_amd import ops
         self.ops, self.mp, self.verbose, self.label, self.cpu_check = ops, monkeypatch, verbose, label, cpu_check
+        unknown = [k for k in extra if k not in EXTRA_KINDS]
+        if unknown:
+            raise ValueError(f"launch shadow: no extra kinds {unknown} (EXTRA_KINDS)")
+        self.wrapped = self.WRAPPED + tuple(k for k in EXTRA_KINDS if k in extra)
         self.records, self.failures, self.counts, self.calls = [], [], {}, {}
         self.cpu_checked = set()
         self.pending = {}
@@ -501,11 +543,11 @@ class LaunchShadow:
         else:
             self.sink = ops._PROFILE
         from mobi_amd import _lib
-        orig = {k: getattr(ops, k) for k in self.WRAPPED}
+        orig = {k: getattr(ops, k) for k in self.wrapped}
         orig_finish = ops.Deferred.finish
         self.orig = orig
         sh = self
-        for k in self.WRAPPED:
+        for k in self.wrapped:
             self.mp.setattr(ops, k, (lambda name: lambda *a, **kw: getattr(sh, "_" + name)(orig[name], *a, **kw))(k))
         self.mp.setattr(ops.Deferred, "finish", lambda d: sh._finish(orig_finish, d))
         census = LibCensus(_lib.load(), self.calls)
@@ -525,8 +567,8 @@ class LaunchShadow:
                 return rec[5]
         return ""
 
-    def _count(self, kind):
-        self.counts[kind] = self.counts.get(kind, 0) + 1
+    def _count(self, kind, calls=1):
+        self.counts[kind] = self.counts.get(kind, 0) + calls
 
     def _fail(self, msg):
         self.failures.append(f"{self.label} {msg}")
@@ -549,26 +591,26 @@ class LaunchShadow:
         if not err <= CPU_AGREE:
             self._fail(f"{key}: device fp64 reference disagrees with the CPU on {rows.numel()} rows: {err:.3e}")
 
-    def _judge(self, kind, tag, got, ref, bound, extra="", form=None):
+    def _judge(self, kind, tag, got, ref, bound, extra="", form=None, tile_factor=TILE_FACTOR):
         res = compare(got, ref)
-        ok = passes(res, bound)
+        ok = res["finite"] and res["rel"] < bound and res["tile"] < tile_factor * bound
         rec = dict(kind=kind, tag=tag, bound=bound, extra=extra, form=form or {}, **res)
         self.records.append(rec)
         name = f"{kind} {tag} {extra}".strip()
         record(f"shadow {self.label} {name}", res["rel"], bound)
-        record(f"shadow {self.label} {name} worst_tile", res["tile"], TILE_FACTOR * bound)
+        record(f"shadow {self.label} {name} worst_tile", res["tile"], tile_factor * bound)
         if self.verbose:
             print(f"[shadow {self.label}] {kind:16s} {tag} {extra} rel={res['rel']:.3e} tile={res['tile']:.3e} "
                   f"at(img,row,col)={res['where']} bound={bound:.1e}{'' if ok else '  FAIL'}")
         if not ok:
             self._fail(f"{name}: rel-L2 {res['rel']:.3e}, worst tile {res['tile']:.3e} at {res['where']}, finite "
-                       f"{res['finite']} (bound {bound:.1e}, tile bound {TILE_FACTOR * bound:.1e})")
+                       f"{res['finite']} (bound {bound:.1e}, tile bound {tile_factor * bound:.1e})")
         return res
 
     # -- igemm ---------------------------------------------------------------------------------------------------------
     def _igemm(self, orig, x, pw, *, x2=None, stride=1, pad=None, upsample=False, hout=None, wout=None, rowvec=None,
                rowvec_has_bias=False, residual=None, out=None, out_mode=0, scale=1.0, weight_per_image=False,
-               w_group_stride=0, split_k=None, groups=1, defer=None):
+               w_group_stride=0, split_k=None, groups=1, defer=None, leaky=False):
         ops = self.ops
         x, x2, residual = ops.finished(x), ops.finished(x2), ops.finished(residual)
         if pw.k_order:
@@ -592,7 +634,7 @@ class LaunchShadow:
         op = dict(x=_snap(x), x2=_snap(x2), w=w, bias=pw.bias, kh=pw.kh, kw=pw.kw, stride=stride, pad_h=ph, pad_w=pw_,
                   upsample=upsample, hout=ho, wout=wo, cout=cout, n_packed=npk, groups=ref_groups, geglu=pw.geglu,
                   ln=pw.svec is not None, ln_eps=pw.ln_eps, scale=scale, rowvec=_snap(rowvec), rowvec_has_bias=rowvec_has_bias,
-                  residual=None if residual is None else residual.detach().reshape(n, ho * wo, cout).clone())
+                  residual=None if residual is None else residual.detach().reshape(n, ho * wo, cout).clone(), leaky=leaky)
         ins = [("x", x, op["x"]), ("x2", x2, op["x2"]), ("rowvec", rowvec, op["rowvec"])]
         in_place = residual is not None and out is not None and residual.data_ptr() == out.data_ptr()
         if residual is not None and not in_place:
@@ -602,7 +644,8 @@ class LaunchShadow:
         n0 = len(self.sink)
         y = orig(x, pw, x2=x2, stride=stride, pad=pad, upsample=upsample, hout=hout, wout=wout, rowvec=rowvec,
                  rowvec_has_bias=rowvec_has_bias, residual=residual, out=out, out_mode=out_mode, scale=scale, split_k=split_k,
-                 groups=groups, defer=defer, weight_per_image=weight_per_image, w_group_stride=w_group_stride)
+                 groups=groups, defer=defer, weight_per_image=weight_per_image, w_group_stride=w_group_stride,
+                 **({"leaky": True} if leaky else {}))
         torch.cuda.synchronize()
         self._count("igemm")
         tag = self._tag(n0, "igemm") + (" per_image" if weight_per_image else "")
@@ -619,7 +662,8 @@ class LaunchShadow:
             return y
         got = y.transpose(1, 2) if out_mode == ops.OUT_TRANSPOSED else y.reshape(n, ho * wo, cout)
         form = dict(per_image=weight_per_image, out_mode=out_mode, upsample=upsample, stride=stride, pad=(ph, pw_), hin=hin,
-                    win=win, hout=ho, wout=wo, cin=pw.cin, kh=pw.kh, kw=pw.kw, thin=self.thin.pop(x.data_ptr(), 0))
+                    win=win, hout=ho, wout=wo, cin=pw.cin, kh=pw.kh, kw=pw.kw, thin=self.thin.pop(x.data_ptr(), 0), leaky=leaky,
+                    residual=residual is not None, k=pw.kh * pw.kw * pw.cin, m=n * ho * wo, images=n, split=_tag_int(tag, "split", 1))
         self._judge("igemm", tag, got, ref, bound, form=form)
         return y
 
@@ -886,4 +930,234 @@ class LaunchShadow:
             self._fail(f"pack_sources {tag}: not the rounded sources followed by zeros, bit for bit")
         self.thin[y.data_ptr()] = len(srcs)
         self._judge("pack_sources", tag, y.reshape(1, -1, c_pad), F.pad(cat, (0, c_pad - c)).reshape(1, -1, c_pad), TOL[dtype])
+        return y
+
+    # -- the conditioning producer's and the realism networks' entry points (extra=...) ------------------------------------
+    def _judge_value(self, kind, tag, err, bound, finite=True, form=None):
+        """A launch whose unit test bounds one figure (a maximum over its outputs), not a rel-L2 over tiles."""
+        ok = finite and err <= bound
+        self.records.append(dict(kind=kind, tag=tag, bound=bound, extra="", form=form or {}, rel=err, tile=err, where=(0, 0, 0),
+                                 finite=finite))
+        record(f"shadow {self.label} {kind} {tag}", err, bound)
+        if self.verbose:
+            print(f"[shadow {self.label}] {kind:16s} {tag} err={err:.3e} bound={bound:.1e}{'' if ok else '  FAIL'}")
+        if not ok:
+            self._fail(f"{kind} {tag}: error {err:.3e}, finite {finite} (bound {bound:.1e})")
+
+    def _judge_exact(self, kind, tag, got, want, form=None):
+        """A launch whose contract is bit-exact: torch.equal against the torch restatement its unit test uses."""
+        ok = got.shape == want.shape and got.dtype == want.dtype and torch.equal(got, want)
+        self.records.append(dict(kind=kind, tag=tag, bound=0.0, extra="", form=form or {}, rel=0.0 if ok else float("inf"),
+                                 tile=0.0 if ok else float("inf"), where=(0, 0, 0), finite=bool(torch.isfinite(got).all())))
+        if self.verbose:
+            print(f"[shadow {self.label}] {kind:16s} {tag} bit-exact{'' if ok else '  FAIL'}")
+        if not ok:
+            diff = int((got != want).sum()) if got.shape == want.shape else -1
+            self._fail(f"{kind} {tag}: not the torch restatement bit for bit ({diff} elements differ)")
+
+    def _skinny_linear(self, orig, x, w, bias=None, pre_act=0, post_act=0, out=None):
+        xs, ws, bs = _snap(x), _snap(w), _snap(bias)
+        outside = OutsideView(out) if out is not None else None
+        y = orig(x, w, bias=bias, pre_act=pre_act, post_act=post_act, out=out)
+        torch.cuda.synchronize()
+        m, k = xs.shape
+        n = ws.shape[0]
+        self._count("skinny_linear", (m + 15) // 16)                  # one library call per 16 rows
+        tag = f"m={m} k={k} n={n} pre={pre_act} post={post_act} bias={int(bias is not None)}"
+        self._inputs_unchanged("skinny_linear " + tag, [("x", x, xs), ("weight", w, ws), ("bias", bias, bs)])
+        if outside is not None and not outside.unchanged():
+            self._fail(f"skinny_linear {tag}: wrote outside its out view")
+        act = {0: lambda t: t, 1: F.silu, 2: F.gelu}
+        ref = act[pre_act](xs.double()) @ ws.double().T
+        if bs is not None:
+            ref = ref + bs.double()
+        ref = act[post_act](ref)
+        bound = BOUND_SKINNY_SILU if 1 in (pre_act, post_act) else BOUND_SKINNY
+        self._judge("skinny_linear", tag, y.reshape(1, m, n), ref.reshape(1, m, n), bound,
+                    form=dict(m=m, k=k, n=n, remainder=m % 16, calls=(m + 15) // 16))
+        return y
+
+    def _layernorm_rows_f32(self, orig, x, gamma, beta, eps=1e-5):
+        xs, gs, bs = _snap(x), _snap(gamma), _snap(beta)
+        y = orig(x, gamma, beta, eps)
+        torch.cuda.synchronize()
+        self._count("layernorm_rows_f32")
+        tag = f"rows={xs.shape[0]} cols={xs.shape[1]}"
+        self._inputs_unchanged("layernorm_rows_f32 " + tag, [("x", x, xs), ("gamma", gamma, gs), ("beta", beta, bs)])
+        ref = layernorm_rows(xs, gs, bs, eps)
+        self._judge("layernorm_rows_f32", tag, y.reshape(1, *y.shape), ref.reshape(1, *ref.shape), BOUND_F32_ROWS)
+        return y
+
+    def _linear_f32(self, orig, x, w, bias=None):
+        xs, ws, bs = _snap(x), _snap(w), _snap(bias)
+        y = orig(x, w, bias)
+        torch.cuda.synchronize()
+        self._count("linear_f32")
+        tag = f"m={xs.shape[0]} k={xs.shape[1]} n={ws.shape[0]} bias={int(bias is not None)}"
+        self._inputs_unchanged("linear_f32 " + tag, [("x", x, xs), ("weight", w, ws), ("bias", bias, bs)])
+        ref = xs.double() @ ws.double().T
+        if bs is not None:
+            ref = ref + bs.double()
+        self._judge("linear_f32", tag, y.reshape(1, *y.shape), ref.reshape(1, *ref.shape), BOUND_F32_ROWS)
+        return y
+
+    def _quick_gelu(self, orig, x):
+        xs = _snap(x)
+        y = orig(x)
+        torch.cuda.synchronize()
+        self._count("quick_gelu")
+        c = xs.shape[-1]
+        tag = f"n={xs.numel()} c={c}"
+        self._inputs_unchanged("quick_gelu " + tag, [("x", x, xs)])
+        if y.shape != xs.shape or y.dtype != xs.dtype:
+            self._fail(f"quick_gelu {tag}: shape / dtype {tuple(y.shape)} {y.dtype}")
+            return y
+        x64 = xs.double()
+        ref = x64 * torch.sigmoid(QUICK_GELU_ALPHA * x64)
+        # one rounding of the fp32 value to T: every element within the unit roundoff, hence the whole tensor and every tile
+        self._judge("quick_gelu", tag, y.reshape(1, -1, c), ref.reshape(1, -1, c), UNIT_ROUNDOFF[xs.dtype], tile_factor=1.0,
+                    form=dict(n=xs.numel()))
+        return y
+
+    def _image_normalize(self, orig, x, shift, scale, dtype=None, nhwc_channels=0):
+        xs = _snap(x)
+        y = orig(x, shift, scale, dtype=dtype, nhwc_channels=nhwc_channels)
+        torch.cuda.synchronize()
+        self._count("image_normalize")
+        n, c, h, w = xs.shape
+        tag = f"n={n} c={c} hw={h}x{w} nhwc={nhwc_channels}"
+        self._inputs_unchanged("image_normalize " + tag, [("x", x, xs)])
+        sh = torch.tensor(shift, device=xs.device).view(1, c, 1, 1)
+        sc = torch.tensor(scale, device=xs.device).view(1, c, 1, 1)
+        want = (xs - sh) / sc
+        if nhwc_channels:
+            want = F.pad(want.to(dtype).permute(0, 2, 3, 1), (0, nhwc_channels - c)).contiguous()
+        self._judge_exact("image_normalize", tag, y, want, form=dict(nhwc=nhwc_channels))
+        return y
+
+    def _maxpool3s2(self, orig, x, relu=False):
+        xs = _snap(x)
+        y = orig(x, relu=relu)
+        torch.cuda.synchronize()
+        self._count("maxpool3s2")
+        tag = f"n={xs.shape[0]} hw={xs.shape[1]}x{xs.shape[2]} c={xs.shape[3]} relu={int(relu)}"
+        self._inputs_unchanged("maxpool3s2 " + tag, [("x", x, xs)])
+        src = torch.relu(xs) if relu else xs
+        want = F.max_pool2d(src.permute(0, 3, 1, 2).float(), 3, 2).to(xs.dtype).permute(0, 2, 3, 1).contiguous()
+        self._judge_exact("maxpool3s2", tag, y, want, form=dict(relu=relu))
+        return y
+
+    def _add(self, orig, a, b):
+        sa, sb = _snap(a), _snap(b)
+        y = orig(a, b)
+        torch.cuda.synchronize()
+        self._count("add")
+        tag = f"n={sa.numel()}"
+        self._inputs_unchanged("add " + tag, [("a", a, sa), ("b", b, sb)])
+        self._judge_exact("add", tag, y, (sa.float() + sb.float()).to(sa.dtype))
+        return y
+
+    def _lpips_distance(self, orig, feat, lin, out, eps=1e-10, relu_in_place=False):
+        fs, ls_, base = _snap(feat), _snap(lin), _snap(out)
+        outside = OutsideView(out)
+        y = orig(feat, lin, out, eps, relu_in_place=relu_in_place)
+        torch.cuda.synchronize()
+        self._count("lpips_distance")
+        n2, h, w, c = fs.shape
+        p = n2 // 2
+        tag = f"pairs={p} hw={h}x{w} c={c} relu_in_place={int(relu_in_place)}"
+        self._inputs_unchanged("lpips_distance " + tag, [("lin", lin, ls_)])
+        if not _same(feat, torch.relu(fs) if relu_in_place else fs):
+            self._fail(f"lpips_distance {tag}: the features are not " + ("relu(features) bit for bit" if relu_in_place else "unchanged"))
+        if not outside.unchanged():
+            self._fail(f"lpips_distance {tag}: wrote outside its out view")
+        f64 = torch.relu(fs.double()).permute(0, 3, 1, 2)
+
+        def unit(f):
+            return f / (torch.sqrt((f * f).sum(dim=1, keepdim=True)) + eps)
+        d = (unit(f64[:p]) - unit(f64[p:])).square() * ls_.double().view(1, -1, 1, 1)
+        want = base.double() + d.sum(1).mean(dim=(1, 2))
+        got = y.double()
+        err = (got - want).abs() / want.abs().clamp_min(1e-300)
+        err = torch.where((want == 0) & (got == 0), torch.zeros_like(err), err)
+        self._judge_value("lpips_distance", tag, float(err.max()), BOUND_LPIPS_DISTANCE, bool(torch.isfinite(got).all()),
+                          form=dict(relu_in_place=relu_in_place, pairs=p))
+        return y
+
+    def _row_cosine(self, orig, a, b, eps=1e-8, scale=1.0):
+        sa, sb = _snap(a), _snap(b)
+        y = orig(a, b, eps=eps, scale=scale)
+        torch.cuda.synchronize()
+        self._count("row_cosine")
+        tag = f"rows={sa.shape[0]} d={sa.shape[1]}"
+        self._inputs_unchanged("row_cosine " + tag, [("a", a, sa), ("b", b, sb)])
+        want = scale * F.cosine_similarity(sa.double(), sb.double(), dim=-1, eps=eps)
+        err = ((y.double() - want).abs() / want.abs().clamp_min(1.0)).max()
+        self._judge_value("row_cosine", tag, float(err), BOUND_ROW_COSINE, bool(torch.isfinite(y).all()))
+        return y
+
+    def _feature_moments(self, orig, feat, shift, sum_, cross=None):
+        fs, ss, s0, c0 = _snap(feat), _snap(shift), _snap(sum_), _snap(cross)
+        r = orig(feat, shift, sum_, cross)
+        torch.cuda.synchronize()
+        self._count("feature_moments")
+        rows, d = fs.shape
+        tag = f"rows={rows} d={d} shift={int(shift is not None)} cross={int(cross is not None)}"
+        self._inputs_unchanged("feature_moments " + tag, [("feat", feat, fs), ("shift", shift, ss)])
+        x = fs.double() if ss is None else fs.double() - ss
+        # increments against fp64, each relative to the size of what was summed (the shifted sum itself is near 0)
+        e_sum = float(((sum_ - s0) - x.sum(0)).abs().max() / x.abs().sum(0).max().clamp_min(1e-300))
+        finite = bool(torch.isfinite(sum_).all())
+        self._judge_value("feature_moments", tag + " sum", e_sum, BOUND_MOMENTS, finite, form=dict(shift=shift is not None))
+        if cross is not None:
+            want = x.T @ x
+            e_cross = float(((cross.reshape(d, d) - c0.reshape(d, d)) - want).abs().max() / want.abs().max().clamp_min(1e-300))
+            self._judge_value("feature_moments", tag + " cross", e_cross, BOUND_MOMENTS, bool(torch.isfinite(cross).all()),
+                              form=dict(shift=shift is not None))
+        return r
+
+    def _frd_input(self, orig, raw, dtype, hout=64, wout=1024, cpad=32, depth_min=1.4, depth_max=54.0):
+        from tests import frd_ref
+        rs = _snap(raw)
+        y = orig(raw, dtype, hout, wout, cpad, depth_min, depth_max)
+        torch.cuda.synchronize()
+        self._count("frd_input")
+        n = rs.shape[0]
+        tag = f"n={n} hw={rs.shape[2]}x{rs.shape[3]} -> {hout}x{wout}x{cpad}"
+        self._inputs_unchanged("frd_input " + tag, [("raw", raw, rs)])
+        if (depth_min, depth_max) != tuple(frd_ref.FRD_DEPTH):
+            self._fail(f"frd_input {tag}: depth range {(depth_min, depth_max)} is not the reference's {frd_ref.FRD_DEPTH}")
+            return y
+        want = torch.stack([frd_ref.prepare(v, hout, wout) for v in rs.cpu().double().numpy()])       # f32 [n, 5, hout, wout]
+        got = y.cpu()
+        g5 = got[..., :5].permute(0, 3, 1, 2)
+        bad = []
+        if tuple(got.shape) != (n, hout, wout, cpad) or got.dtype != dtype:
+            bad.append(f"shape / dtype {tuple(got.shape)} {got.dtype}")
+        elif bool(got[..., 5:].any()):
+            bad.append("the padding channels are not zero")
+        elif not torch.equal(~(g5 == -1).all(1), ~(want == -1).all(1)):
+            bad.append("the validity mask differs from the reference's")
+        ulps = float("inf")
+        if not bad:
+            wt = want.to(dtype)
+            ulp = torch.nextafter(wt.float().abs().to(dtype), torch.tensor(float("inf")).to(dtype)).float() - wt.float().abs()
+            ulps = float(((g5.float() - wt.float()).abs() / ulp).max())
+        for msg in bad:
+            self._fail(f"frd_input {tag}: {msg}")
+        self._judge_value("frd_input", tag, ulps, 1.0, bool(torch.isfinite(got.float()).all()))
+        return y
+
+    def _band_mean(self, orig, x, skip=None, bands=16):
+        xs, ss = _snap(x), _snap(skip)
+        y = orig(x, skip, bands)
+        torch.cuda.synchronize()
+        self._count("band_mean")
+        n, h, w, c = xs.shape
+        tag = f"n={n} hw={h}x{w} c={c} bands={bands} skip={int(skip is not None)}"
+        self._inputs_unchanged("band_mean " + tag, [("x", x, xs), ("skip", skip, ss)])
+        t = xs.double() if ss is None else xs.double() + ss.double()
+        want = t.permute(0, 3, 1, 2).reshape(n, c, bands, h // bands, w).mean((3, 4)).reshape(n, -1)
+        err = float((y.double() - want).abs().max() / want.abs().max().clamp_min(1e-300))
+        self._judge_value("band_mean", tag, err, BOUND_BAND_MEAN, bool(torch.isfinite(y).all()), form=dict(skip=skip is not None))
         return y

@@ -57,6 +57,23 @@ def _ln(x, sd, name, eps=1e-5):
     return F.layer_norm(x, x.shape[-1:], sd[name + ".weight"].to(x), sd[name + ".bias"].to(x), eps)
 
 
+def clip_layer(x, sd, pre, heads):
+    """One encoder layer (OpenAI's ResidualAttentionBlock with QuickGELU) on tokens x [N, T, width]; sd: HF-named tower
+    tensors, `pre` = "encoder.layers.<i>." -> [N, T, width] in x's type."""
+    n, t, width = x.shape
+    dh = width // heads
+
+    def lin(v, name):
+        return F.linear(v, sd[pre + name + ".weight"].to(v), sd[pre + name + ".bias"].to(v))
+
+    h = _ln(x, sd, pre + "layer_norm1")
+    q, k, v = (lin(h, f"self_attn.{m}_proj").view(n, t, heads, dh).transpose(1, 2) for m in "qkv")
+    att = torch.softmax((q * dh ** -0.5) @ k.transpose(-1, -2), dim=-1)
+    x = x + lin((att @ v).transpose(1, 2).reshape(n, t, width), "self_attn.out_proj")
+    h = lin(_ln(x, sd, pre + "layer_norm2"), "mlp.fc1")
+    return x + lin(h * torch.sigmoid(1.702 * h), "mlp.fc2")
+
+
 def clip_embed(images, sd, heads=None, dtype=torch.float64):
     """images [N, 3, S, S] in [0, 1]; sd: HF-named tower + `visual_projection.weight` -> [N, embed] (float64 by default)."""
     sd = {k[len("vision_model."):] if k.startswith("vision_model.") else k: v for k, v in sd.items()}
@@ -70,21 +87,9 @@ def clip_embed(images, sd, heads=None, dtype=torch.float64):
     cls = sd["embeddings.class_embedding"].to(x).expand(x.shape[0], 1, width)
     x = torch.cat([cls, x], 1) + sd["embeddings.position_embedding.weight"].to(x)
     x = _ln(x, sd, "pre_layrnorm")
-    n, t, _ = x.shape
-    dh = width // heads
     layers = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("encoder.layers."))
     for i in range(layers):
-        pre = f"encoder.layers.{i}."
-
-        def lin(v, name):
-            return F.linear(v, sd[pre + name + ".weight"].to(v), sd[pre + name + ".bias"].to(v))
-
-        h = _ln(x, sd, pre + "layer_norm1")
-        q, k, v = (lin(h, f"self_attn.{m}_proj").view(n, t, heads, dh).transpose(1, 2) for m in "qkv")
-        att = torch.softmax((q * dh ** -0.5) @ k.transpose(-1, -2), dim=-1)
-        x = x + lin((att @ v).transpose(1, 2).reshape(n, t, width), "self_attn.out_proj")
-        h = lin(_ln(x, sd, pre + "layer_norm2"), "mlp.fc1")
-        x = x + lin(h * torch.sigmoid(1.702 * h), "mlp.fc2")
+        x = clip_layer(x, sd, f"encoder.layers.{i}.", heads)
     pooled = _ln(x[:, 0], sd, "post_layernorm")
     return pooled @ sd["visual_projection.weight"].to(pooled).t()
 

@@ -542,6 +542,70 @@ def test_attention_strided_partner_and_spike(ops, dtype, tune):
 
 
 @pytest.mark.parametrize("dtype", DT)
+@pytest.mark.parametrize("nw", ["4", "8"])
+@pytest.mark.parametrize("heads,dh,t", [(16, 64, 257), (12, 64, 50)], ids=["vit_l14", "vit_b32"])
+def test_attention_tower_geometry(ops, dtype, nw, heads, dh, t, tune):
+    """The CLIP towers' call (ViT-L/14: 16 heads x 64, 257 tokens; ViT-B/32: 12 x 64, 50 tokens): q, k and v are the three thirds
+    of one stacked projection [n, T, 3 C] (row stride 3 C), V row-major, through 4-wave and 8-wave blocks, against fp64."""
+    n, c = 2, heads * dh
+    xf, xd = rnd(f"at.qkv{heads}.{t}", (n, t, 3 * c), dtype, 1.5)
+    tune.setenv("MOBI_ATTN_NW", nw)
+    keep = xd.clone()
+    y = ops.attention(xd[..., :c], xd[..., c:2 * c], xd[..., 2 * c:], heads, dh ** -0.5, v_rows=True)
+    sp = lambda z: z.double().reshape(n, t, heads, dh).permute(0, 2, 1, 3)
+    s = sp(xf[..., :c]) @ sp(xf[..., c:2 * c]).transpose(-1, -2) * dh ** -0.5
+    e = torch.exp(s - s.amax(dim=-1, keepdim=True))
+    ref = ((e @ sp(xf[..., 2 * c:])) / e.sum(dim=-1, keepdim=True)).permute(0, 2, 1, 3).reshape(n, t, c)
+    assert y.shape == (n, t, c) and y.is_contiguous() and bool(torch.isfinite(y).all())
+    assert torch.equal(xd, keep)
+    assert rel(y, ref) < TOL[dtype]
+    for i in range(n):                                       # each image and each head on its own (a head is 1 / heads of the norm)
+        for h in range(heads):
+            assert rel(y[i, :, h * dh:(h + 1) * dh], ref[i, :, h * dh:(h + 1) * dh]) < TOL[dtype], (i, h)
+
+
+QUICK_GELU_CAP = 8192 * 256 * 8                             # mobi_quick_gelu's grid: beyond it a thread strides over the tensor
+
+
+@pytest.mark.parametrize("dtype", DT)
+@pytest.mark.parametrize("n", [8, QUICK_GELU_CAP - 8, QUICK_GELU_CAP, QUICK_GELU_CAP + 8], ids=["8", "cap-8", "cap", "cap+8"])
+def test_quick_gelu(ops, dtype, n):
+    """mobi_quick_gelu against fp64 at, just below and just beyond its grid cap (the grid-stride branch): the output is
+    x sigmoid(1.702 x) in fp32 rounded once to T, so every element lies within the unit roundoff of T of the reference (plus one
+    subnormal step where T's subnormals round), and is finite -- at 0, +-6e-8, +-1, +-51.7 (where 1.702 x meets __expf's range),
+    +-1e4 and the largest finite T too."""
+    from mobi_amd import _lib
+    big = float(torch.finfo(dtype).max)
+    special = torch.tensor([0.0, 6e-8, -6e-8, 1.0, -1.0, 51.7, -51.7, 1e4, -1e4, big, -big, -0.0, 30.0, -30.0, 88.0, -88.0])
+    g = torch.Generator().manual_seed(n % 1000 + 1)
+    x = (torch.randn((n,), generator=g) * 3.0)
+    k = min(n, special.numel())
+    x[:k] = special[:k]
+    x[-8:] = special[5:13]                                   # the tensor's last vector: +-51.7, +-1e4, +-max, -0, 30
+    xd = x.to(dtype).cuda()
+    keep = xd.clone()
+    y = ops.quick_gelu(xd)
+    assert y.shape == xd.shape and y.dtype == dtype and torch.equal(xd, keep)
+    x64 = xd.double()
+    ref = x64 * torch.sigmoid(1.702 * x64)
+    u = 2.0 ** -11 if dtype == torch.float16 else 2.0 ** -8
+    step = 2.0 ** -24 if dtype == torch.float16 else 2.0 ** -133     # T's subnormal spacing
+    d = (y.double() - ref).abs()
+    slack = u * ref.abs() + step
+    worst = float((d / slack).max())
+    print(f"quick_gelu {dtype} n={n}: max |d| / (u |ref| + subnormal step) = {worst:.3f}")
+    assert bool(torch.isfinite(y).all())
+    assert bool((d <= slack).all()), (worst, int((d > slack).sum()), int(torch.argmax(d / slack)))
+    if n > QUICK_GELU_CAP:                                   # the 8 elements only the grid-stride round writes
+        assert bool(torch.isfinite(y[-8:]).all()) and bool((d[-8:] <= slack[-8:]).all()), (y[-8:], ref[-8:])
+        assert float(y[-1]) == float(torch.tensor(30.0).to(dtype)) and float(y[-2]) == 0.0
+    if n == 8:                                               # a count that is no multiple of 8 is refused, not rounded
+        lib = _lib.load()
+        with pytest.raises(_lib.EngineError):
+            _lib.check(lib.mobi_quick_gelu(ops._ptr(xd), ops._ptr(y), 12, ops._dt(dtype), ops._stream()), "mobi_quick_gelu")
+
+
+@pytest.mark.parametrize("dtype", DT)
 @pytest.mark.parametrize("tk", [1, 2, 8])
 def test_ctx_attention(ops, dtype, tk):
     n, t, heads, dh = 3, 70, 8, 40

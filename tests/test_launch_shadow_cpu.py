@@ -386,3 +386,48 @@ def test_census_reports_an_unshadowed_launch():
     lib.mobi_nearest_resize(None)
     bad = sh.census_failures()
     assert any(m.startswith("mobi_igemm:") for m in bad) and any(m.startswith("mobi_nearest_resize:") for m in bad), bad
+
+
+def test_igemm_reference_leaky_is_before_the_residual():
+    """MOBI_EPI_LEAKY_RELU: leaky_relu(conv + bias + rowvec, 0.1) + residual; on the paired-width view a 3 x 2 launch with an
+    explicit output size is the stride-(1, 2) convolution realism.stride2_weight rewrites."""
+    from mobi_amd.realism import stride2_weight
+    x, wt, b = _rand((2, 32, 6, 8), 81), _rand((24, 32, 3, 3), 82, 0.1), _rand((24,), 83)
+    rv, res = _rand((2, 24), 84), _rand((2, 6, 8, 24), 85)
+    op = dict(_op(_nhwc(x), wt, bias=b, rowvec=rv, residual=res.reshape(2, 48, 24)), leaky=True)
+    want = F.leaky_relu(_nhwc(F.conv2d(x, wt, b, padding=1)) + rv[:, None, None, :], 0.1) + res
+    assert torch.allclose(ls.igemm_reference(op), _flat(want), rtol=1e-12, atol=1e-12)
+    plain = dict(op, leaky=False)
+    assert not torch.allclose(ls.igemm_reference(plain), _flat(want), rtol=1e-3, atol=1e-3)
+    paired = _nhwc(x).reshape(2, 6, 4, 64)
+    op = dict(_op(paired, stride2_weight(wt), bias=b, hout=6, wout=4), leaky=True)
+    want = F.leaky_relu(F.conv2d(x, wt, b, stride=(1, 2), padding=1), 0.1)
+    assert torch.allclose(ls.igemm_reference(op), _flat(_nhwc(want)), rtol=1e-12, atol=1e-12)
+
+
+def test_extra_kinds_are_opt_in_and_counted_per_library_call():
+    """Without `extra` the wrapped set is the UNet's and the VAEs'; an unknown kind is refused; every extra kind has its entry
+    point in LAUNCH_KINDS; a skinny_linear judged once for 17 rows accounts for two library calls."""
+    class MP:
+        pass
+    assert ls.LaunchShadow(MP()).wrapped == ls.LaunchShadow.WRAPPED
+    both = ls.LaunchShadow(MP(), extra=ls.EXTRA_KINDS).wrapped
+    assert both == ls.LaunchShadow.WRAPPED + ls.EXTRA_KINDS and len(set(both)) == len(both)
+    assert ls.LaunchShadow(MP(), extra=("quick_gelu",)).wrapped == ls.LaunchShadow.WRAPPED + ("quick_gelu",)
+    with pytest.raises(ValueError):
+        ls.LaunchShadow(MP(), extra=("quick_gelu", "nearest_resize"))
+    assert set(ls.EXTRA_KINDS) <= set(ls.LAUNCH_KINDS.values())
+    assert all(hasattr(ls.LaunchShadow, "_" + k) for k in both)
+    assert ls.is_query_only("mobi_lpips_distance_ws_floats") and not ls.is_query_only("mobi_lpips_distance")
+
+    class Lib:
+        def __getattr__(self, name):
+            return lambda *a: 0
+    sh = ls.LaunchShadow(MP(), extra=("skinny_linear",))
+    lib = ls.LibCensus(Lib(), sh.calls)
+    lib.mobi_skinny_linear(None)
+    lib.mobi_skinny_linear(None)
+    sh._count("skinny_linear", (17 + 15) // 16)
+    assert sh.census_failures() == []
+    lib.mobi_quick_gelu(None)
+    assert [m for m in sh.census_failures() if m.startswith("mobi_quick_gelu: 1 calls, 0 judged")]
