@@ -278,28 +278,31 @@ extern "C" int mobi_adamw_multi(const mobi_mt_tensor* tensors, int32_t n_tensors
   return MOBI_OK;
 }
 
-extern "C" int mobi_ema_multi(const mobi_mt_pair* pairs, int32_t n_pairs, const mobi_mt_chunk* chunks, int32_t n_chunks,
-                              float one_minus_decay, int32_t op, void* stream) {
-  if (!pairs || !chunks || n_pairs <= 0 || n_chunks <= 0 || (op != MOBI_MT_EMA && op != MOBI_MT_SWAP)) return MOBI_ERR_ARG;
-  if (op == MOBI_MT_EMA)
-    hipLaunchKernelGGL(pair_multi_kernel<kPairEma>, dim3(mt_grid(n_chunks)), dim3(kMtBlock), 0, ST(stream), pairs, n_pairs, chunks,
-                       n_chunks, one_minus_decay);
-  else
-    hipLaunchKernelGGL(pair_multi_kernel<kPairSwap>, dim3(mt_grid(n_chunks)), dim3(kMtBlock), 0, ST(stream), pairs, n_pairs, chunks,
-                       n_chunks, one_minus_decay);
+static bool pairs_args_ok(const mobi_mt_pair* pairs, int32_t n_pairs, const mobi_mt_chunk* chunks, int32_t n_chunks) {
+  return pairs && chunks && n_pairs > 0 && n_chunks > 0;
+}
+
+template <int OP>
+static int launch_pairs(const mobi_mt_pair* pairs, int32_t n_pairs, const mobi_mt_chunk* chunks, int32_t n_chunks, float scalar,
+                        void* stream) {
+  hipLaunchKernelGGL(pair_multi_kernel<OP>, dim3(mt_grid(n_chunks)), dim3(kMtBlock), 0, ST(stream), pairs, n_pairs, chunks, n_chunks,
+                     scalar);
   MOBI_CHECK_LAUNCH();
   return MOBI_OK;
 }
 
+extern "C" int mobi_ema_multi(const mobi_mt_pair* pairs, int32_t n_pairs, const mobi_mt_chunk* chunks, int32_t n_chunks,
+                              float one_minus_decay, int32_t op, void* stream) {
+  if (!pairs_args_ok(pairs, n_pairs, chunks, n_chunks)) return MOBI_ERR_ARG;
+  if (op == MOBI_MT_EMA) return launch_pairs<kPairEma>(pairs, n_pairs, chunks, n_chunks, one_minus_decay, stream);
+  if (op == MOBI_MT_SWAP) return launch_pairs<kPairSwap>(pairs, n_pairs, chunks, n_chunks, one_minus_decay, stream);
+  return MOBI_ERR_ARG;
+}
+
 extern "C" int mobi_accum_multi(const mobi_mt_pair* pairs, int32_t n_pairs, const mobi_mt_chunk* chunks, int32_t n_chunks, float w,
                                 int32_t op, void* stream) {
-  if (!pairs || !chunks || n_pairs <= 0 || n_chunks <= 0 || (op != MOBI_MT_ACCUM && op != MOBI_MT_ASSIGN)) return MOBI_ERR_ARG;
-  if (op == MOBI_MT_ACCUM)
-    hipLaunchKernelGGL(pair_multi_kernel<kPairAccum>, dim3(mt_grid(n_chunks)), dim3(kMtBlock), 0, ST(stream), pairs, n_pairs, chunks,
-                       n_chunks, w);
-  else
-    hipLaunchKernelGGL(pair_multi_kernel<kPairAssign>, dim3(mt_grid(n_chunks)), dim3(kMtBlock), 0, ST(stream), pairs, n_pairs, chunks,
-                       n_chunks, w);
-  MOBI_CHECK_LAUNCH();
-  return MOBI_OK;
+  if (!pairs_args_ok(pairs, n_pairs, chunks, n_chunks)) return MOBI_ERR_ARG;
+  if (op == MOBI_MT_ACCUM) return launch_pairs<kPairAccum>(pairs, n_pairs, chunks, n_chunks, w, stream);
+  if (op == MOBI_MT_ASSIGN) return launch_pairs<kPairAssign>(pairs, n_pairs, chunks, n_chunks, w, stream);
+  return MOBI_ERR_ARG;
 }

@@ -6,6 +6,7 @@ replicated, no communication during sampling; ONE collective per batch: the all-
 decoded images (`torch.distributed`, backend "nccl" = RCCL over xGMI on ROCm, "gloo" in the CPU
 tests).  The reference has no multi-GPU inference (inference_test_bench.py:337 is one process, one GPU).
 """
+import itertools
 from typing import Dict, List, Tuple
 
 import torch
@@ -94,13 +95,9 @@ def allreduce_gradients(grads: Dict[str, torch.Tensor], bucket_bytes: int = 256 
         return grads
     names = sorted(grads)
     check_same_layout(names, [grads[k].numel() for k in names], grads[names[0]].device if names else torch.device("cpu"))
-    i = 0
-    while i < len(names):
-        bucket, size = [], 0
-        while i < len(names) and (not bucket or size + grads[names[i]].numel() * 4 <= bucket_bytes):
-            bucket.append(names[i])
-            size += grads[names[i]].numel() * 4
-            i += 1
+    layout, _ = gradient_bucket_layout({k: grads[k].numel() for k in names}, bucket_bytes)
+    for _, bucket in itertools.groupby(names, key=lambda k: layout[k][0]):
+        bucket = list(bucket)
         flat = torch.cat([grads[k].reshape(-1).float() for k in bucket])
         dist.all_reduce(flat, op=dist.ReduceOp.SUM)
         if average:
@@ -115,8 +112,8 @@ def allreduce_gradients(grads: Dict[str, torch.Tensor], bucket_bytes: int = 256 
 
 def gradient_bucket_layout(numels: Dict[str, int], bucket_bytes: int = 256 << 20):
     """Where a gradient accumulator keeps every tensor (`train.GradAccumulator`): ({name: (bucket, offset, numel)}, [bucket
-    length]), offsets and lengths in fp32 elements.  Names in sorted order, cut into buckets exactly where `allreduce_gradients`
-    cuts the same names and sizes (a tensor opens a new bucket when the bytes of the tensors already in this one plus its own
+    length]), offsets and lengths in fp32 elements.  Names in sorted order, cut into buckets -- `allreduce_gradients` takes its
+    cut from here -- by one rule (a tensor opens a new bucket when the bytes of the tensors already in this one plus its own
     would exceed `bucket_bytes`; a tensor larger than that has a bucket to itself); inside a bucket every tensor starts on a
     16-byte boundary (the multi-tensor kernels' 16-byte path), the padding is not counted by the cut.  Pure: no tensors."""
     layout, lengths = {}, []

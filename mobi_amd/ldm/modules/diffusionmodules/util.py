@@ -105,6 +105,16 @@ _CHUNK_MAJOR = _os.environ.get("MOBI_CHUNK_MAJOR", "0") == "1"
 WEIGHTS_EPOCH = [0]
 
 
+def weights_changed(params=()):
+    """Parameters were written under the packed 16-bit copies: bump the version of every one of `params` (the copies are keyed on
+    the version counter; a raw-pointer write does not move it, `copy_` does) and open a new weights epoch -- captured step
+    graphs read the OLD packed copies and are dropped when it moves (samplers key their graphs on it, so training-then-sampling
+    re-captures without the caller having to refresh any fingerprint)."""
+    for p in params:
+        torch.autograd.graph.increment_version(p)
+    WEIGHTS_EPOCH[0] += 1
+
+
 class _Holder(nn.Module):
     """Caches device-side packed copies keyed on (dtype, device, parameter versions)."""
 

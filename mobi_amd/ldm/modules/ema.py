@@ -9,6 +9,7 @@ import torch
 from torch import nn
 
 from ... import ops
+from .diffusionmodules.util import weights_changed
 
 
 class LitEma(nn.Module):
@@ -26,7 +27,7 @@ class LitEma(nn.Module):
                 self.register_buffer(s_name, p.detach().clone())
         self.collected_params = []
         self._host = None               # (decay: np.float32, num_updates: int) as the buffers hold them, read once
-        self._pairs = None              # ops.MultiTensorPairs over (parameter, shadow), built at the first launch
+        self._pairs = None              # ops.MultiTensorTable over (parameter, shadow), built at the first launch
 
     def _load_from_state_dict(self, *args, **kwargs):
         self._host = None               # a checkpoint brings its own decay and update count
@@ -60,7 +61,7 @@ class LitEma(nn.Module):
                 assert key not in self.m_name2s_name
         ptrs = tuple((p.data_ptr(), s.data_ptr()) for p, s in zip(params, shadows))
         if self._pairs is None or self._pairs.ptrs != ptrs:
-            self._pairs = ops.MultiTensorPairs(params, shadows)
+            self._pairs = ops.MultiTensorTable([params, shadows])
         return self._pairs, [p for p in m_param.values() if p.requires_grad]
 
     @torch.no_grad()
@@ -74,22 +75,18 @@ class LitEma(nn.Module):
         """Exchange every parameter with its shadow, one launch, no copy of either.  The parameters change under the packed
         16-bit copies and captured step graphs that are keyed on them: every swapped parameter's version and the weights
         epoch are bumped, as `train.AdamW.step` does."""
-        from .diffusionmodules.util import WEIGHTS_EPOCH
         pairs, params = self._table(model)
         ops.swap_multi(pairs)
-        for p in params:
-            torch.autograd.graph.increment_version(p)
-        WEIGHTS_EPOCH[0] += 1
+        weights_changed(params)
 
     @torch.no_grad()
     def copy_to(self, model):
-        from .diffusionmodules.util import WEIGHTS_EPOCH
         for key, p in model.named_parameters():
             if p.requires_grad:
                 p.copy_(self._buffers[self.m_name2s_name[key]])
             else:
                 assert key not in self.m_name2s_name
-        WEIGHTS_EPOCH[0] += 1
+        weights_changed()                               # (`copy_` has bumped the versions)
 
     def store(self, parameters):
         """Keep a copy of `parameters` (an iterable of `nn.Parameter`) for `restore`."""
@@ -98,7 +95,6 @@ class LitEma(nn.Module):
     @torch.no_grad()
     def restore(self, parameters):
         """Write what `store` kept back into `parameters`."""
-        from .diffusionmodules.util import WEIGHTS_EPOCH
         for c_param, param in zip(self.collected_params, parameters):
             param.copy_(c_param)
-        WEIGHTS_EPOCH[0] += 1
+        weights_changed()                               # (`copy_` has bumped the versions)

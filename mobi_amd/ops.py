@@ -619,74 +619,88 @@ def multi_tensor_chunk_map(numels, chunk=None):
     return cmap
 
 
-class _PointerTable:
-    """A table of `count` rows of `width` 8-byte fields whose device copy the multi-tensor kernels read and of which ONE column
-    changes from call to call (this step's gradient pointers): the rows live in pinned host memory, `write_column` rewrites the
-    column and copies the table to the device on the current stream.  The host rows are not rewritten before the previous copy
-    has completed: `write_column` waits on that copy's event first (already signalled where a step read a result back)."""
+LIVE = object()      # in a MultiTensorTable's column list: the one column whose pointers change from call to call (`set_live`)
 
-    def __init__(self, count, width, device):
+
+def multi_tensor_rows(columns, numels):
+    """The int64 rows {column pointers..., n} the multi-tensor kernels read (`_lib.MtTensor`: 4 columns, `_lib.MtPair`: 2), as a
+    numpy array [len(numels), len(columns) + 1].  columns: one list of addresses per column, or LIVE (zeros until `set_live`).
+    Pure: no tensors, no library."""
+    import numpy as np
+    rows = np.zeros((len(numels), len(columns) + 1), dtype=np.int64)
+    for col, ptrs in enumerate(columns):
+        if ptrs is not LIVE:
+            rows[:, col] = ptrs
+    rows[:, -1] = numels
+    return rows
+
+
+class MultiTensorTable:
+    """The device-resident tables the multi-tensor kernels walk: `rows`, {column pointers..., n} per tensor, and `chunks`, the
+    chunk map {element offset, tensor index} (`multi_tensor_chunk_map`'s, or `chunk_map`: one of the caller's own in its format).
+    columns: lists of dense fp32 tensors on one device, row i of every column of numel n_i -- [params, LIVE, exp_avgs,
+    exp_avg_sqs] for `grad_stats` / `adamw_multi`, [a_list, b_list] for `ema_multi` / `swap_multi`, [LIVE, b_list] for
+    `accum_multi`.  The listed tensors are kept alive and their pointers are stable (`ptrs`, per row, is what a caller compares
+    to notice that one moved): without a LIVE column everything is uploaded once.  A LIVE column (one at most) holds pointers
+    that change every call (this step's gradients): the rows then live in pinned host memory and `set_live` rewrites the column
+    and copies the rows on the current stream.  The host rows are not rewritten before that copy has completed: `set_live`
+    waits on the copy's event first (already signalled where a step read a result back, as `AdamW.step_scaled` does)."""
+
+    def __init__(self, columns, chunk_map=None):
         import numpy as np
-        self._host = torch.empty(count * width * 8, dtype=torch.uint8).pin_memory()
-        self.rows = self._host.numpy().view(np.int64).reshape(count, width)
-        self.device_rows = torch.empty(self._host.numel(), dtype=torch.uint8, device=device)
-        self._copied = None
-
-    def write_column(self, col, values):
-        if self._copied is not None:
-            self._copied.synchronize()
-        self.rows[:, col] = values
-        self.device_rows.copy_(self._host, non_blocking=True)
-        self._copied = torch.cuda.Event()
-        self._copied.record()
-
-
-class MultiTensorList:
-    """The device-resident tables `grad_stats` / `adamw_multi` walk: {param, grad, exp_avg, exp_avg_sq, n} per tensor and the
-    chunk map {element offset, tensor index}.  Parameters and moments are fixed at construction (stable pointers, uploaded once
-    with the chunk map); `set_grads` writes this step's gradient pointers into a pinned host table and copies it on the current
-    stream.  The host table is not rewritten before that copy has completed: `set_grads` waits on the copy's event first (already
-    signalled where a step read the statistics record back, `read_grad_stats`, as `AdamW.step_scaled` does)."""
-
-    def __init__(self, params, exp_avgs, exp_avg_sqs):
-        import numpy as np
-        lib = _lib.load()
-        assert len(params) > 0 and len(params) == len(exp_avgs) == len(exp_avg_sqs)
-        for p, m, v in zip(params, exp_avgs, exp_avg_sqs):
-            for t_ in (p, m, v):
-                assert _dev(t_).dtype == torch.float32 and t_.is_contiguous() and t_.numel() == p.numel() > 0
-        self.device, self.count = params[0].device, len(params)
-        self._keep = (list(params), list(exp_avgs), list(exp_avg_sqs))
-        self.numels = [p.numel() for p in params]
-        assert C.sizeof(_lib.MtTensor) == 5 * 8                                    # MtTensor: four pointers and n, 8 bytes each
-        self._table = _PointerTable(self.count, 5, self.device)
-        for col, ts in enumerate((params, None, exp_avgs, exp_avg_sqs)):
-            self._table.rows[:, col] = 0 if ts is None else [t_.data_ptr() for t_ in ts]
-        self._table.rows[:, 4] = self.numels
-        cmap = multi_tensor_chunk_map(self.numels)
+        fixed = [list(c) for c in columns if c is not LIVE]
+        assert fixed and len(fixed) >= len(columns) - 1 and len(fixed[0]) > 0 and all(len(c) == len(fixed[0]) for c in fixed)
+        self.device, self.count, self.width = fixed[0][0].device, len(fixed[0]), len(columns)
+        self.numels = [t_.numel() for t_ in fixed[0]]
+        for c in fixed:
+            for t_, n in zip(c, self.numels):
+                assert _dev(t_).dtype == torch.float32 and t_.is_contiguous() and t_.numel() == n > 0 and t_.device == self.device
+        self._keep = fixed
+        self.ptrs = tuple(zip(*[[t_.data_ptr() for t_ in c] for c in fixed]))
+        rows = multi_tensor_rows([LIVE if c is LIVE else [t_.data_ptr() for t_ in c] for c in columns], self.numels)
+        cmap = multi_tensor_chunk_map(self.numels) if chunk_map is None else chunk_map
         self.n_chunks = len(cmap)
         self.chunks = torch.from_numpy(cmap.view(np.uint8)).to(self.device)        # (a blocking copy, once)
-        self.tensors = self._table.device_rows
-        self.workspace = torch.empty(lib.mobi_multi_tensor_workspace_bytes(None) // 8, dtype=torch.float64, device=self.device)
-        self.record = torch.zeros(C.sizeof(_lib.GradStatsRecord) // 8, dtype=torch.int64, device=self.device)
-        self._grads = None
+        self._live_col = next((i for i, c in enumerate(columns) if c is LIVE), None)
+        self._live = self._copied = None
+        if self._live_col is None:
+            self.rows = torch.from_numpy(rows.view(np.uint8).reshape(-1)).to(self.device)
+        else:
+            self._host = torch.empty(rows.nbytes, dtype=torch.uint8).pin_memory()
+            self._host_rows = self._host.numpy().view(np.int64).reshape(rows.shape)
+            self._host_rows[:] = rows
+            self.rows = torch.empty(rows.nbytes, dtype=torch.uint8, device=self.device)
+        if self.width == 4:                            # `grad_stats`' partial sums and 16-byte record: once per table, not per call
+            self.workspace = torch.empty(_lib.load().mobi_multi_tensor_workspace_bytes(None) // 8, dtype=torch.float64, device=self.device)
+            self.record = torch.zeros(C.sizeof(_lib.GradStatsRecord) // 8, dtype=torch.int64, device=self.device)
 
-    def set_grads(self, grads):
-        """grads: one fp32 tensor per listed parameter, of its numel (kept alive until the next call)."""
-        assert len(grads) == self.count
-        grads = [g.contiguous() for g in grads]
-        for g, n in zip(grads, self.numels):
-            assert _dev(g).dtype == torch.float32 and g.numel() == n
-        self._table.write_column(1, [g.data_ptr() for g in grads])
-        self._grads = grads
+    def set_live(self, tensors):
+        """tensors: one fp32 tensor per row for the LIVE column, of the row's numel (kept alive until the next call)."""
+        assert self._live_col is not None and len(tensors) == self.count
+        tensors = [t_.contiguous() for t_ in tensors]
+        for t_, n in zip(tensors, self.numels):
+            assert _dev(t_).dtype == torch.float32 and t_.numel() == n and t_.device == self.device
+        if self._copied is not None:
+            self._copied.synchronize()
+        self._host_rows[:, self._live_col] = [t_.data_ptr() for t_ in tensors]
+        self.rows.copy_(self._host, non_blocking=True)
+        self._copied = torch.cuda.Event()
+        self._copied.record()
+        self._live = tensors
+
+    def ready(self, width):
+        """What every launch asserts: the table has the kernel's row layout and its LIVE column, if any, has been set."""
+        assert self.width == width, f"a table of {self.width} pointer columns where the kernel reads {width}"
+        assert self._live_col is None or self._live is not None, "set_live() first"
 
 
 def grad_stats(mt):
-    """Sum of squares (fp64) and non-finite flag over every gradient of `mt` (one launch + its one-block finish pass) -> the device
-    record (`mt.record`); `read_grad_stats` brings it to the host."""
+    """Sum of squares (fp64) and non-finite flag over every gradient of `mt` (a MultiTensorTable [params, LIVE = grads, exp_avgs,
+    exp_avg_sqs]; one launch + its one-block finish pass) -> the device record (`mt.record`); `read_grad_stats` brings it to the
+    host."""
     lib = _lib.load()
-    assert mt._grads is not None, "set_grads() first"
-    _lib.check(lib.mobi_grad_stats(_ptr(mt.tensors), mt.count, _ptr(mt.chunks), mt.n_chunks, _ptr(mt.workspace), _ptr(mt.record),
+    mt.ready(4)
+    _lib.check(lib.mobi_grad_stats(_ptr(mt.rows), mt.count, _ptr(mt.chunks), mt.n_chunks, _ptr(mt.workspace), _ptr(mt.record),
                                    _stream()), "mobi_grad_stats")
     return mt.record
 
@@ -700,93 +714,35 @@ def read_grad_stats(record):
 def adamw_multi(mt, grad_mul, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
     """`adamw_step` of every tensor of `mt` IN PLACE on grad * grad_mul, one launch (the caller bumps the tensors' versions)."""
     lib = _lib.load()
-    assert mt._grads is not None, "set_grads() first"
-    _lib.check(lib.mobi_adamw_multi(_ptr(mt.tensors), mt.count, _ptr(mt.chunks), mt.n_chunks, grad_mul, lr, betas[0], betas[1], eps,
+    mt.ready(4)
+    _lib.check(lib.mobi_adamw_multi(_ptr(mt.rows), mt.count, _ptr(mt.chunks), mt.n_chunks, grad_mul, lr, betas[0], betas[1], eps,
                                     weight_decay, step, _stream()), "mobi_adamw_multi")
 
 
-class MultiTensorPairs:
-    """The device-resident tables `ema_multi` / `swap_multi` walk: {a, b, n} per pair of dense fp32 tensors of equal length and
-    the chunk map.  Uploaded once: the pointers are stable (parameters and their EMA shadows never reallocate; `ptrs` is what
-    a caller compares to notice that they did).  `chunk_map`: a map of the caller's own (a numpy record array as
-    `multi_tensor_chunk_map` makes it) in place of the table's."""
-
-    def __init__(self, a_list, b_list, chunk_map=None):
-        import numpy as np
-        assert len(a_list) > 0 and len(a_list) == len(b_list)
-        for a, b in zip(a_list, b_list):
-            for t_ in (a, b):
-                assert _dev(t_).dtype == torch.float32 and t_.is_contiguous() and t_.numel() == a.numel() > 0
-            assert a.device == b.device
-        self.device, self.count = a_list[0].device, len(a_list)
-        self._keep = (list(a_list), list(b_list))
-        self.numels = [a.numel() for a in a_list]
-        self.ptrs = tuple((a.data_ptr(), b.data_ptr()) for a, b in zip(a_list, b_list))
-        rows = np.empty((self.count, 3), dtype=np.int64)                           # MtPair: two pointers and n, 8 bytes each
-        assert rows.itemsize * 3 == C.sizeof(_lib.MtPair)
-        rows[:, :2] = self.ptrs
-        rows[:, 2] = self.numels
-        cmap = multi_tensor_chunk_map(self.numels) if chunk_map is None else chunk_map
-        self.n_chunks = len(cmap)
-        self.chunks = torch.from_numpy(cmap.view(np.uint8)).to(self.device)        # (blocking copies, once)
-        self.pairs = torch.from_numpy(rows.view(np.uint8).reshape(-1)).to(self.device)
-
-
 def ema_multi(pairs, one_minus_decay):
-    """b <- b - one_minus_decay * (b - a) for every pair of `pairs` (a MultiTensorPairs: a = parameter, b = shadow), one launch;
-    three separately rounded fp32 operations per element, as torch's `b.sub_(omd * (b - a))`."""
+    """b <- b - one_minus_decay * (b - a) for every pair of `pairs` (a MultiTensorTable [a_list, b_list]: a = parameter, b =
+    shadow), one launch; three separately rounded fp32 operations per element, as torch's `b.sub_(omd * (b - a))`."""
     lib = _lib.load()
-    _lib.check(lib.mobi_ema_multi(_ptr(pairs.pairs), pairs.count, _ptr(pairs.chunks), pairs.n_chunks, float(one_minus_decay),
+    pairs.ready(2)
+    _lib.check(lib.mobi_ema_multi(_ptr(pairs.rows), pairs.count, _ptr(pairs.chunks), pairs.n_chunks, float(one_minus_decay),
                                   _lib.MT_EMA, _stream()), "mobi_ema_multi")
 
 
 def swap_multi(pairs):
     """a <-> b for every pair of `pairs`, one launch, IN PLACE on both (raw-pointer writes: the caller bumps the versions)."""
     lib = _lib.load()
-    _lib.check(lib.mobi_ema_multi(_ptr(pairs.pairs), pairs.count, _ptr(pairs.chunks), pairs.n_chunks, 0.0, _lib.MT_SWAP,
+    pairs.ready(2)
+    _lib.check(lib.mobi_ema_multi(_ptr(pairs.rows), pairs.count, _ptr(pairs.chunks), pairs.n_chunks, 0.0, _lib.MT_SWAP,
                                   _stream()), "mobi_ema_multi")
 
 
-class MultiTensorAccumPairs:
-    """The tables `accum_multi` walks: {a, b, n} per tensor, b = the accumulator (stable pointers, written into the rows once,
-    like the chunk map), a = one micro-batch's gradient -- a fresh allocation every time, so `set_sources` sends the `a` column
-    through the pinned table of `MultiTensorList.set_grads` (`_PointerTable`)."""
-
-    def __init__(self, b_list):
-        import numpy as np
-        assert len(b_list) > 0
-        for b in b_list:
-            assert _dev(b).dtype == torch.float32 and b.is_contiguous() and b.numel() > 0 and b.device == b_list[0].device
-        self.device, self.count = b_list[0].device, len(b_list)
-        self._keep = list(b_list)
-        self.numels = [b.numel() for b in b_list]
-        assert C.sizeof(_lib.MtPair) == 3 * 8                                      # MtPair: two pointers and n, 8 bytes each
-        self._table = _PointerTable(self.count, 3, self.device)
-        self._table.rows[:, 0] = 0
-        self._table.rows[:, 1] = [b.data_ptr() for b in b_list]
-        self._table.rows[:, 2] = self.numels
-        cmap = multi_tensor_chunk_map(self.numels)
-        self.n_chunks = len(cmap)
-        self.chunks = torch.from_numpy(cmap.view(np.uint8)).to(self.device)        # (a blocking copy, once)
-        self.pairs = self._table.device_rows
-        self._sources = None
-
-    def set_sources(self, a_list):
-        """a_list: one fp32 tensor per accumulator, of its numel (kept alive until the next call)."""
-        assert len(a_list) == self.count
-        a_list = [a.contiguous() for a in a_list]
-        for a, n in zip(a_list, self.numels):
-            assert _dev(a).dtype == torch.float32 and a.numel() == n and a.device == self.device
-        self._table.write_column(0, [a.data_ptr() for a in a_list])
-        self._sources = a_list
-
-
 def accum_multi(table, w, op):
-    """One micro-batch into the accumulators of `table` (a MultiTensorAccumPairs after `set_sources`), one launch, IN PLACE on
-    b: op `_lib.MT_ACCUM` b <- b + (w * a), product and sum each rounded to fp32; `_lib.MT_ASSIGN` b <- w * a, b not read."""
+    """One micro-batch into the accumulators of `table` (a MultiTensorTable [LIVE, b_list] after `set_live`: a = the micro-batch's
+    gradients, b = the accumulators), one launch, IN PLACE on b: op `_lib.MT_ACCUM` b <- b + (w * a), product and sum each
+    rounded to fp32; `_lib.MT_ASSIGN` b <- w * a, b not read."""
     lib = _lib.load()
-    assert table._sources is not None, "set_sources() first"
-    _lib.check(lib.mobi_accum_multi(_ptr(table.pairs), table.count, _ptr(table.chunks), table.n_chunks, float(w), int(op),
+    table.ready(2)
+    _lib.check(lib.mobi_accum_multi(_ptr(table.rows), table.count, _ptr(table.chunks), table.n_chunks, float(w), int(op),
                                     _stream()), "mobi_accum_multi")
 
 

@@ -24,6 +24,7 @@ import torch
 
 from . import engine_dtype, ops
 from .ops import Packed
+from .ldm.modules.diffusionmodules.util import weights_changed
 
 TRAINABLE_MARKERS = ("cond_adapter", "lidar", "cross_modal")          # ddpm.py:1622-1626 of the reference
 
@@ -481,6 +482,16 @@ class StepResult:
         return f"StepResult(found_inf={self.found_inf}, grad_norm={self.grad_norm}, clip_coef={self.clip_coef}, scale={self.scale})"
 
 
+class _TableCache(dict):
+    """Multi-tensor tables per tuple of names, built at first use: `cache.get_or_build(names, build)`."""
+
+    def get_or_build(self, names, build):
+        table = self.get(names)
+        if table is None:
+            table = self[names] = build()
+        return table
+
+
 class AdamW:
     """torch.optim.AdamW's update (what `configure_optimizers` returns, ddpm.py:1649) on the engine: fp32 master parameters
     updated in place by `mobi_adamw_step`, moments kept per parameter name."""
@@ -489,22 +500,17 @@ class AdamW:
         self.params = dict(named_params)
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.state, self.steps = {}, 0
-        self._multi = {}                              # step_scaled's tables, per set of names that had a gradient (built lazily)
+        self._multi = _TableCache()                   # step_scaled's tables, per set of names that had a gradient (built lazily)
 
     def step(self, grads):
         """grads: {name: fp32 tensor}; names without an entry are left alone."""
         self.steps += 1
-        for name, p in self.params.items():
-            if name not in grads:
-                continue
+        stepped = {name: p for name, p in self.params.items() if name in grads}
+        for name, p in stepped.items():
             st = self.state.setdefault(name, (torch.zeros_like(p.data, dtype=torch.float32), torch.zeros_like(p.data, dtype=torch.float32)))
             ops.adamw_step(p.data, grads[name].reshape(p.shape).contiguous(), st[0], st[1], self.steps, self.lr, self.betas, self.eps,
                            self.weight_decay)
-            torch.autograd.graph.increment_version(p)          # the packed 16-bit copies are keyed on the version counter
-        # captured step graphs read the OLD packed copies: a new weights epoch drops them (samplers key their graphs on it, so
-        # training-then-sampling re-captures without the caller having to refresh any fingerprint)
-        from .ldm.modules.diffusionmodules.util import WEIGHTS_EPOCH
-        WEIGHTS_EPOCH[0] += 1
+        weights_changed(stepped.values())
         return self
 
     def step_scaled(self, grads, scaler=None, max_norm=None):
@@ -519,14 +525,14 @@ class AdamW:
         scale = 1.0 if scaler is None else scaler.scale
         if not names:
             return StepResult(False, 0.0, 1.0, scale)
-        mt = self._multi.get(names)
-        if mt is None:
+        def build():
             for n in names:
                 p = self.params[n]
                 self.state.setdefault(n, (torch.zeros_like(p.data, dtype=torch.float32), torch.zeros_like(p.data, dtype=torch.float32)))
-            mt = self._multi[names] = ops.MultiTensorList([self.params[n].data for n in names], [self.state[n][0] for n in names],
-                                                          [self.state[n][1] for n in names])
-        mt.set_grads([grads[n].reshape(self.params[n].shape) for n in names])
+            return ops.MultiTensorTable([[self.params[n].data for n in names], ops.LIVE, [self.state[n][0] for n in names],
+                                         [self.state[n][1] for n in names]])
+        mt = self._multi.get_or_build(names, build)
+        mt.set_live([grads[n].reshape(self.params[n].shape) for n in names])
         sumsq, found_inf = ops.read_grad_stats(ops.grad_stats(mt))
         if found_inf:
             if scaler is not None:
@@ -536,10 +542,7 @@ class AdamW:
         clip = 1.0 if max_norm is None else min(1.0, float(max_norm) / (norm + 1e-6))
         self.steps += 1
         ops.adamw_multi(mt, clip / scale, self.steps, self.lr, self.betas, self.eps, self.weight_decay)
-        for n in names:
-            torch.autograd.graph.increment_version(self.params[n])
-        from .ldm.modules.diffusionmodules.util import WEIGHTS_EPOCH
-        WEIGHTS_EPOCH[0] += 1
+        weights_changed(self.params[n] for n in names)
         if scaler is not None:
             scaler.update(False)
         return StepResult(False, norm, clip, scale)
@@ -570,7 +573,7 @@ class GradAccumulator:
         mdist.check_same_layout(self.names, [numels[k] for k in self.names], device)      # once: the layout cannot diverge later
         self.buckets = [torch.zeros(n, dtype=torch.float32, device=device) for n in lengths]
         self.views = {k: self.buckets[b][off:off + n].view(optimizer.params[k].shape) for k, (b, off, n) in self.layout.items()}
-        self._tables = {}                             # per tuple of names, as AdamW._multi
+        self._tables = _TableCache()                  # per tuple of names, as AdamW._multi
         self._clear()
 
     def _clear(self):
@@ -579,10 +582,8 @@ class GradAccumulator:
     def _launch(self, names, grads, op):
         if not names:
             return
-        table = self._tables.get(names)
-        if table is None:
-            table = self._tables[names] = ops.MultiTensorAccumPairs([self.views[k] for k in names])
-        table.set_sources([grads[k].reshape(self.views[k].shape) for k in names])
+        table = self._tables.get_or_build(names, lambda: ops.MultiTensorTable([ops.LIVE, [self.views[k] for k in names]]))
+        table.set_live([grads[k].reshape(self.views[k].shape) for k in names])
         ops.accum_multi(table, self.weight, op)
 
     def add(self, grads, scale=1.0):

@@ -92,7 +92,7 @@ def test_update_equals_the_references_shadows_bit_for_bit(ops, golden, tag):
     reference's CPU result; guards and parameters untouched."""
     init, steps = E.draws(E.DECAYS[tag][1])
     buf = Buffers(init[:len(E.SIZES)], init[:len(E.SIZES)])          # a shadow starts as a copy of its parameter
-    pairs = ops.MultiTensorPairs(buf.av, buf.bv)
+    pairs = ops.MultiTensorTable([buf.av, buf.bv])
     assert pairs.n_chunks == 1 + 1 + 1 + 1 + 1 + 1 + 2 + 3
     omd = golden[f"{tag}_one_minus_decay"].numpy()
     for vals, c in zip(steps, omd):
@@ -111,7 +111,7 @@ def test_degenerate_coefficients(ops):
     """1 - decay = 0: the shadows keep their bits.  = 1: b - (b - a) in three roundings, which is not always a."""
     init, steps = E.draws(77)
     buf = Buffers(steps[0], init[:len(E.SIZES)])
-    pairs = ops.MultiTensorPairs(buf.av, buf.bv)
+    pairs = ops.MultiTensorTable([buf.av, buf.bv])
     ops.ema_multi(pairs, 0.0)
     for got, v in zip(buf.bv, init):
         assert _same_bits(got, torch.from_numpy(v))
@@ -129,7 +129,7 @@ def test_swap_exchanges_and_restores(ops):
     init, steps = E.draws(78)
     a0, b0 = steps[0], init[:len(E.SIZES)]
     buf = Buffers(a0, b0)
-    pairs = ops.MultiTensorPairs(buf.av, buf.bv)
+    pairs = ops.MultiTensorTable([buf.av, buf.bv])
     ops.swap_multi(pairs)
     for ga, gb, va, vb in zip(buf.av, buf.bv, a0, b0):
         assert _same_bits(ga, torch.from_numpy(vb)) and _same_bits(gb, torch.from_numpy(va))
@@ -151,11 +151,11 @@ def test_entries_outside_their_tensor_are_skipped(ops):
     bad["offset"] = [0, 0, 8192, 2 ** 40, -8192]
     assert E.SIZES[5] == 8192
     mixed = np.concatenate([bad[:2], cmap[:4], bad[2:4], cmap[4:], bad[4:]])
-    ops.ema_multi(ops.MultiTensorPairs(plain.av, plain.bv), 0.25)
-    ops.ema_multi(ops.MultiTensorPairs(foreign.av, foreign.bv, chunk_map=mixed), 0.25)
+    ops.ema_multi(ops.MultiTensorTable([plain.av, plain.bv]), 0.25)
+    ops.ema_multi(ops.MultiTensorTable([foreign.av, foreign.bv], chunk_map=mixed), 0.25)
     assert _same_bits(foreign.b, plain.b) and _same_bits(foreign.a, plain.a) and foreign.guards_intact()
     assert not _same_bits(plain.bv[-1], torch.from_numpy(init[len(E.SIZES) - 1]))      # (something was updated)
-    ops.swap_multi(ops.MultiTensorPairs(foreign.av, foreign.bv, chunk_map=mixed))
+    ops.swap_multi(ops.MultiTensorTable([foreign.av, foreign.bv], chunk_map=mixed))
     for ga, gb, pa, pb in zip(foreign.av, foreign.bv, plain.av, plain.bv):
         assert _same_bits(ga, pb) and _same_bits(gb, pa)
     assert foreign.guards_intact()
@@ -166,9 +166,9 @@ def test_argument_errors_launch_nothing(ops):
     lib = _lib.load()
     init, steps = E.draws(80)
     buf = Buffers(steps[0], init[:len(E.SIZES)])
-    pairs = ops.MultiTensorPairs(buf.av, buf.bv)
+    pairs = ops.MultiTensorTable([buf.av, buf.bv])
     before = (buf.a.clone(), buf.b.clone())
-    tab, cm, st = C.c_void_p(pairs.pairs.data_ptr()), C.c_void_p(pairs.chunks.data_ptr()), ops._stream()
+    tab, cm, st = C.c_void_p(pairs.rows.data_ptr()), C.c_void_p(pairs.chunks.data_ptr()), ops._stream()
     ERR_ARG = -1
     assert lib.mobi_ema_multi(None, pairs.count, cm, pairs.n_chunks, 0.5, _lib.MT_EMA, st) == ERR_ARG
     assert lib.mobi_ema_multi(tab, pairs.count, None, pairs.n_chunks, 0.5, _lib.MT_SWAP, st) == ERR_ARG
@@ -180,7 +180,7 @@ def test_argument_errors_launch_nothing(ops):
     torch.cuda.synchronize()
     assert torch.equal(buf.a, before[0]) and torch.equal(buf.b, before[1])
     with pytest.raises(_lib.EngineUnavailable):
-        ops.MultiTensorPairs([torch.zeros(4)], [torch.zeros(4)])                       # no CPU path
+        ops.MultiTensorTable([[torch.zeros(4)], [torch.zeros(4)]])                     # no CPU path
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -51,12 +51,12 @@ def _launch_window(ops, case, acc, grad_sets, w, first_op):
     """One launch per gradient set over `case.names` (`first_op`, then ACCUM) -> the gradient buffers as (before, after)."""
     from mobi_amd import _lib
     views = _carve(acc, case.lay)
-    table = ops.MultiTensorAccumPairs([views[k] for k in case.names])
+    table = ops.MultiTensorTable([ops.LIVE, [views[k] for k in case.names]])
     kept = []
     for i, g in enumerate(grad_sets):
         flat, gv = case.grad_buffer(g)
         before = flat.clone()
-        table.set_sources([gv[k] for k in case.names])
+        table.set_live([gv[k] for k in case.names])
         ops.accum_multi(table, w, first_op if i == 0 else _lib.MT_ACCUM)
         kept.append((before, flat))
     torch.cuda.synchronize()
@@ -135,9 +135,9 @@ def test_non_finite_values_survive_the_window_and_the_next_window_is_clean(ops, 
     keep = [_add(case, acc, g, s.scale) for g in bad]
     assert bool(torch.isnan(acc.views[name_inf][11])) and bool(torch.isnan(acc.views[name_nan][-1]))
     assert bool(torch.isfinite(acc.views[name_inf][:11]).all()) and bool(torch.isfinite(acc.views[name_nan][:-1]).all())
-    mt = ops.MultiTensorList([opt.params[k] for k in case.names], [torch.zeros_like(opt.params[k]) for k in case.names],
-                             [torch.zeros_like(opt.params[k]) for k in case.names])
-    mt.set_grads([acc.views[k] for k in case.names])
+    mt = ops.MultiTensorTable([[opt.params[k] for k in case.names], ops.LIVE, [torch.zeros_like(opt.params[k]) for k in case.names],
+                               [torch.zeros_like(opt.params[k]) for k in case.names]])
+    mt.set_live([acc.views[k] for k in case.names])
     assert ops.read_grad_stats(ops.grad_stats(mt))[1] is True
     res = acc.step(scaler=s)
     assert res.found_inf is True and res.scale == 1024.0 and s.scale == 512.0 and opt.steps == 0
@@ -163,11 +163,11 @@ def test_argument_errors_launch_nothing(ops, case):
     lib = _lib.load()
     acc = _accumulators(case, 3.0)
     views = _carve(acc, case.lay)
-    table = ops.MultiTensorAccumPairs([views[k] for k in case.names])
+    table = ops.MultiTensorTable([ops.LIVE, [views[k] for k in case.names]])
     flat, gv = case.grad_buffer(case.grads[0])
-    table.set_sources([gv[k] for k in case.names])
+    table.set_live([gv[k] for k in case.names])
     before = (acc.clone(), flat.clone())
-    tab, cm, st = C.c_void_p(table.pairs.data_ptr()), C.c_void_p(table.chunks.data_ptr()), ops._stream()
+    tab, cm, st = C.c_void_p(table.rows.data_ptr()), C.c_void_p(table.chunks.data_ptr()), ops._stream()
     ERR_ARG = -1
     assert lib.mobi_accum_multi(None, table.count, cm, table.n_chunks, 0.5, _lib.MT_ACCUM, st) == ERR_ARG
     assert lib.mobi_accum_multi(tab, table.count, None, table.n_chunks, 0.5, _lib.MT_ASSIGN, st) == ERR_ARG
@@ -179,7 +179,7 @@ def test_argument_errors_launch_nothing(ops, case):
     torch.cuda.synchronize()
     assert _same_bits(acc, before[0]) and _same_bits(flat, before[1])
     with pytest.raises(_lib.EngineUnavailable):
-        ops.MultiTensorAccumPairs([torch.zeros(4)])                                    # no CPU path
+        ops.MultiTensorTable([ops.LIVE, [torch.zeros(4)]])                             # no CPU path
 
 
 def test_misuse_raises(case):

@@ -90,14 +90,14 @@ def case(ops):
 
 def _list(ops, case, p, m, v):
     pv, mv, vv = _carve(p, case.lay), _carve(m, case.lay), _carve(v, case.lay)
-    return ops.MultiTensorList([pv[k] for k in case.names], [mv[k] for k in case.names], [vv[k] for k in case.names])
+    return ops.MultiTensorTable([[pv[k] for k in case.names], ops.LIVE, [mv[k] for k in case.names], [vv[k] for k in case.names]])
 
 
 def _stats(ops, case, g):
     p, m, v = case.state()
     mt = _list(ops, case, p, m, v)
     flat, views = case.grad_buffer(g)
-    mt.set_grads([views[k] for k in case.names])
+    mt.set_live([views[k] for k in case.names])
     return ops.read_grad_stats(ops.grad_stats(mt)), ops.read_grad_stats(ops.grad_stats(mt))
 
 
@@ -146,7 +146,7 @@ def _run_multi(ops, case, grads, grad_mul, pre_mul=1.0):
     mt = _list(ops, case, p, m, v)
     for step, g in enumerate(grads, 1):
         flat, views = case.grad_buffer(g, pre_mul)
-        mt.set_grads([views[k] for k in case.names])
+        mt.set_live([views[k] for k in case.names])
         ops.adamw_multi(mt, grad_mul, step, LR)
     return p.cpu(), m.cpu(), v.cpu()
 

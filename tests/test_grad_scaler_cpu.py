@@ -3,6 +3,7 @@ multi-tensor entry points' argument checks (validation happens before any launch
 import ctypes as C
 import math
 
+import numpy as np
 import pytest
 import torch
 
@@ -92,3 +93,27 @@ def test_multi_tensor_entry_points_validate_on_the_host():
     assert lib.mobi_adamw_multi(16, 1, None, 1, 1.0, 1e-3, 0.9, 0.999, 1e-8, 1e-2, 1, None) == -1
     assert lib.mobi_adamw_multi(16, 1, 16, 1, 1.0, 1e-3, 0.9, 0.999, 1e-8, 1e-2, 0, None) == -1      # steps count from 1
     assert C.sizeof(_lib.MtTensor) == 40 and C.sizeof(_lib.MtChunk) == 16 and C.sizeof(_lib.GradStatsRecord) == 16
+
+
+def test_table_rows_match_the_structs_field_by_field():
+    """`ops.multi_tensor_rows` builds what the kernels read as `mobi_mt_tensor` / `mobi_mt_pair`: the bytes of a row equal the
+    bytes of the ctypes struct filled, field by field, with the same distinct values (size AND field order)."""
+    from mobi_amd import _lib, ops
+    for cls in (_lib.MtTensor, _lib.MtPair):
+        fields = [name for name, _ in cls._fields_]
+        assert fields[-1] == "n"
+        structs, columns, numels = [], [[] for _ in fields[:-1]], []
+        for row in range(3):
+            s = cls()
+            for col, name in enumerate(fields[:-1]):
+                value = 0x1000 * (row + 1) + 0x10 * (col + 1)             # distinct per row and per field
+                setattr(s, name, value)
+                columns[col].append(value)
+            s.n = 7 + row
+            numels.append(7 + row)
+            structs.append(bytes(s))
+        rows = ops.multi_tensor_rows(columns, numels)
+        assert rows.dtype == np.int64 and rows.shape == (3, len(fields)) and rows.flags["C_CONTIGUOUS"]
+        assert rows.tobytes() == b"".join(structs), cls.__name__
+        live = ops.multi_tensor_rows([ops.LIVE] + columns[1:], numels)   # a live column: zeros until it is set, the rest in place
+        assert (live[:, 0] == 0).all() and (live[:, 1:] == rows[:, 1:]).all()

@@ -41,9 +41,9 @@ def main():
     grads = [torch.randn(layout[k][2], device="cuda") for k in names]
     shadows = [torch.randn(layout[k][2], device="cuda") for k in names]
     n = sum(t.numel() for t in acc)
-    table = ops.MultiTensorAccumPairs(acc)
-    table.set_sources(grads)
-    pairs = ops.MultiTensorPairs(grads, shadows)
+    table = ops.MultiTensorTable([ops.LIVE, acc])
+    table.set_live(grads)
+    pairs = ops.MultiTensorTable([grads, shadows])
     w = 0.25
     lines = [f"{torch.cuda.get_device_name(0)}; device events, median (min .. max) of {a.reps}; fp32",
              f"-- trained tensors: {len(names)} tensors, {n / 1e6:.1f} M elements, {table.n_chunks} chunks, {len(buckets)} buckets"]

@@ -55,7 +55,7 @@ def main():
         make = lambda: [torch.randn(math.prod(s), device="cuda") for _, s in lst]
         p, s = make(), make()
         n = sum(t.numel() for t in p)
-        pairs = ops.MultiTensorPairs(p, s)
+        pairs = ops.MultiTensorTable([p, s])
         lines.append(f"-- {title}: {len(lst)} tensors, {n / 1e6:.1f} M elements, {pairs.n_chunks} chunks")
 
         def row(what, fn, bytes_per_elem):
@@ -75,8 +75,8 @@ def main():
         row("torch, per tensor: s.sub_(omd * (s - p))", per_tensor, 12)
         if title == "trained tensors":
             m, v = [torch.zeros_like(t) for t in p], [torch.zeros_like(t) for t in p]
-            mt = ops.MultiTensorList(p, m, v)
-            mt.set_grads([torch.randn_like(t) * 1e-3 for t in p])
+            mt = ops.MultiTensorTable([p, ops.LIVE, m, v])
+            mt.set_live([torch.randn_like(t) * 1e-3 for t in p])
             step = [0]
 
             def adamw():
