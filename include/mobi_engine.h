@@ -51,7 +51,8 @@ extern "C" {
  *      mobi_image_normalize (mobi_image_normalize_params, struct id 22) and mobi_row_cosine; likewise the multi-tensor
  *      passes mobi_grad_stats / mobi_adamw_multi + mobi_multi_tensor_workspace_bytes (mobi_mt_tensor 23, mobi_mt_chunk 24,
  *      mobi_grad_stats_record 25); likewise the EMA / swap pass over tensor pairs, mobi_ema_multi (mobi_mt_pair 26); likewise
- *      the gradient accumulation over the same pair tables, mobi_accum_multi (no new struct) */
+ *      the gradient accumulation over the same pair tables, mobi_accum_multi (no new struct); likewise the fused loss /
+ *      entering-gradient launch mobi_loss_grad + mobi_loss_grad_blocks_per_sample (mobi_loss_grad_params 27) */
 #define MOBI_ABI_VERSION 6
 
 enum { MOBI_OK = 0, MOBI_ERR_ARG = -1, MOBI_ERR_UNSUPPORTED = -2, MOBI_ERR_LAUNCH = -3, MOBI_ERR_ALIGN = -4 };
@@ -64,7 +65,7 @@ const char* mobi_error_string(int code);
  * 3 attention, 4 ctx_attention, 5 skinny_linear, 6 conv_small_cin, 7 conv_small_cout,
  * 8 ddim_step, 9 two_key_adapter, 10 range_paste, 11 lidar_metrics, 12 range_prepare, 13 image_prepare, 14 ff_geglu,
  * 15 row_chain, 16 chain_op, 17 layernorm_bwd, 18 attention_bwd, 19 split_source, 20 dpm_step, 21 lpips_distance,
- * 22 image_normalize, 23 mt_tensor, 24 mt_chunk, 25 grad_stats_record, 26 mt_pair.  Returns 0 for an unknown id. */
+ * 22 image_normalize, 23 mt_tensor, 24 mt_chunk, 25 grad_stats_record, 26 mt_pair, 27 loss_grad.  Returns 0 for an unknown id. */
 size_t mobi_struct_size(int id);
 /* Development hook: the library reads its MOBI_* A/B environment variables once, at the first launch
  * (mobi_amd/csrc/tuning.h lists them); this re-reads them.  Not needed by a product caller. */
@@ -703,6 +704,40 @@ int mobi_range_denorm(const float* sample, const float* min_d, const float* max_
 int mobi_q_sample(const float* x0, const float* noise, const int64_t* t, const float* sqrt_ac,
                   const float* sqrt_1m_ac, float* out, int32_t batch, int32_t per_image, int32_t table_len,
                   void* stream);
+
+/* Where the training loss meets the network: LatentDiffusion.p_losses' three loss terms (ddpm.py:1189-1216 of the reference,
+ * eps-parameterisation, loss_type l2 or l1, per-timestep logvar and variational-bound weights) AND the gradient of `loss`
+ * w.r.t. the UNet's output, already in the layout the first backward launch reads -- one launch (one thread per pixel, blocks
+ * never straddle samples, one fp64 partial per block) plus its one-block finish pass.  Addition to ABI 6 (struct id 27).
+ *   eps, target  f32 [batch][channels][hw] dense; t: int64 [batch] on the device (no host read-back), an entry outside
+ *                [0, table_len) is clamped into it as mobi_q_sample does; logvar, lvlb: f32 [table_len] on the device
+ *   dy           T [batch][hw][c_pad], channels >= `channels` zero (what mobi_pack_nchw_sources writes); 16-byte aligned
+ *   per_sample   f32 [batch] = loss_simple_i;  terms: f32 [3] = {mean_i loss_simple_i, loss_vlb, loss}
+ *   workspace    f64 [batch][mobi_loss_grad_blocks_per_sample(hw)]
+ * Arithmetic (the contract):
+ *   g_i = l_simple_weight * exp(-logvar[t_i]) + elbo_weight * lvlb[t_i]            fp64, from the fp32 table entries
+ *   k_i = fp32(loss_scale * g_i * (l2 ? 2 : 1) / (batch * channels * hw))
+ *   l2:  dy = T(k_i * eps + (-k_i) * target), fp32: v = k_i * eps; v += (-k_i) * target, product and sum each rounded (never
+ *        contracted) -- mobi_lincomb4's expression under mobi_lincomb4's flags.  With logvar 0, elbo_weight 0 and
+ *        l_simple_weight 1, dy equals mobi_pack_nchw_sources(mobi_lincomb4(eps, target; k, -k)) bit for bit,
+ *        k = fp32(2 * loss_scale / numel)
+ *   l1:  dy = T(+k_i) where eps > target, T(-k_i) where eps < target, 0 where equal (torch.abs's gradient)
+ *   a NaN in eps or target is a NaN in dy under either loss (mobi_grad_stats finds it downstream)
+ *   loss_simple_i = (sum over channels, hw of (eps - target)^2 or |eps - target|) / (channels * hw): every element formed in
+ *        fp32, summed in fp64; the finish pass adds a sample's partials in ascending order; no atomics: two runs are bit-equal
+ *   terms[0] = mean_i loss_simple_i;  terms[1] = mean_i (lvlb[t_i] * loss_simple_i);
+ *   terms[2] = l_simple_weight * mean_i (loss_simple_i * exp(-logvar[t_i]) + logvar[t_i]) + elbo_weight * terms[1]
+ *        all three in fp64 (samples in ascending order), each rounded once to fp32
+ * MOBI_ERR_UNSUPPORTED: channels > c_pad, c_pad % 8, an unknown loss_type, batch > 65535. */
+enum { MOBI_LOSS_L2 = 0, MOBI_LOSS_L1 = 1 };
+typedef struct mobi_loss_grad_params {
+  const float* eps; const float* target; const int64_t* t; const float* logvar; const float* lvlb;
+  void* dy; float* per_sample; float* terms; double* workspace;
+  int32_t batch, channels, hw, table_len, c_pad, loss_type, dtype, reserved;
+  double l_simple_weight, elbo_weight, loss_scale;
+} mobi_loss_grad_params;
+int32_t mobi_loss_grad_blocks_per_sample(int32_t hw);
+int mobi_loss_grad(const mobi_loss_grad_params* p, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Harness post-processing on the device.  All buffers are device memory.

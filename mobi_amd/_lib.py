@@ -194,13 +194,23 @@ class GradStatsRecord(C.Structure):
     _fields_ = [("sumsq", C.c_double), ("nonfinite", i32), ("reserved", i32)]
 
 
+LOSS_L2, LOSS_L1 = 0, 1           # mobi_loss_grad's loss_type
+
+
+class LossGradParams(C.Structure):
+    _fields_ = [("eps", vp), ("target", vp), ("t", vp), ("logvar", vp), ("lvlb", vp), ("dy", vp), ("per_sample", vp),
+                ("terms", vp), ("workspace", vp), ("batch", i32), ("channels", i32), ("hw", i32), ("table_len", i32),
+                ("c_pad", i32), ("loss_type", i32), ("dtype", i32), ("reserved", i32), ("l_simple_weight", C.c_double),
+                ("elbo_weight", C.c_double), ("loss_scale", C.c_double)]
+
+
 STRUCT_IDS = {0: IgemmParams, 1: GroupNormParams, 2: LayerNormParams, 3: AttentionParams, 4: CtxAttentionParams,
               5: SkinnyLinearParams, 6: ConvSmallCinParams, 7: ConvSmallCoutParams, 8: DdimStepParams, 9: TwoKeyAdapterParams,
               10: RangePasteParams, 11: LidarMetricsParams, 12: RangePrepareParams, 13: ImagePrepareParams,
               14: FfGegluParams, 15: RowChainParams, 16: ChainOp,
               17: LayerNormBwdParams, 18: AttentionBwdParams, 19: SplitSource, 20: DpmStepParams,
               21: LpipsDistanceParams, 22: ImageNormalizeParams, 23: MtTensor, 24: MtChunk, 25: GradStatsRecord,
-              26: MtPair}
+              26: MtPair, 27: LossGradParams}
 
 # every symbol include/mobi_engine.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -265,6 +275,8 @@ SYMBOLS = {
     "mobi_dpm_step": (C.c_int, [C.POINTER(DpmStepParams), vp]),
     "mobi_lincomb4": (C.c_int, [vp, vp, vp, vp, vp, f32, f32, f32, f32, i64, vp]),
     "mobi_q_sample": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "mobi_loss_grad_blocks_per_sample": (i32, [i32]),
+    "mobi_loss_grad": (C.c_int, [C.POINTER(LossGradParams), vp]),
     "mobi_mask_blend": (C.c_int, [vp, vp, vp, vp, f32, f32, i32, i32, i32, vp]),
     "mobi_posterior_sample": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]),
     "mobi_range_denorm": (C.c_int, [vp, vp, vp, f32, f32, f32, f32, i32, i32, vp, vp, i32, i32, vp]),

@@ -63,6 +63,8 @@ class DDPM(nn.Module):
         self.v_posterior = v_posterior
         self.loss_type, self.l_simple_weight, self.original_elbo_weight = loss_type, l_simple_weight, original_elbo_weight
         if learn_logvar:
+            # `logvar` is a fixed per-timestep table here: `training_step` honours it (a checkpoint's, `logvar_init`) but does not
+            # optimise it -- the backward pass covers the UNet's adapter tensors and the conditioning stage's
             raise NotImplementedError("learn_logvar: the engine's backward pass covers the UNet's adapter tensors, not logvar")
         self.learn_logvar = learn_logvar
         self.use_scheduler = scheduler_config is not None      # ddpm.py:97-99
@@ -420,10 +422,16 @@ class LatentDiffusion(DDPM):
         main.py:510): returns the loss and leaves `self.adapter_grads` = {`model.diffusion_model.<name>`: fp32 gradient} for
         every UNet tensor the reference's optimizer filter selects (ddpm.py:1616-1629: `cond_adapter*`, `cross_modal*` --
         432 tensors, 180 M parameters), computed by the engine's backward pass (mobi_amd/train.py) and summed over the ranks
-        (mobi_amd.dist.allreduce_gradients).  FIRST SLICE of SURVEY 8(f) row 4: l2 loss with the default weights
-        (`learn_logvar=False`, `original_elbo_weight=0`: the gradient of mean(loss_simple)); the conditioning stage's
-        trainable tensors (the 3-D box embedder's four Linear layers, or `bbox_uncond_vector` on an unconditional draw) get
-        theirs too when `cond_stage_trainable`; `configure_optimizers()` returns the engine's AdamW to step with them.
+        (mobi_amd.dist.allreduce_gradients).  Every objective `p_losses` can express with the eps-parameterisation is trained
+        on: `loss_type` l2 or l1, `l_simple_weight`, `original_elbo_weight` and the per-timestep `logvar` table (zeros unless
+        `logvar_init` or a checkpoint says otherwise) -- one launch (`mobi_loss_grad`) forms the three loss terms and the
+        gradient of `loss` that enters the backward pass, from the device-resident t, without a read-back.  `logvar` is a
+        FIXED table here, honoured but not optimised: `learn_logvar=True` stays refused (in the constructor), as does any
+        parameterisation but eps.  The return value is `loss` (a 0-d device tensor); `self.loss_dict` keeps the reference's
+        logged dict {`train/loss_simple`, `train/loss_vlb`, `train/loss`} (`val/...` outside training mode) as 0-d device
+        tensors.  The conditioning stage's trainable tensors (the 3-D box embedder's four Linear layers, or
+        `bbox_uncond_vector` on an unconditional draw) get their gradients too when `cond_stage_trainable`;
+        `configure_optimizers()` returns the engine's AdamW to step with them.
 
         scaler (a `train.GradScaler`): dynamic loss scaling.  The loss scale is `scaler.scale` (fixed at this first use from the
         output's element count where the scaler was built with init_scale=None) and `self.adapter_grads` is left MULTIPLIED by it
@@ -433,8 +441,8 @@ class LatentDiffusion(DDPM):
         are taken after it (in `step_scaled`), on data every rank holds identically: all ranks take the same skip decision
         without a collective of their own.  Without a scaler nothing changes (`adapter_grads_scale` is 1.0)."""
         from .... import dist as mdist, engine_dtype, train
-        if self.loss_type != "l2" or self.parameterization != "eps" or self.learn_logvar or self.original_elbo_weight != 0:
-            raise NotImplementedError("the engine's training step covers the eps / l2 simple loss MObI trains with")
+        if self.parameterization != "eps" or self.learn_logvar:
+            raise NotImplementedError("the engine's training step covers the eps-parameterisation with a fixed logvar table")
         data = self.get_input(batch, self.first_stage_key)
         x, c = data["z"], data["cond"]
         # the conditioning stage's trainable part (ddpm.py:1635-1647): the 3-D box embedder runs with a tape, so that the
@@ -462,13 +470,12 @@ class LatentDiffusion(DDPM):
             # O(1) at every batch size) -- measured on the full-width network at 64 x 64, one pair: all 432 gradients 1.6e-2
             # off with a fixed 256, 1.7e-3 with 8,192 (tests/test_gpu_backward.py, full width)
             loss_scale = train.static_loss_scale(target.numel()) if engine_dtype() == torch.float16 else 1.0
-        logvar_t = self.logvar[t].to(self.device)                      # (zeros unless a checkpoint says otherwise)
-        if bool((logvar_t != 0).any()):
-            raise NotImplementedError("per-timestep logvar weights in the backward pass")
-        mse, grads = train.loss_and_gradients(self.model.diffusion_model, x_noisy, t, c, target, loss_scale=loss_scale,
-                                              unscale=scaler is None)
-        if self.l_simple_weight != 1.0:
-            grads = {k: ops.lincomb4([g.contiguous()], [float(self.l_simple_weight)]) for k, g in grads.items()}
+        # the weights of ddpm.py:1196-1216 (l_simple_weight, 1 / exp(logvar_t), original_elbo_weight * lvlb_weights_t) are
+        # gathered by the device-resident t inside the launch that forms the entering gradient
+        loss, grads, (_, terms) = train.loss_and_gradients(
+            self.model.diffusion_model, x_noisy, t, c, target, loss_scale=loss_scale, unscale=scaler is None,
+            loss_type=self.loss_type, t_weights=(self.logvar.to(x.device), self.lvlb_weights.to(x.device)),
+            l_simple_weight=float(self.l_simple_weight), elbo_weight=float(self.original_elbo_weight), return_terms=True)
         dctx = grads.pop("__dcontext__", None)                         # fp32 [N, 2, ctx_dim]
         named = {"model.diffusion_model." + k: v for k, v in grads.items()}
         if self.cond_stage_trainable and dctx is not None and "ref_bbox" in self.cond_stage_key:
@@ -489,7 +496,9 @@ class LatentDiffusion(DDPM):
             mdist.allreduce_gradients(self._complete_cond_stage_grads(named, x.device, across_ranks=True))
         self.adapter_grads = named
         self.adapter_grads_scale = 1.0 if scaler is None else float(loss_scale)
-        return self.l_simple_weight * mse
+        prefix = "train" if self.training else "val"
+        self.loss_dict = {f"{prefix}/loss_simple": terms[0], f"{prefix}/loss_vlb": terms[1], f"{prefix}/loss": terms[2]}
+        return loss
 
     def _cond_stage_trainables(self):
         """{name: parameter} of the conditioning stage's trainable tensors (ddpm.py:1635-1647): the 3-D box embedder's Linear

@@ -1340,6 +1340,44 @@ def q_sample(x0, noise, t, sqrt_ac, sqrt_1m_ac):
     return out
 
 
+_LOSS_TYPES = {"l2": _lib.LOSS_L2, "l1": _lib.LOSS_L1}
+_LOSS_WS = {}                # mobi_loss_grad's fp64 partials per (device, N, blocks per sample): stream-ordered reuse, as the tables' workspaces
+
+
+def loss_grad(eps, target, t, logvar, lvlb, loss_type="l2", l_simple_weight=1.0, elbo_weight=0.0, loss_scale=1.0, dtype=None,
+              c_pad=32):
+    """The loss terms of `p_losses` and the gradient of `loss * loss_scale` w.r.t. `eps`, one launch + its one-block finish pass
+    (include/mobi_engine.h, mobi_loss_grad, states the arithmetic).  eps / target: fp32 [N, C, H, W]; t: int64 [N]; logvar, lvlb:
+    fp32 [T] tables; all on the device, nothing is read back.  -> (dy: T [N, H, W, c_pad] as `pack_sources` lays it out,
+    per_sample: fp32 [N] = loss_simple, terms: fp32 [3] = loss_simple's mean, loss_vlb, loss)."""
+    lib = _lib.load()
+    if loss_type not in _LOSS_TYPES:
+        raise NotImplementedError(f"unknown loss type '{loss_type}'")
+    from . import engine_dtype
+    dtype = engine_dtype() if dtype is None else dtype
+    n, c, h, w = eps.shape
+    for t_ in (eps, target, logvar, lvlb):
+        assert _dev(t_).dtype == torch.float32 and t_.is_contiguous() and t_.device == eps.device
+    assert target.shape == eps.shape and logvar.dim() == 1 and lvlb.shape == logvar.shape
+    assert _dev(t).dtype == torch.int64 and t.is_contiguous() and t.numel() == n and t.device == eps.device
+    bps = lib.mobi_loss_grad_blocks_per_sample(h * w)
+    key = (eps.device, n, bps)
+    ws = _LOSS_WS.get(key)
+    if ws is None:
+        ws = _LOSS_WS[key] = torch.empty((n, bps), dtype=torch.float64, device=eps.device)
+    dy = torch.empty((n, h, w, c_pad), device=eps.device, dtype=dtype)
+    per_sample = torch.empty(n, device=eps.device, dtype=torch.float32)
+    terms = torch.empty(3, device=eps.device, dtype=torch.float32)
+    p = _lib.LossGradParams()
+    p.eps, p.target, p.t, p.logvar, p.lvlb = _ptr(eps), _ptr(target), _ptr(t), _ptr(logvar), _ptr(lvlb)
+    p.dy, p.per_sample, p.terms, p.workspace = _ptr(dy), _ptr(per_sample), _ptr(terms), _ptr(ws)
+    p.batch, p.channels, p.hw, p.table_len, p.c_pad = n, c, h * w, logvar.numel(), c_pad
+    p.loss_type, p.dtype = _LOSS_TYPES[loss_type], _dt(dtype)
+    p.l_simple_weight, p.elbo_weight, p.loss_scale = float(l_simple_weight), float(elbo_weight), float(loss_scale)
+    _lib.check(lib.mobi_loss_grad(C.byref(p), _stream()), "mobi_loss_grad")
+    return dy, per_sample, terms
+
+
 def mask_blend_(img, x0, noise, mask, sqrt_ac_t, sqrt_1m_ac_t):
     lib = _lib.load()
     b, c, h, w = img.shape

@@ -15,7 +15,12 @@ or hides tensors the backward pass needs, and has no place here.  Frozen layers 
 
 Pinned to torch.autograd through the CPU oracle (tests/test_gpu_backward.py): one block, and the reduced UNet end to end.
 Also here: the conditioning stage's trainable part (the 3-D box embedder, `bbox_uncond_vector`: ddpm.py:1635-1647) and AdamW.
-Not built: `logvar`, LR schedulers, activation checkpointing (the tape of a full-width step at 64 x 64 x 4 is 17 GB: fine in 288 GB).
+The objective is every one `p_losses` can express with the eps-parameterisation (ddpm.py:1189-1216): l2 or l1, `l_simple_weight`,
+the variational-bound term (`original_elbo_weight` x `lvlb_weights[t]`) and a per-timestep `logvar` table -- `mobi_loss_grad`
+(csrc/loss.hip) reads eps and the target once and writes the three loss terms and the gradient that enters `unet_backward`, in the
+layout its first launch reads, gathering the tables by the device-resident t: no torch arithmetic, no read-back.
+Not built: optimising `logvar` (`learn_logvar`: the table is fixed, honoured but not trained), the x0 parameterisation, activation
+checkpointing (the tape of a full-width step at 64 x 64 x 4 is 17 GB: fine in 288 GB).
 `mobi_amd.dist.allreduce_gradients` is the gradient collective (bucketed, RCCL; gloo on CPU in the tests).
 """
 import math
@@ -316,9 +321,11 @@ def unet_forward(net, x, timesteps, context):
     return ops.conv_small_cout(a, net.out[2].packed_tap_major(), pad=net.out[2].padding), tape
 
 
-def unet_backward(net, tape, deps):
-    """deps: fp32 [N, out_channels, h, w], the gradient of the loss w.r.t. `unet_forward`'s result -> {parameter name relative
+def unet_backward(net, tape, deps=None, dy=None):
+    """deps: fp32 [N, out_channels, h, w], the gradient of the loss w.r.t. `unet_forward`'s result -- or dy: the same gradient
+    already as T [N, h, w, 32] channels-last, zero beyond out_channels (what `ops.loss_grad` writes) -> {parameter name relative
     to the UNet: fp32 gradient} for every tensor of `trainable_names(net)` (ddpm.py:1616-1629 of the reference)."""
+    assert (deps is None) != (dy is None), "one of deps (plain fp32 gradient) and dy (packed by ops.loss_grad)"
     grads = {}
     conv = net.out[2]
     key = (conv.weight._version, conv.weight.data_ptr(), engine_dtype())
@@ -326,7 +333,9 @@ def unet_backward(net, tape, deps):
     if c.get("key") != key:                       # 4 -> 320 channels: the thin side zero-padded to 32 like the input convolution's
         w = conv.weight.detach().flip(2, 3).transpose(0, 1).contiguous()
         c["key"], c["val"] = key, ops.pack_conv_padded_cin(w, None, engine_dtype(), conv.weight.device)
-    dy = ops.pack_sources([deps.float().contiguous()], engine_dtype())
+    if dy is None:
+        dy = ops.pack_sources([deps.float().contiguous()], engine_dtype())
+    assert dy.dtype == engine_dtype() and dy.is_contiguous() and dy.shape[3] == 32
     n0 = net.out[0]
     dh = ops.groupnorm_bwd(tape["head"], ops.igemm(dy, c["val"]), *n0.affine(), n0.eps, True)
     nin = len(net.input_blocks)
@@ -341,21 +350,41 @@ def unet_backward(net, tape, deps):
     return grads
 
 
-def loss_and_gradients(net, x_noisy, timesteps, context, target, loss_scale=1.0, unscale=True):
-    """The eps-parameterised simple loss of `p_losses` (ddpm.py:1177-1217: mean squared error of the UNet's output against
-    the noise) and its gradient w.r.t. every adapter tensor.  loss_scale multiplies the gradient that enters the backward
-    pass and is divided out of the fp32 results (fp16 storage underflows without it at production sizes); with
-    unscale=False that per-tensor pass is skipped and every gradient (`__dcontext__` too) comes back still multiplied by
-    loss_scale, for `AdamW.step_scaled` to divide out inside its one update launch."""
+_ZERO_TABLES = {}
+
+
+def _zero_tables(device):
+    """(logvar, lvlb) of the default objective, one entry each, cached per device: `mobi_loss_grad` clamps t into the tables, so
+    every t reads logvar 0 and weight 0."""
+    if device not in _ZERO_TABLES:
+        _ZERO_TABLES[device] = (torch.zeros(1, dtype=torch.float32, device=device), torch.zeros(1, dtype=torch.float32, device=device))
+    return _ZERO_TABLES[device]
+
+
+def loss_and_gradients(net, x_noisy, timesteps, context, target, loss_scale=1.0, unscale=True, *, loss_type="l2", t_weights=None,
+                       l_simple_weight=1.0, elbo_weight=0.0, return_terms=False):
+    """The eps-parameterised loss of `p_losses` (ddpm.py:1177-1217 of the reference) and its gradient w.r.t. every adapter tensor:
+    loss = l_simple_weight * mean_i(loss_simple_i / exp(logvar[t_i]) + logvar[t_i]) + elbo_weight * mean_i(lvlb[t_i] * loss_simple_i),
+    loss_simple_i the per-sample mean of (eps - target)^2 (loss_type "l2") or |eps - target| ("l1").  t_weights: the device
+    tables (logvar, lvlb), fp32 [T]; None: logvar 0 and weight 0 at every t (with the default weights: the mean squared error).
+    One launch (`ops.loss_grad`) forms the loss terms and the gradient that enters the backward pass, in the layout its first
+    launch reads; nothing is read back.  loss_scale multiplies that gradient and is divided out of the fp32 results (fp16
+    storage underflows without it at production sizes); with unscale=False that per-tensor pass is skipped and every gradient
+    (`__dcontext__` too) comes back still multiplied by loss_scale, for `AdamW.step_scaled` to divide out inside its one update
+    launch.  -> (loss: 0-d fp32 device tensor, grads); return_terms=True: (loss, grads, (per_sample fp32 [N], terms fp32 [3] =
+    loss_simple's mean, loss_vlb, loss))."""
     eps, tape = unet_forward(net, x_noisy, timesteps, context)
-    target = target.float().contiguous()
-    loss = torch.mean((eps - target) ** 2)
-    k = 2.0 * loss_scale / eps.numel()
-    deps = ops.lincomb4([eps.contiguous(), target], [k, -k])
-    grads = unet_backward(net, tape, deps)
+    eps, target = eps.contiguous(), target.float().contiguous()
+    logvar, lvlb = _zero_tables(eps.device) if t_weights is None else t_weights
+    t = timesteps.to(device=eps.device, dtype=torch.int64).contiguous()
+    dy, per_sample, terms = ops.loss_grad(eps, target, t, logvar.float().contiguous(), lvlb.float().contiguous(), loss_type=loss_type,
+                                          l_simple_weight=l_simple_weight, elbo_weight=elbo_weight, loss_scale=loss_scale,
+                                          dtype=engine_dtype())
+    grads = unet_backward(net, tape, dy=dy)
     if unscale and loss_scale != 1.0:
         grads = {name: ops.lincomb4([g.contiguous()], [1.0 / loss_scale]) for name, g in grads.items()}
-    return loss, grads                            # (grads["__dcontext__"]: the gradient w.r.t. the context tokens)
+    loss = terms[2]                               # (grads["__dcontext__"]: the gradient w.r.t. the context tokens)
+    return (loss, grads, (per_sample, terms)) if return_terms else (loss, grads)
 
 
 # ======================================================================================================================
