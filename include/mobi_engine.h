@@ -328,7 +328,7 @@ int mobi_ff_geglu(const mobi_ff_geglu_params* p, void* stream);
  * A wave's registers hold the row state `s` (the operand of every product) and, until it is consumed, a residual `r`.
  * Operations (code):
  *   MOBI_CH_LOAD_S    s <- rows of p0 (T; image index img / img_div, strides in elements)
- *   MOBI_CH_LOAD_R    r <- rows of p0
+ *   MOBI_CH_LOAD_R    r <- rows of p0 (among a program's leading loads only: its first two places, in front of anything else)
  *   MOBI_CH_AFFINE_S  s <- s * bias[img][ch] + svec[img][ch]   (f32 [images][C] each: GroupNorm folded to scale / shift)
  *   MOBI_CH_ROWSTATS  (rs, cs) <- (rstd, -rstd * mean) of s over the C channels (eps)
  *   MOBI_CH_PRODUCT   v = W s (p0 = weight image, p1 = the NEXT product's image or NULL: prefetched);

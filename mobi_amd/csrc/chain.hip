@@ -684,11 +684,12 @@ extern "C" int mobi_row_chain(const mobi_row_chain_params* p, void* stream) {
     // may take the residual] then LOAD_S / ROWSTATS / ADAPTER / PRODUCT / STORE_S in any order
     int head = 0;
     while (head < 2 && head < p->nops[k] && (p->prog[k][head].code == MOBI_CH_LOAD_S || p->prog[k][head].code == MOBI_CH_LOAD_R)) ++head;
+    const int loads = head;                       // a LOAD_R behind anything else is never issued by the kernel: refused, not ignored
     if (head < p->nops[k] && p->prog[k][head].code == MOBI_CH_AFFINE_S) ++head;
     const int first_product = head < p->nops[k] && p->prog[k][head].code == MOBI_CH_PRODUCT ? head : -1;
     for (int i = p->nops[k] - 1; i >= 0; --i) {
       const mobi_chain_op& op = p->prog[k][i];
-      if ((op.code == MOBI_CH_LOAD_R && i >= 2) || (op.code == MOBI_CH_AFFINE_S && i >= head) ||
+      if ((op.code == MOBI_CH_LOAD_R && i >= loads) || (op.code == MOBI_CH_AFFINE_S && i >= head) ||
           (op.code == MOBI_CH_PRODUCT && (op.flags & MOBI_CH_RESID) && i != first_product)) return MOBI_ERR_UNSUPPORTED;
       switch (op.code) {
         case MOBI_CH_LOAD_S: case MOBI_CH_LOAD_R:

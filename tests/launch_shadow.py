@@ -3,7 +3,15 @@ own against a float64 restatement of its entry point's contract (include/mobi_en
 
 `LaunchShadow(monkeypatch)` wraps the `mobi_amd.ops` entry points the model files call as `ops.<name>(...)`: igemm (and with it
 `linear`, which calls the module's igemm), Deferred.finish, groupnorm, layernorm, attention, ctx_attention, ff_geglu,
-two_key_adapter and the VAEs' softmax_rows, split_f32, trunk_add, lincomb4, conv_small_cout, conv_small_cin and pack_sources.
+two_key_adapter, row_chain (with chain_adapter_image and groupnorm_scale_shift) and the VAEs' softmax_rows, split_f32,
+trunk_add, lincomb4, conv_small_cout, conv_small_cin and pack_sources.
+A row_chain launch is judged per stored tensor against tests/chain_ref.py, the fp64 interpreter of mobi_row_chain_params'
+contract: while a shadow runs, `ops.ChainProgram` is the recording subclass, so every program arrives with the plain description
+of what it was asked to build; the adapter's fp32 tables are found by the CONTENT of the image the launch was given (the
+transformer block copies the image into a persistent buffer) among the clones kept per chain_adapter_image call -- no match is
+a failure.  Bounds: TOL for a product and the adapter, 1.5 TOL for a folded product (tests/test_gpu_chain.py); the tag is the
+launch's note (post_attn1 / post_cam / pre_attn1).  groupnorm_scale_shift: x * scale + shift against fp64 GroupNorm within 1e-5
+(test_spatial_transformer_pre_chain_equals_launches).
 An igemm with per-image weights (the VAEs' mid attention) multiplies image i by slab i of the weight tensor's own shape; a
 `w_group_stride` that disagrees with it is a failure.  The elementwise entry points are bit-exact where their contract is
 (split_f32's hi and third part, trunk_add, the two-term coefficient-1 lincomb4, pack_sources).  Per call it snapshots the operands, runs the original with the same arguments, synchronises, computes the
@@ -39,6 +47,7 @@ import math
 import torch
 import torch.nn.functional as F
 
+from tests import chain_ref
 from tests.golden_cases import record
 from tests.test_gpu_ops import TOL
 
@@ -64,6 +73,7 @@ def bound_gn_split(dtype):
     return 2e-6 if dtype == torch.float16 else 2e-5
 
 
+BOUND_GN_SCALE_SHIFT = 1e-5     # test_spatial_transformer_pre_chain_equals_launches: x * scale + shift against GroupNorm
 BOUND_LINCOMB = 1e-6            # test_sampler_arithmetic_bit_exact: lincomb4 against fp64
 BOUND_SMALL_COUT = 2e-5         # test_conv_small_cout_matrix_core_form: fp32 NCHW output of 16-bit operands
 BOUND_SMALL_CIN_F32 = 2e-6      # test_small_convs: conv_small_cin with out_f32_nchw
@@ -84,7 +94,8 @@ LAUNCH_KINDS = {"mobi_igemm": "igemm", "mobi_igemm_finish": "split_finish", "mob
                 "mobi_ff_geglu": "ff_geglu", "mobi_two_key_adapter": "two_key_adapter", "mobi_softmax_rows": "softmax_rows",
                 "mobi_split_f32": "split_f32", "mobi_trunk_add": "trunk_add", "mobi_lincomb4": "lincomb4",
                 "mobi_conv_small_cout": "conv_small_cout", "mobi_conv_small_cin": "conv_small_cin",
-                "mobi_pack_nchw_sources": "pack_sources",
+                "mobi_pack_nchw_sources": "pack_sources", "mobi_row_chain": "row_chain",
+                "mobi_row_chain_adapter_image": "chain_adapter_image", "mobi_groupnorm_scale_shift": "groupnorm_scale_shift",
                 # the conditioning producer's and the realism networks' (LaunchShadow(extra=...))
                 "mobi_skinny_linear": "skinny_linear", "mobi_layernorm_rows_f32": "layernorm_rows_f32",
                 "mobi_linear_f32": "linear_f32", "mobi_quick_gelu": "quick_gelu", "mobi_image_normalize": "image_normalize",
@@ -95,7 +106,7 @@ EXTRA_KINDS = ("skinny_linear", "layernorm_rows_f32", "linear_f32", "quick_gelu"
                "lpips_distance", "row_cosine", "feature_moments", "frd_input", "band_mean")
 # entry points that answer a question and launch nothing (mobi_tile_weights: the load-time weight image of a pack)
 QUERY_SUFFIXES = ("_workspace_bytes", "_plan_splits", "_slab_count", "_kernel_variant", "_takes_split", "_sync_bytes",
-                  "_supported", "_fuses_ln", "_packed_bytes", "_weight_bytes", "_ws_floats")
+                  "_supported", "_fuses_ln", "_packed_bytes", "_weight_bytes", "_image_bytes", "_ws_floats")
 QUERY_NAMES = ("mobi_tile_weights", "mobi_error_string", "mobi_build_info", "mobi_abi_version", "mobi_struct_size")
 
 
@@ -506,7 +517,8 @@ class LaunchShadow:
     through the library while the shadow ran) and `sh.census_failures()`."""
 
     WRAPPED = ("igemm", "groupnorm", "layernorm", "attention", "ctx_attention", "ff_geglu", "two_key_adapter", "softmax_rows",
-               "split_f32", "trunk_add", "lincomb4", "conv_small_cout", "conv_small_cin", "pack_sources")
+               "split_f32", "trunk_add", "lincomb4", "conv_small_cout", "conv_small_cin", "pack_sources", "row_chain",
+               "chain_adapter_image", "groupnorm_scale_shift")
 
     def __init__(self, monkeypatch, verbose=False, label="", cpu_check=True, seed=0, extra=()):
         from mobi_amd import ops
@@ -519,6 +531,7 @@ class LaunchShadow:
         self.cpu_checked = set()
         self.pending = {}
         self.thin = {}                  # data_ptr of a pack_sources output -> its number of sources
+        self.adapter_images = []        # per chain_adapter_image call: clones of the fp32 tables and of the returned image
         self.gen = torch.Generator().manual_seed(seed)
 
     def census_failures(self):
@@ -550,6 +563,7 @@ class LaunchShadow:
         for k in self.wrapped:
             self.mp.setattr(ops, k, (lambda name: lambda *a, **kw: getattr(sh, "_" + name)(orig[name], *a, **kw))(k))
         self.mp.setattr(ops.Deferred, "finish", lambda d: sh._finish(orig_finish, d))
+        self.mp.setattr(ops, "ChainProgram", chain_ref.recording_program())      # (builds what ops.ChainProgram builds)
         census = LibCensus(_lib.load(), self.calls)
         self.mp.setattr(_lib, "load", lambda: census)
         return self
@@ -818,6 +832,103 @@ class LaunchShadow:
                 want = layernorm_rows(ref[i::2], g, bb, ln_eps)
                 self._judge("two_key_adapter", tag, got, want, TOL[x.dtype], extra=f"ln_pair[{i}]")
         return r
+
+    # -- row chains ------------------------------------------------------------------------------------------------------
+    def _chain_adapter_image(self, orig, a, c, u, b, dtype, out=None):
+        snaps = dict(a=_snap(a), c=_snap(c), u=_snap(u), b=_snap(b))
+        outside = OutsideView(out) if out is not None else None
+        image = orig(a, c, u, b, dtype, out=out)
+        torch.cuda.synchronize()
+        self._count("chain_adapter_image")
+        tag = f"chain_adapter_image n={a.shape[0]} heads={a.shape[1]}"
+        self._inputs_unchanged(tag, [(k, t, snaps[k]) for k, t in (("a", a), ("c", c), ("u", u), ("b", b))])
+        if outside is not None and not outside.unchanged():
+            self._fail(f"{tag}: wrote outside its out view")
+        self.adapter_images.append(dict(snaps, image=image.detach().clone(), dtype=dtype))      # judged through the launches that use it
+        return image
+
+    def adapter_tables(self, image, dtype):
+        """The fp32 tables of the chain_adapter_image call whose image has this content (latest first), or None."""
+        for rec in reversed(self.adapter_images):
+            if rec["dtype"] == dtype and rec["image"].shape == image.shape and torch.equal(rec["image"], image):
+                return rec
+        return None
+
+    def _groupnorm_scale_shift(self, orig, x, gamma, beta, eps):
+        snap = _snap(x)
+        scale, shift = orig(x, gamma, beta, eps)
+        torch.cuda.synchronize()
+        self._count("groupnorm_scale_shift")
+        n, c = x.shape[0], x.shape[-1]
+        tag = f"n={n} hw={x.numel() // (n * c)} c={c}"
+        self._inputs_unchanged("groupnorm_scale_shift " + tag, [("x", x, snap)])
+        op = dict(x=snap, x2=None, gamma=gamma, beta=beta, eps=eps, silu=False)
+        ref = groupnorm_reference(op)
+        self._cpu_agree("groupnorm_scale_shift " + tag, groupnorm_reference, op, ref, ref.shape[0] * ref.shape[1])
+        got = snap.double().reshape(n, -1, c) * scale.double()[:, None, :] + shift.double()[:, None, :]
+        self._judge("groupnorm_scale_shift", tag, got, ref, BOUND_GN_SCALE_SHIFT)
+        return scale, shift
+
+    def _row_chain(self, orig, programs, images, rows_per_image, dtype, adapter=None, flops=0.0, nbytes=0.0, note=""):
+        what = f"row_chain {note}".strip()
+        descs = [getattr(p, "desc", None) for p in programs]
+        if any(d is None for d in descs):
+            self._fail(f"{what}: a program that was not built through ops.ChainProgram while the shadow ran")
+            descs = None
+        tables = None
+        if descs is not None:
+            snaps, memo = chain_ref.snapshot(descs)
+            if adapter is not None:
+                image_before = adapter[0].detach().clone()
+                rec = self.adapter_tables(image_before, dtype)
+                if rec is None:
+                    self._fail(f"{what}: the adapter image matches no chain_adapter_image call the shadow saw")
+                else:
+                    tables = dict(a=rec["a"], c=rec["c"], u=rec["u"], b=rec["b"], eps=adapter[1])
+        orig(programs, images, rows_per_image, dtype, adapter=adapter, flops=flops, nbytes=nbytes, note=note)
+        torch.cuda.synchronize()
+        self._count("row_chain")
+        if descs is None or (adapter is not None and tables is None):
+            return
+        tag = note.split()[0] if note.split() else "unnamed"
+        dev = next(v.device for desc in descs for _, kw in desc for v in kw.values() if torch.is_tensor(v))
+        results = chain_ref.run_launch(snaps, images, rows_per_image, dtype, tables, dev=dev)
+        if not results:
+            self._fail(f"{what}: the launch stores nothing")
+        key = f"row_chain {tag} {len(descs)} programs"
+        if self.cpu_check and key not in self.cpu_checked:
+            self.cpu_checked.add(key)
+            self._chain_cpu_agree(key, snaps, images, rows_per_image, dtype, tables, results)
+        for rec in results:
+            form = f"prog{rec['prog']} op{rec['index']} {rec['code']}"
+            if rec["code"] == "product":
+                form += " " + chain_ref.flag_name(rec["flags"])
+            bound = TOL[dtype] * (1.5 if rec["code"] == "product" and rec["flags"] & 1 else 1.0)
+            self._judge("row_chain", f"{tag} rows={images * rows_per_image}", chain_ref.as_images(chain_ref.stored_rows(rec), rows_per_image),
+                        chain_ref.as_images(rec["ref"], rows_per_image), bound, extra=form,
+                        form=dict(note=tag, code=rec["code"], flags=rec["flags"], programs=len(descs), images=images, rows=rows_per_image))
+        for msg in chain_ref.changed_inputs(descs, snaps):
+            self._fail(f"{what}: input changed: {msg}")
+        for msg in chain_ref.touched_outside(results, memo):
+            self._fail(f"{what}: {msg}")
+        if adapter is not None and not torch.equal(adapter[0], image_before):
+            self._fail(f"{what}: the adapter image changed")
+
+    def _chain_cpu_agree(self, key, snaps, images, rows_per_image, dtype, tables, results):
+        """First launch of a tag: 64 (image, row) pairs (first, last, 62 random) through the interpreter on the CPU."""
+        total = images * rows_per_image
+        rnd = torch.randperm(max(total - 2, 1), generator=self.gen)[:CPU_ROWS - 2] + 1
+        flat = torch.unique(torch.cat([torch.tensor([0, total - 1]), rnd.clamp(max=total - 1)]))
+        cpu = chain_ref.run_launch(snaps, images, rows_per_image, dtype, tables, sel=(flat // rows_per_image, flat % rows_per_image),
+                                   dev=torch.device("cpu"))
+        step = 1 if len(snaps) == 1 else 2
+        for c, d in zip(cpu, results):
+            pos = (c["img"] // step) * rows_per_image + c["row"]           # image-major over the images the program ran
+            dref = d["ref"][pos.to(d["ref"].device)].cpu()
+            err = float((c["ref"] - dref).norm() / c["ref"].norm().clamp_min(1e-300))
+            if not err <= CPU_AGREE:
+                self._fail(f"{key} prog{c['prog']} op{c['index']}: device fp64 reference disagrees with the CPU on {pos.numel()} rows: "
+                           f"{err:.3e}")
 
     # -- the VAEs' entry points ------------------------------------------------------------------------------------------
     def _softmax_rows(self, orig, s, dtype):

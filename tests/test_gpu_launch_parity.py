@@ -5,10 +5,13 @@ the guidance batch of the shipped PLMS / CFG-5 invocation (64 x 64, batch 32: [u
 each in fp16 and bf16 storage, on the full-width net of tests/test_gpu_production.py.
 
   * launch shadow (tests/launch_shadow.py): every igemm / split-K reduce / GroupNorm / LayerNorm / attention / ff_geglu /
-    two-key-adapter launch of one forward against a float64 restatement of its contract on the operands it read, within the
-    bound its unit test in tests/test_gpu_ops.py asserts, its worst 128 x 64 tile within 4x that, finite, inputs and the
-    storage outside its view untouched; the shadow must have seen every launch the profiler saw (row_chain aside: its
-    operations are covered below);
+    two-key-adapter / row_chain launch of one forward against a float64 restatement of its contract on the operands it read,
+    within the bound its unit test in tests/test_gpu_ops.py (tests/test_gpu_chain.py for a chain's products) asserts, its
+    worst 128 x 64 tile within 4x that, finite, inputs and the storage outside its view untouched; the shadow must have seen
+    every launch the profiler saw.  A row_chain launch is judged per stored tensor against tests/chain_ref.py, the fp64
+    interpreter of the chain program it ran; the two 64 x 64 configurations run post_attn1 and post_cam launches, the
+    32 x 32 one sits below ROW_CHAIN_MIN_ROWS and runs none; pre_attn1 (MOBI_PRE_CHAIN) and groupnorm_scale_shift are judged
+    on one SpatialTransformer at the row threshold;
   * block shadow: a second forward with ops.DEFER_SPLIT = False (bit-identical, test_full_width_forward_vs_oracle) whose
     every input / middle / output block is compared with oracle/unet.py::_run_block on the block's engine input, in float64
     on the device, pair by pair, with the fp32 master weights: row_chain, its adapter image, the routing thresholds and the
@@ -75,9 +78,13 @@ def _launch_run(dtype, name):
 def test_launch_shadow(dtype, name):
     r = _launch_run(dtype, name)
     for kind, count in r["kinds"].items():
-        if kind != "row_chain":
-            assert r["counts"].get(kind, 0) == count, (kind, count, r["counts"])
+        assert r["counts"].get(kind, 0) == count, (kind, count, r["counts"])
     assert r["counts"].get("igemm", 0) > 0 and r["counts"].get("attention", 0) > 0
+    notes = collections.Counter(rec["form"]["note"] for rec in r["records"] if rec["kind"] == "row_chain")
+    if CONFIGS[name][0] == 64:
+        assert notes["post_attn1"] > 0 and notes["post_cam"] > 0 and r["counts"].get("chain_adapter_image", 0) > 0, notes
+    else:                                                      # 8 x 1,024 token rows: below ROW_CHAIN_MIN_ROWS
+        assert not notes and r["counts"].get("row_chain", 0) == 0, notes
     assert not r["failures"], "\n".join(r["failures"][:40])
 
 
@@ -99,6 +106,9 @@ def test_launch_shadow_covers_the_routing():
             fam += " (split-K slabs)"
         if rec["kind"] == "attention":
             fam += " dh=" + rec["tag"].split("dh=")[1].split()[0]
+        if rec["kind"] == "row_chain":
+            folded = rec["form"]["code"] == "product" and rec["form"]["flags"] & 1        # judged at 1.5 TOL
+            fam += " " + rec["form"]["note"] + (" (folded product)" if folded else "")
         key = (name, _dname(dtype), fam)
         w = worst.setdefault(key, [0.0, 0.0, 0, rec["bound"]])
         w[0], w[1], w[2] = max(w[0], rec["rel"]), max(w[1], rec["tile"]), w[2] + 1
@@ -111,6 +121,36 @@ def test_launch_shadow_covers_the_routing():
     if path:
         with open(path, "w") as f:
             f.write("\n".join(lines) + "\n")
+
+
+@pytest.mark.parametrize("dtype", DT, ids=_dname)
+def test_launch_shadow_pre_chain_spatial_transformer(dtype, monkeypatch):
+    """One SpatialTransformer at C = 320 on 6 x 64 x 64 (24,576 token rows: the threshold) with PRE_CHAIN on: the shadow judges
+    a pre_attn1, a post_attn1 and a post_cam launch and the GroupNorm scale / shift pass, and the census has seen no call of a
+    chain entry point that the shadow did not judge."""
+    import mobi_amd
+    from mobi_amd.ldm.modules import attention as A
+    from tests.test_gpu_ops import rnd
+    mobi_amd.set_engine_dtype(dtype)
+    st = A.SpatialTransformer(320, 8, 40, depth=1, context_dim=768, bbox_cond=True, multimodal=True)
+    W.fill_module_(st, seed=53)
+    st = st.cuda()
+    n, side = 6, 64
+    _, x = rnd("parity.st.x", (n, side, side, 320), dtype, 1.5)
+    ctx = W.synth_input("parity.st.ctx", (n, 2, 768)).cuda()
+    monkeypatch.setattr(A, "PRE_CHAIN", True)
+    assert n * side * side == A.ROW_CHAIN_MIN_ROWS and st._pre_chain_ok(x)
+    with LaunchShadow(monkeypatch, verbose=True, label=f"st320 {_dname(dtype)}") as sh, torch.no_grad():
+        st(x, context=ctx)
+    torch.cuda.synchronize()
+    assert not sh.failures, "\n".join(sh.failures[:40])
+    notes = {rec["form"]["note"] for rec in sh.records if rec["kind"] == "row_chain"}
+    assert notes == {"pre_attn1", "post_attn1", "post_cam"}, notes
+    assert sh.counts.get("groupnorm_scale_shift", 0) == 1 and sh.counts.get("chain_adapter_image", 0) == 1
+    assert any(rec["kind"] == "groupnorm_scale_shift" for rec in sh.records)
+    chain_entry = [m for m in sh.census_failures() if "row_chain" in m or "groupnorm_scale_shift" in m]
+    assert not chain_entry, chain_entry
+    assert sh.calls.get("mobi_row_chain", 0) == sh.counts["row_chain"] == 3
 
 
 # ---- block shadow ------------------------------------------------------------------------------------------------------

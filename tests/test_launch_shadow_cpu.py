@@ -431,3 +431,64 @@ def test_extra_kinds_are_opt_in_and_counted_per_library_call():
     assert sh.census_failures() == []
     lib.mobi_quick_gelu(None)
     assert [m for m in sh.census_failures() if m.startswith("mobi_quick_gelu: 1 calls, 0 judged")]
+
+
+# ---- row chains -----------------------------------------------------------------------------------------------------------
+def test_chain_kinds_are_wrapped_and_counted():
+    """row_chain, chain_adapter_image and groupnorm_scale_shift are launch kinds of the default set; the image-size query is
+    query-only, the image launch is not; an unjudged chain launch is a census failure."""
+    class MP:
+        pass
+    for kind, name in (("row_chain", "mobi_row_chain"), ("chain_adapter_image", "mobi_row_chain_adapter_image"),
+                       ("groupnorm_scale_shift", "mobi_groupnorm_scale_shift")):
+        assert ls.LAUNCH_KINDS[name] == kind and kind in ls.LaunchShadow.WRAPPED and hasattr(ls.LaunchShadow, "_" + kind)
+    assert ls.is_query_only("mobi_row_chain_adapter_image_bytes") and ls.is_query_only("mobi_row_chain_weight_bytes")
+    assert ls.is_query_only("mobi_row_chain_supported") and not ls.is_query_only("mobi_row_chain_adapter_image")
+
+    class Lib:
+        def __getattr__(self, name):
+            return lambda *a: 0
+    sh = ls.LaunchShadow(MP())
+    lib = ls.LibCensus(Lib(), sh.calls)
+    lib.mobi_row_chain(None)
+    lib.mobi_row_chain_adapter_image_bytes(320)
+    assert [m for m in sh.census_failures() if m.startswith("mobi_row_chain: 1 calls, 0 judged")]
+    sh._count("row_chain")
+    assert sh.census_failures() == []
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_row_chain_wrapper_judges_an_emulated_launch(dtype, monkeypatch):
+    """The shadow's row_chain wrapper around an fp32 emulation of the kernel (tests/chain_cases.py): the clean launch passes
+    with one record per stored tensor under the launch's note; a launch with products 0 and 1 swapped fails; the adapter's
+    tables are found by the CONTENT of the image (a copy in another buffer matches), and an image no chain_adapter_image call
+    produced is a failure."""
+    from tests import chain_cases as cc, chain_ref
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a: None)
+
+    class MP:
+        pass
+
+    def run(defect, image_of, note="post_attn1 rows=1024"):
+        case = cc.build_case("post_attn1-4x256", dtype, "cpu", chain_ref.ProgramDescription)
+        sh = ls.LaunchShadow(MP(), label="cpu")
+        tb = case.tables
+        made = torch.arange(4 * 64, dtype=torch.int64).view(4, 64).to(torch.uint8)       # stands in for the image's bytes
+        sh.adapter_images.append(dict(a=tb["a"], c=tb["c"], u=tb["u"], b=tb["b"], image=made.clone(), dtype=dtype))
+        sh.adapter_images.append(dict(a=tb["a"] * 2, c=tb["c"], u=tb["u"], b=tb["b"], image=made.clone() + 1, dtype=dtype))
+        orig = lambda programs, images, rows, dt, adapter=None, flops=0.0, nbytes=0.0, note="": cc.emulate(case, defect)
+        sh._row_chain(orig, case.programs, case.images, case.rows, dtype, adapter=(image_of(made), tb["eps"]), note=note)
+        return sh
+
+    sh = run(None, lambda made: made.clone())
+    assert sh.failures == [] and sh.counts == {"row_chain": 1}
+    assert len(sh.records) == 6 and all(r["kind"] == "row_chain" and r["form"]["note"] == "post_attn1" for r in sh.records)
+    assert sorted(r["bound"] for r in sh.records) == sorted([TOL[dtype]] * 4 + [1.5 * TOL[dtype]] * 2)
+    sh = run("swap_weights", lambda made: made.clone())
+    assert sh.failures and sh.counts == {"row_chain": 1}
+    sh = run(None, lambda made: made.clone() + 7)
+    assert len(sh.failures) == 1 and "matches no chain_adapter_image call" in sh.failures[0] and sh.counts == {"row_chain": 1}
+    # a program that did not come from the recording class cannot be judged: a failure, not a silent pass
+    sh = ls.LaunchShadow(MP(), label="cpu")
+    sh._row_chain(lambda *a, **kw: None, [object()], 2, 128, dtype)
+    assert len(sh.failures) == 1 and "not built through ops.ChainProgram" in sh.failures[0]
