@@ -40,15 +40,36 @@ x sigmoid(1.702 x) in fp32 rounded once to T, so its rel-L2 AND its worst tile a
 `extra` the wrapped set is the UNet's and the VAEs' (WRAPPED), as before.  An igemm with `leaky` (MOBI_EPI_LEAKY_RELU) is judged
 like any igemm: leaky_relu(., 0.1) after bias and rowvec, before the residual.
 
+`LaunchShadow(monkeypatch, extra=TRAIN_KINDS + (...))` wraps the entry points the training step adds (mobi_amd/train.py:
+unet_forward, unet_backward, loss_and_gradients, bbox_embedder_forward / _backward): transpose, colsum, layernorm_bwd,
+groupnorm_bwd, geglu_fwd, geglu_bwd, attention_bwd, sumpool2, silu_bwd_f32, loss_grad and timestep_embedding.  Their references
+are the ones the kernels' unit tests trust -- tests/backward_ref.py (`*_ref`, float64, on the CPU: every operand of a step at a
+16 x 16 latent is small), tests/loss_grad_ref.py, oracle/unet.py's timestep_embedding -- and their bounds those tests' own (TOL1,
+TOL_SUM, TOL_DGAMMA, REL; 1.5 TOL1 for an attention_bwd launch that backward_ref.attention_bwd_route sends to the matrix cores
+with the strides and pointers the call passed).  The judgement of each kind is a plain function of CPU tensors (`*_checks`, as
+check_split is) that returns Check records; the wrapper only snapshots, runs and records.  attention_bwd has one record per
+output (dq, dk, dv); fp32 vectors / matrices are judged by rel-L2 with backward_ref.row_measure(block=64) recorded beside it.
+`ops.linear_wgrad` and `ops.linear` need no wrapper: they call the MODULE's transpose / igemm / linear_f32 (`transpose(dy)`,
+`igemm(...)`, `linear_f32(...)` are looked up in mobi_amd.ops' globals at call time), which are the patched ones -- a weight
+gradient is a transpose pair and an OUT_ROWS_F32 igemm record (k = the token rows), or a linear_f32 record; the census proves it
+(an unjudged mobi_transpose / mobi_igemm / mobi_linear_f32 call is a failure).  `add` stays bit-exact against the rounded fp32
+sum (its unit test's own assertion; stricter than TOL1).  An igemm record's form says whether its source, its output and its
+residual had a non-dense image stride (src_strided, out_strided, res_strided) and whether a 3 x 3 launch read a zero-spread
+input (the stride-2 data gradient).
+
 Nothing here calls a `mobi_*` entry point: the references are torch float64 (matmul per tap, attention per image and head).
 """
+import collections
 import math
 
 import torch
 import torch.nn.functional as F
 
-from tests import chain_ref
+from tests import backward_ref as R, chain_ref, loss_grad_ref
 from tests.golden_cases import record
+from tests.test_gpu_backward import TOL1
+from tests.test_gpu_backward_geometry import TOL_DGAMMA, TOL_SUM
+from tests.test_gpu_loss_grad import REL
 from tests.test_gpu_ops import TOL
 
 LN2 = math.log(2.0)
@@ -85,6 +106,7 @@ BOUND_LPIPS_DISTANCE = 1e-6     # test_layer_distance_against_fp64: max relative
 BOUND_ROW_COSINE = 1e-6         # test_row_cosine_against_fp64: |d| / max(|ref|, 1)
 BOUND_MOMENTS = 1e-15           # test_moments_against_fp64_and_reproducible (fp64 sums)
 BOUND_BAND_MEAN = 4.5e-7        # test_band_mean_against_fp64: max |d| / max |ref|
+BOUND_TIMESTEP = 1e-6           # test_skinny_linear_and_timestep_embedding: rel-L2 against oracle/unet.py's fp32 restatement
 UNIT_ROUNDOFF = {torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}      # quick_gelu: one rounding of an fp32 value to T
 QUICK_GELU_ALPHA = 1.702
 
@@ -101,13 +123,21 @@ LAUNCH_KINDS = {"mobi_igemm": "igemm", "mobi_igemm_finish": "split_finish", "mob
                 "mobi_linear_f32": "linear_f32", "mobi_quick_gelu": "quick_gelu", "mobi_image_normalize": "image_normalize",
                 "mobi_maxpool3s2": "maxpool3s2", "mobi_add": "add", "mobi_lpips_distance": "lpips_distance",
                 "mobi_row_cosine": "row_cosine", "mobi_feature_moments": "feature_moments", "mobi_frd_input": "frd_input",
-                "mobi_band_mean": "band_mean"}
+                "mobi_band_mean": "band_mean",
+                # the training step's (LaunchShadow(extra=TRAIN_KINDS + ...))
+                "mobi_transpose": "transpose", "mobi_colsum": "colsum", "mobi_layernorm_bwd": "layernorm_bwd",
+                "mobi_groupnorm_bwd": "groupnorm_bwd", "mobi_geglu_fwd": "geglu_fwd", "mobi_geglu_bwd": "geglu_bwd",
+                "mobi_attention_bwd": "attention_bwd", "mobi_sumpool2": "sumpool2", "mobi_silu_bwd_f32": "silu_bwd_f32",
+                "mobi_loss_grad": "loss_grad", "mobi_timestep_embedding": "timestep_embedding"}
 EXTRA_KINDS = ("skinny_linear", "layernorm_rows_f32", "linear_f32", "quick_gelu", "image_normalize", "maxpool3s2", "add",
                "lpips_distance", "row_cosine", "feature_moments", "frd_input", "band_mean")
+TRAIN_KINDS = ("transpose", "colsum", "layernorm_bwd", "groupnorm_bwd", "geglu_fwd", "geglu_bwd", "attention_bwd", "sumpool2",
+               "silu_bwd_f32", "loss_grad", "timestep_embedding")
 # entry points that answer a question and launch nothing (mobi_tile_weights: the load-time weight image of a pack)
 QUERY_SUFFIXES = ("_workspace_bytes", "_plan_splits", "_slab_count", "_kernel_variant", "_takes_split", "_sync_bytes",
-                  "_supported", "_fuses_ln", "_packed_bytes", "_weight_bytes", "_image_bytes", "_ws_floats")
-QUERY_NAMES = ("mobi_tile_weights", "mobi_error_string", "mobi_build_info", "mobi_abi_version", "mobi_struct_size")
+                  "_supported", "_fuses_ln", "_packed_bytes", "_weight_bytes", "_image_bytes", "_ws_floats", "_workspace_floats")
+QUERY_NAMES = ("mobi_tile_weights", "mobi_error_string", "mobi_build_info", "mobi_abi_version", "mobi_struct_size",
+               "mobi_backward_partial_blocks", "mobi_loss_grad_blocks_per_sample")
 
 
 def is_query_only(name):
@@ -237,6 +267,16 @@ def per_image_weights(w, n, n_packed, k, w_group_stride):
 
 def _snap(t):
     return None if t is None else t.detach().clone()
+
+
+def _host(t):
+    """The CPU copy of an operand: what the training kinds' references (tests/backward_ref.py: CPU torch) read."""
+    return None if t is None else t.detach().cpu()
+
+
+def _img_strided(t):
+    """A batch-strided view (`x[::2]`): more than one image and an image stride that is not the dense one."""
+    return t.shape[0] > 1 and t.stride(0) != t[0].numel()
 
 
 def _tag_int(tag, key, default):
@@ -509,6 +549,166 @@ def conv_small_cin_op(srcs, weight, bias, kh, kw, pad):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# the training step's launches: plain judgements of CPU tensors (the operands a launch read, what it wrote) -> Check records
+# ------------------------------------------------------------------------------------------------------------------
+# mode "tiles": got / ref [images, rows, channels] through `compare` (rel-L2 < bound, worst tile < 4x bound); "value": an fp32
+# vector / matrix, rel-L2 < bound with backward_ref.row_measure(block=64) beside it; "exact": bit for bit; "figure": `got` is an
+# error figure already (<= bound); "fault": a broken contract, `got` says which
+Check = collections.namedtuple("Check", "what mode got ref bound")
+
+
+def evaluate(ck):
+    """-> dict(rel, tile, where, finite, row, ok) of one Check."""
+    if ck.mode == "tiles":
+        res = compare(ck.got, ck.ref)
+        return dict(res, row=None, ok=passes(res, ck.bound))
+    if ck.mode == "value":
+        finite = bool(torch.isfinite(ck.got).all())
+        rel = R.rel_l2(ck.got, ck.ref) if finite else float("inf")
+        row = R.row_measure(ck.got, ck.ref, block=64) if finite else float("inf")
+        return dict(rel=rel, tile=rel, where=(0, 0, 0), finite=finite, row=row, ok=finite and rel < ck.bound)
+    if ck.mode == "exact":
+        ok = ck.got.dtype == ck.ref.dtype and _same(ck.got, ck.ref)
+        err = 0.0 if ok else float("inf")
+        return dict(rel=err, tile=err, where=(0, 0, 0), finite=bool(torch.isfinite(ck.got.float()).all()), row=None, ok=ok)
+    if ck.mode == "figure":
+        ok = ck.got <= ck.bound                                   # (a NaN figure fails)
+        return dict(rel=ck.got, tile=ck.got, where=(0, 0, 0), finite=math.isfinite(ck.got), row=None, ok=ok)
+    return dict(rel=float("inf"), tile=float("inf"), where=(0, 0, 0), finite=True, row=None, ok=False)      # "fault"
+
+
+def check_failures(kind, tag, checks):
+    """The failure strings of a launch's checks, each naming the launch (kind, tag) and the output."""
+    bad = []
+    for ck in checks:
+        res = evaluate(ck)
+        if res["ok"]:
+            continue
+        if ck.mode == "fault":
+            bad.append(f"{kind} {tag}: {ck.got}")
+        elif ck.mode == "exact":
+            bad.append(f"{kind} {tag} {ck.what}: not the restatement bit for bit")
+        else:
+            bad.append(f"{kind} {tag} {ck.what}: rel-L2 {res['rel']:.3e}, worst tile {res['tile']:.3e} at {res['where']}, finite "
+                       f"{res['finite']} (bound {ck.bound:.1e})")
+    return bad
+
+
+def describe(**tensors):
+    """name=shape/strides of every tensor given: what a failure string says about the operands."""
+    return " ".join(f"{k}={tuple(t.shape)}/{tuple(t.stride())}" for k, t in tensors.items() if t is not None)
+
+
+def _images(t):
+    return t.reshape(t.shape[0], -1, t.shape[-1])
+
+
+def transpose_checks(x, out):
+    """mobi_transpose: out == x^T bit for bit (tests/test_gpu_backward_geometry.py::test_transpose_and_tile_weights_bit_exact)."""
+    if tuple(out.shape) != (x.shape[1], x.shape[0]):
+        return [Check("out", "fault", f"shape {tuple(out.shape)}", None, 0.0)]
+    return [Check("out", "exact", out, x.t().contiguous(), 0.0)]
+
+
+def colsum_checks(dy, out):
+    return [Check("out", "value", out, R.colsum_ref(dy), TOL_SUM)]
+
+
+def layernorm_bwd_checks(x, dy, gamma, eps, dx_add, dx, dgamma, dbeta):
+    """x, dy, dx_add, dx [N, T, C]; gamma, dgamma, dbeta [C]."""
+    c = x.shape[-1]
+    rows = lambda t: None if t is None else t.reshape(-1, c)
+    rdx, rdg, rdb = R.layernorm_bwd_ref(rows(x), rows(dy), gamma, eps, dx_add=rows(dx_add))
+    return [Check("dx", "tiles", dx, rdx.reshape(x.shape), TOL1[x.dtype]), Check("dgamma", "value", dgamma, rdg, TOL_DGAMMA),
+            Check("dbeta", "value", dbeta, rdb, TOL_DGAMMA)]
+
+
+def groupnorm_bwd_checks(x, dy, gamma, beta, eps, silu, dx_add, dx):
+    """x, dy, dx_add, dx [N, H, W, C]."""
+    ref = R.groupnorm_bwd_ref(_images(x), _images(dy), gamma, beta, eps, silu, dx_add=None if dx_add is None else _images(dx_add))
+    return [Check("dx", "tiles", _images(dx), ref, TOL1[x.dtype])]
+
+
+def geglu_fwd_checks(pre, h):
+    return [Check("h", "tiles", _images(h), _images(R.geglu_fwd_ref(pre)), TOL1[pre.dtype])]
+
+
+def geglu_bwd_checks(pre, dh, dpre):
+    return [Check("dpre", "tiles", _images(dpre), _images(R.geglu_bwd_ref(pre, dh)), TOL1[pre.dtype])]
+
+
+def attention_bwd_checks(q, k, v, dout, heads, scale, route, dq, dk, dv):
+    """q, dout, dq [N, Tq, C]; k, v, dk, dv [N, Tk, C]; route: what backward_ref.attention_bwd_route says of the call."""
+    bound = TOL1[q.dtype] * (1.5 if route == "mfma" else 1.0)
+    ref = R.attention_bwd_ref(q, k, v, dout, heads, scale)
+    return [Check(nm, "tiles", got, want, bound) for nm, got, want in zip(("dq", "dk", "dv"), (dq, dk, dv), ref)]
+
+
+def attention_bwd_diagnosis(q, k, v, dout, heads, scale, dtype, ref):
+    """For a failure string: rel-L2 of both storage restatements (backward_ref.attention_bwd_restated) against the same float64
+    reference, the share of dout and of the reference dq below the smallest fp16 normal, and the keys' common component."""
+    parts = []
+    for route in ("mfma", "vector"):
+        rs = R.attention_bwd_restated(q, k, v, dout, heads, scale, dtype, route)
+        parts.append(f"restated {route}: " + " ".join(f"{nm} {R.rel_l2(g, w):.3e}" for nm, g, w in zip(("dq", "dk", "dv"), rs, ref)))
+    # the same restatement with dout x 256 (a power of two: exact) and the result / 256: what dS would keep above fp16's subnormals
+    rs = R.attention_bwd_restated(q, k, v, (dout.float() * 256.0).to(dtype), heads, scale, dtype, "mfma")
+    parts.append("restated mfma on dout x 256: " + " ".join(f"{nm} {R.rel_l2(g / 256.0, w):.3e}" for nm, g, w in zip(("dq", "dk", "dv"), rs, ref)))
+    tiny = lambda t: float((t.double().abs() < 2.0 ** -14).double().mean())
+    kd = k.double()
+    offset = float(kd.mean(1).norm() / (kd - kd.mean(1, keepdim=True)).pow(2).mean(1).sum(-1).sqrt().mean().clamp_min(1e-300))
+    parts.append(f"below 2^-14: dout {tiny(dout):.2f} dq {tiny(ref[0]):.2f}; rms dout {float(dout.double().pow(2).mean().sqrt()):.2e}; "
+                 f"keys' common component / spread {offset:.2f}")
+    return "; ".join(parts)
+
+
+def sumpool2_checks(src, out):
+    return [Check("out", "tiles", _images(out), _images(R.sumpool2_ref(src)), TOL1[src.dtype])]
+
+
+def silu_bwd_f32_checks(z, dy, dx):
+    return [Check("dx", "value", dx, R.silu_bwd_ref(z, dy), TOL_SUM)]
+
+
+def _max_relative(got, want):
+    """max |got - want| / |want|, 0 where both are exactly 0 (loss_vlb of the default objective's zero tables)."""
+    got, want = got.double(), want.double()
+    err = (got - want).abs() / want.abs()
+    err = torch.where((got == 0) & (want == 0), torch.zeros_like(err), err)
+    return float(err.max()) if bool(torch.isfinite(err).all()) else float("inf")
+
+
+def loss_grad_checks(eps, target, t, logvar, lvlb, kw, dtype, c_pad, dy, per_sample, terms):
+    """mobi_loss_grad as tests/test_gpu_loss_grad.py::test_kernel_against_the_contract asserts it: dy [N, H, W, c_pad] of the
+    storage type, exactly +0 beyond the channels; l1: the fp64 contract rounded once, bit for bit; l2: within one storage ulp of
+    the fp64 contract (the kernel forms k e - k g in fp32 before its one rounding); per_sample and terms within REL.
+    kw: loss_type, l_simple_weight, elbo_weight, loss_scale."""
+    n, c, h, w = eps.shape
+    if tuple(dy.shape) != (n, h, w, c_pad) or dy.dtype != dtype:
+        return [Check("dy", "fault", f"dy shape / dtype {tuple(dy.shape)} {dy.dtype}", None, 0.0)]
+    rdy, rper, rterms = loss_grad_ref.loss_grad_ref(eps, target, t, logvar, lvlb, **kw)
+    out = []
+    pad = dy[..., c:]
+    if bool((pad != 0).any()) or bool(torch.signbit(pad).any()):
+        out.append(Check("dy", "fault", f"dy is not +0 beyond the {c} out_channels", None, 0.0))
+    if kw["loss_type"] == "l1":
+        out.append(Check("dy", "exact", dy, loss_grad_ref.to_storage(rdy, dtype, c_pad), 0.0))
+    else:
+        over = (dy[..., :c].permute(0, 3, 1, 2).double() - rdy).abs() / loss_grad_ref.storage_ulp(rdy, dtype)
+        out.append(Check("dy (storage ulp)", "figure", float(over.max()) if bool(torch.isfinite(over).all()) else float("inf"), None, 1.0))
+    out.append(Check("per_sample", "figure", _max_relative(per_sample, rper), None, REL))
+    out.append(Check("terms", "figure", _max_relative(terms, rterms), None, REL))
+    return out
+
+
+def timestep_embedding_checks(t, freqs, out):
+    """As test_skinny_linear_and_timestep_embedding: rel-L2 against oracle/unet.py's timestep_embedding (fp32, max_period
+    10,000; it forms its own frequencies, so a wrong table shows)."""
+    from oracle.unet import timestep_embedding as ref_temb
+    return [Check("out", "value", out, ref_temb(t, 2 * freqs.shape[0]), BOUND_TIMESTEP)]
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # the shadow
 # ------------------------------------------------------------------------------------------------------------------
 class LaunchShadow:
@@ -520,14 +720,17 @@ class LaunchShadow:
                "split_f32", "trunk_add", "lincomb4", "conv_small_cout", "conv_small_cin", "pack_sources", "row_chain",
                "chain_adapter_image", "groupnorm_scale_shift")
 
-    def __init__(self, monkeypatch, verbose=False, label="", cpu_check=True, seed=0, extra=()):
+    def __init__(self, monkeypatch, verbose=False, label="", cpu_check=True, seed=0, extra=(), pinned=None):
         from mobi_amd import ops
         self.ops, self.mp, self.verbose, self.label, self.cpu_check = ops, monkeypatch, verbose, label, cpu_check
-        unknown = [k for k in extra if k not in EXTRA_KINDS]
+        unknown = [k for k in extra if k not in EXTRA_KINDS + TRAIN_KINDS]
         if unknown:
-            raise ValueError(f"launch shadow: no extra kinds {unknown} (EXTRA_KINDS)")
-        self.wrapped = self.WRAPPED + tuple(k for k in EXTRA_KINDS if k in extra)
+            raise ValueError(f"launch shadow: no extra kinds {unknown} (EXTRA_KINDS, TRAIN_KINDS)")
+        self.wrapped = self.WRAPPED + tuple(k for k in EXTRA_KINDS + TRAIN_KINDS if k in extra)
         self.records, self.failures, self.counts, self.calls = [], [], {}, {}
+        # {"<kind> #<ordinal of the launch among its kind> <output>": bound}: launches judged at a bound written down by name
+        # (an fp16 operand range finding; twice the storage restatement's own figure on the same operands)
+        self.pinned, self.pins_used = dict(pinned or {}), set()
         self.cpu_checked = set()
         self.pending = {}
         self.thin = {}                  # data_ptr of a pack_sources output -> its number of sources
@@ -572,6 +775,8 @@ class LaunchShadow:
         self.mp.undo()
         if exc[0] is None and self.pending:
             self.failures.append(f"{len(self.pending)} split-K launches whose partial sums nobody consumed")
+        for name in sorted(set(self.pinned) - self.pins_used) if exc[0] is None else ():
+            self._fail(f"pinned launch '{name}' did not run")
         return False
 
     def _tag(self, n0, kind):
@@ -605,7 +810,7 @@ class LaunchShadow:
         if not err <= CPU_AGREE:
             self._fail(f"{key}: device fp64 reference disagrees with the CPU on {rows.numel()} rows: {err:.3e}")
 
-    def _judge(self, kind, tag, got, ref, bound, extra="", form=None, tile_factor=TILE_FACTOR):
+    def _judge(self, kind, tag, got, ref, bound, extra="", form=None, tile_factor=TILE_FACTOR, detail=""):
         res = compare(got, ref)
         ok = res["finite"] and res["rel"] < bound and res["tile"] < tile_factor * bound
         rec = dict(kind=kind, tag=tag, bound=bound, extra=extra, form=form or {}, **res)
@@ -618,7 +823,7 @@ class LaunchShadow:
                   f"at(img,row,col)={res['where']} bound={bound:.1e}{'' if ok else '  FAIL'}")
         if not ok:
             self._fail(f"{name}: rel-L2 {res['rel']:.3e}, worst tile {res['tile']:.3e} at {res['where']}, finite "
-                       f"{res['finite']} (bound {bound:.1e}, tile bound {tile_factor * bound:.1e})")
+                       f"{res['finite']} (bound {bound:.1e}, tile bound {tile_factor * bound:.1e})" + (f" [{detail}]" if detail else ""))
         return res
 
     # -- igemm ---------------------------------------------------------------------------------------------------------
@@ -677,8 +882,13 @@ class LaunchShadow:
         got = y.transpose(1, 2) if out_mode == ops.OUT_TRANSPOSED else y.reshape(n, ho * wo, cout)
         form = dict(per_image=weight_per_image, out_mode=out_mode, upsample=upsample, stride=stride, pad=(ph, pw_), hin=hin,
                     win=win, hout=ho, wout=wo, cin=pw.cin, kh=pw.kh, kw=pw.kw, thin=self.thin.pop(x.data_ptr(), 0), leaky=leaky,
-                    residual=residual is not None, k=pw.kh * pw.kw * pw.cin, m=n * ho * wo, images=n, split=_tag_int(tag, "split", 1))
-        self._judge("igemm", tag, got, ref, bound, form=form)
+                    residual=residual is not None, k=pw.kh * pw.kw * pw.cin, m=n * ho * wo, images=n, split=_tag_int(tag, "split", 1),
+                    src_strided=_img_strided(x), out_strided=out is not None and _img_strided(out),
+                    res_strided=residual is not None and _img_strided(residual),
+                    zero_spread=pw.kh == 3 and stride == 1 and min(hin, win) >= 2 and not bool(x[:, 1::2].any())
+                    and not bool(x[:, :, 1::2].any()) and bool(x.any()))
+        self._judge("igemm", tag, got, ref, bound, form=form,
+                    detail=describe(x=x, x2=x2, w=pw.w, residual=residual, out=y) + f" images={n}")
         return y
 
     def _finish(self, orig, d):
@@ -1109,7 +1319,8 @@ class LaunchShadow:
         ref = xs.double() @ ws.double().T
         if bs is not None:
             ref = ref + bs.double()
-        self._judge("linear_f32", tag, y.reshape(1, *y.shape), ref.reshape(1, *ref.shape), BOUND_F32_ROWS)
+        self._judge("linear_f32", tag, y.reshape(1, *y.shape), ref.reshape(1, *ref.shape), BOUND_F32_ROWS,
+                    form=dict(m=xs.shape[0], k=xs.shape[1], n=ws.shape[0]))
         return y
 
     def _quick_gelu(self, orig, x):
@@ -1271,4 +1482,169 @@ class LaunchShadow:
         want = t.permute(0, 3, 1, 2).reshape(n, c, bands, h // bands, w).mean((3, 4)).reshape(n, -1)
         err = float((y.double() - want).abs().max() / want.abs().max().clamp_min(1e-300))
         self._judge_value("band_mean", tag, err, BOUND_BAND_MEAN, bool(torch.isfinite(y).all()), form=dict(skip=skip is not None))
+        return y
+
+
+    # -- the training step's entry points (extra=TRAIN_KINDS) --------------------------------------------------------------
+    def _apply(self, kind, tag, checks, form=None):
+        """Records and judges the Check records of one launch (one record per output)."""
+        ordinal = self.counts.get(kind, 0)
+        checks = list(checks)
+        for i, ck in enumerate(checks):
+            name = f"{kind} #{ordinal} {ck.what}"
+            if name in self.pinned:
+                self.pins_used.add(name)
+                checks[i] = ck = ck._replace(bound=self.pinned[name])
+            res = evaluate(ck)
+            self.records.append(dict(kind=kind, tag=tag, bound=ck.bound, extra=ck.what, form=form or {}, rel=res["rel"], tile=res["tile"],
+                                     where=res["where"], finite=res["finite"], row=res["row"], pinned=name if name in self.pinned else None))
+            if ck.mode in ("tiles", "value", "figure"):
+                record(f"shadow {self.label} {kind} {tag} {ck.what}", res["rel"], ck.bound)
+            if res["row"] is not None:
+                record(f"shadow {self.label} {kind} {tag} {ck.what} row_measure", res["row"])
+            if self.verbose:
+                row = "" if res["row"] is None else f" row={res['row']:.3e}"
+                print(f"[shadow {self.label}] {kind:16s} {tag} {ck.what} rel={res['rel']:.3e} tile={res['tile']:.3e}{row} "
+                      f"bound={ck.bound:.1e}{'' if res['ok'] else '  FAIL'}")
+        for msg in check_failures(kind, tag, checks):
+            self._fail(msg)
+
+    def _host_unchanged(self, what, pairs):
+        for name, live, snap in pairs:
+            if live is not None and not _same(live.detach().cpu(), snap):
+                self._fail(f"{what}: input {name} changed")
+
+    def _transpose(self, orig, x):
+        xs = _host(x)
+        y = orig(x)
+        torch.cuda.synchronize()
+        self._count("transpose")
+        tag = describe(x=x)
+        self._host_unchanged("transpose " + tag, [("x", x, xs)])
+        self._apply("transpose", tag, transpose_checks(xs, _host(y)), form=dict(rows=x.shape[0], cols=x.shape[1]))
+        return y
+
+    def _colsum(self, orig, dy):
+        ds = _host(dy)
+        y = orig(dy)
+        torch.cuda.synchronize()
+        self._count("colsum")
+        tag = describe(dy=dy)
+        self._host_unchanged("colsum " + tag, [("dy", dy, ds)])
+        self._apply("colsum", tag, colsum_checks(ds, _host(y)), form=dict(rows=dy.shape[0], blocks=R.partial_blocks(dy.shape[0])))
+        return y
+
+    def _layernorm_bwd(self, orig, x, dy, gamma, eps, dx_add=None):
+        xs, ds, gs, adds = _host(x), _host(dy), _host(gamma), _host(dx_add)
+        dx, dg, db = orig(x, dy, gamma, eps, dx_add=dx_add)
+        torch.cuda.synchronize()
+        self._count("layernorm_bwd")
+        tag = describe(x=x, dy=dy, dx_add=dx_add)
+        self._host_unchanged("layernorm_bwd " + tag, [("x", x, xs), ("dy", dy, ds), ("gamma", gamma, gs), ("dx_add", dx_add, adds)])
+        self._apply("layernorm_bwd", tag, layernorm_bwd_checks(xs, ds, gs, eps, adds, _host(dx), _host(dg), _host(db)),
+                    form=dict(images=x.shape[0], x_strided=_img_strided(x), dy_strided=_img_strided(dy), dx_add=dx_add is not None))
+        return dx, dg, db
+
+    def _groupnorm_bwd(self, orig, x, dy, gamma, beta, eps, silu, dx_add=None, one_block_per_group=False):
+        xs, ds, gs, bs, adds = _host(x), _host(dy), _host(gamma), _host(beta), _host(dx_add)
+        dx = orig(x, dy, gamma, beta, eps, silu, dx_add=dx_add, one_block_per_group=one_block_per_group)
+        torch.cuda.synchronize()
+        self._count("groupnorm_bwd")
+        tag = describe(x=x, dx_add=dx_add) + f" silu={int(silu)} one_block={int(one_block_per_group)}"
+        self._host_unchanged("groupnorm_bwd " + tag, [("x", x, xs), ("dy", dy, ds), ("gamma", gamma, gs), ("beta", beta, bs),
+                                                      ("dx_add", dx_add, adds)])
+        self._apply("groupnorm_bwd", tag, groupnorm_bwd_checks(xs, ds, gs, bs, eps, silu, adds, _host(dx)),
+                    form=dict(silu=bool(silu), dx_add=dx_add is not None, c=x.shape[-1]))
+        return dx
+
+    def _geglu_fwd(self, orig, pre):
+        ps = _host(pre)
+        h = orig(pre)
+        torch.cuda.synchronize()
+        self._count("geglu_fwd")
+        tag = describe(pre=pre)
+        self._host_unchanged("geglu_fwd " + tag, [("pre", pre, ps)])
+        self._apply("geglu_fwd", tag, geglu_fwd_checks(ps, _host(h)))
+        return h
+
+    def _geglu_bwd(self, orig, pre, dh):
+        ps, ds = _host(pre), _host(dh)
+        dpre = orig(pre, dh)
+        torch.cuda.synchronize()
+        self._count("geglu_bwd")
+        tag = describe(pre=pre, dh=dh)
+        self._host_unchanged("geglu_bwd " + tag, [("pre", pre, ps), ("dh", dh, ds)])
+        self._apply("geglu_bwd", tag, geglu_bwd_checks(ps, ds, _host(dpre)))
+        return dpre
+
+    def _attention_bwd(self, orig, q, k, v, o, dout, heads, scale, force_vector=False):
+        live = dict(q=q, k=k, v=v, o=o, dout=dout)
+        snaps = {nm: _host(t) for nm, t in live.items()}
+        dq, dk, dv = orig(q, k, v, o, dout, heads, scale, force_vector=force_vector)
+        torch.cuda.synchronize()
+        self._count("attention_bwd")
+        c = o.shape[2]
+        dh = c // heads
+        route = R.attention_bwd_route(dh, [s for t in live.values() for s in (t.stride(0), t.stride(1))],
+                                      [t.data_ptr() for t in live.values()], force_vector)
+        tag = f"#{self.counts['attention_bwd']} heads={heads} dh={dh} route={route} " + describe(**live)
+        self._host_unchanged("attention_bwd " + tag, [(nm, live[nm], snaps[nm]) for nm in live])
+        ops_ = (snaps["q"][..., :c], snaps["k"][..., :c], snaps["v"][..., :c], snaps["dout"])
+        checks = attention_bwd_checks(*ops_, heads, scale, route, _host(dq), _host(dk), _host(dv))
+        nfail = len(self.failures)
+        form = dict(route=route, dh=dh, tq=q.shape[1], tk=k.shape[1], images=q.shape[0])
+        if any(name.startswith(f"attention_bwd #{self.counts['attention_bwd']} ") for name in self.pinned):
+            rs = R.attention_bwd_restated(*ops_, heads, scale, q.dtype, route)           # recorded beside the pinned bound
+            form["restated"] = {ck.what: R.rel_l2(g, ck.ref) for ck, g in zip(checks, rs)}
+        self._apply("attention_bwd", tag, checks, form=form)
+        if len(self.failures) > nfail:              # what the operands say: the storage restatements on them, their range, the keys' offset
+            self.failures[-1] += " [" + attention_bwd_diagnosis(*ops_, heads, scale, q.dtype, [ck.ref for ck in checks]) + "]"
+        return dq, dk, dv
+
+    def _sumpool2(self, orig, src):
+        ss = _host(src)
+        y = orig(src)
+        torch.cuda.synchronize()
+        self._count("sumpool2")
+        tag = describe(src=src)
+        self._host_unchanged("sumpool2 " + tag, [("src", src, ss)])
+        self._apply("sumpool2", tag, sumpool2_checks(ss, _host(y)))
+        return y
+
+    def _silu_bwd_f32(self, orig, z, dy):
+        zs, ds = _host(z), _host(dy)
+        dx = orig(z, dy)
+        torch.cuda.synchronize()
+        self._count("silu_bwd_f32")
+        tag = describe(z=z)
+        self._host_unchanged("silu_bwd_f32 " + tag, [("z", z, zs), ("dy", dy, ds)])
+        self._apply("silu_bwd_f32", tag, silu_bwd_f32_checks(zs, ds, _host(dx)))
+        return dx
+
+    def _loss_grad(self, orig, eps, target, t, logvar, lvlb, loss_type="l2", l_simple_weight=1.0, elbo_weight=0.0, loss_scale=1.0,
+                   dtype=None, c_pad=32):
+        from mobi_amd import engine_dtype
+        live = dict(eps=eps, target=target, t=t, logvar=logvar, lvlb=lvlb)
+        snaps = {nm: _host(v) for nm, v in live.items()}
+        kw = dict(loss_type=loss_type, l_simple_weight=l_simple_weight, elbo_weight=elbo_weight, loss_scale=loss_scale)
+        dy, per_sample, terms = orig(eps, target, t, logvar, lvlb, dtype=dtype, c_pad=c_pad, **kw)
+        torch.cuda.synchronize()
+        self._count("loss_grad")
+        dtype = engine_dtype() if dtype is None else dtype
+        tag = f"{loss_type} scale={loss_scale:g} " + describe(eps=eps)
+        self._host_unchanged("loss_grad " + tag, [(nm, live[nm], snaps[nm]) for nm in live])
+        self._apply("loss_grad", tag, loss_grad_checks(*(snaps[nm] for nm in ("eps", "target", "t", "logvar", "lvlb")), kw, dtype, c_pad,
+                                                       _host(dy), _host(per_sample), _host(terms)),
+                    form=dict(loss_type=loss_type, loss_scale=loss_scale))
+        self.thin[dy.data_ptr()] = 1                # (the thin 32-channel pack the head's data gradient reads)
+        return dy, per_sample, terms
+
+    def _timestep_embedding(self, orig, t, freqs):
+        ts, fs = _host(t), _host(freqs)
+        y = orig(t, freqs)
+        torch.cuda.synchronize()
+        self._count("timestep_embedding")
+        tag = f"n={t.shape[0]} dim={2 * freqs.shape[0]}"
+        self._host_unchanged("timestep_embedding " + tag, [("t", t, ts), ("freqs", freqs, fs)])
+        self._apply("timestep_embedding", tag, timestep_embedding_checks(ts, fs, _host(y)))
         return y

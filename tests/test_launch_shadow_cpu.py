@@ -492,3 +492,406 @@ def test_row_chain_wrapper_judges_an_emulated_launch(dtype, monkeypatch):
     sh = ls.LaunchShadow(MP(), label="cpu")
     sh._row_chain(lambda *a, **kw: None, [object()], 2, 128, dtype)
     assert len(sh.failures) == 1 and "not built through ops.ChainProgram" in sh.failures[0]
+
+
+# ---- the training step's kinds (TRAIN_KINDS) --------------------------------------------------------------------------------
+# Every judge is fed the float64 reference rounded once to the type the launch stores (it passes, at a quarter of its bound or
+# less) and one planted fault (it fails, and the failure names the launch).
+from tests import backward_ref as R, loss_grad_ref           # noqa: E402
+from tests.golden_cases import record                        # noqa: E402
+
+
+class _MP:
+    pass
+
+
+# Rounding to a 16-bit type with unit roundoff u (2^-11 fp16, 2^-8 bf16) leaves an error uniform within half a unit in the last
+# place: rms ulp / sqrt(12) = u 2^e / sqrt(3) for a value in [2^e, 2^(e+1)), so the rel-L2 of a once-rounded tensor is at most
+# u / sqrt(3) = 2.82e-4 (fp16) / 2.26e-3 (bf16) whatever its mantissas, and 2.07e-4 / 1.66e-3 for Gaussian values (measured; TOL1 /
+# 3.86 and / 3.98).  A factor 4 below TOL1 is out of reach of ANY once-rounded 16-bit result; those checks are held to
+# TOL1 / (u / sqrt(3)) = 2.8, which every correct rounding meets.  Round-to-nearest is within half a storage ulp: a factor 2 below
+# the one ulp the l2 dy is allowed.  Everything else (fp32 results, the loss terms, the 1.5 TOL1 of the matrix-core attention
+# route, the fp32 weight gradient) keeps the factor 4.
+ROOM, ROOM_ROUNDED_ONCE, ROOM_ULP = 4.0, 2.8, 2.0
+
+
+def _room(ck):
+    if ck.what.endswith("(storage ulp)"):
+        return ROOM_ULP
+    return ROOM_ROUNDED_ONCE if ck.mode == "tiles" and ck.bound in ls.TOL1.values() else ROOM
+
+
+def _clean(kind, checks):
+    """The rounded reference passes every check, with room: rel-L2 (and the worst tile) a factor `_room` inside the bound."""
+    assert ls.check_failures(kind, "clean", checks) == []
+    for ck in checks:
+        res = ls.evaluate(ck)
+        if ck.mode in ("tiles", "value", "figure"):
+            record(f"shadow cpu {kind} {ck.what} clean", res["rel"], ck.bound)
+            assert _room(ck) * res["rel"] <= ck.bound, (kind, ck.what, res["rel"], ck.bound)
+        if ck.mode == "tiles":
+            assert _room(ck) * res["tile"] <= ls.TILE_FACTOR * ck.bound, (kind, ck.what, res["tile"], ck.bound)
+
+
+def _faulty(kind, checks, *outputs):
+    """The planted fault is reported on exactly the named outputs, each failure naming the launch."""
+    bad = ls.check_failures(kind, "planted", checks)
+    assert bad and all(m.startswith(f"{kind} planted") for m in bad), bad
+    for what in outputs:
+        assert any(f"{kind} planted {what}" in m for m in bad), (what, bad)
+    return bad
+
+
+def test_train_kinds_are_opt_in():
+    assert ls.LaunchShadow(_MP()).wrapped == ls.LaunchShadow.WRAPPED
+    both = ls.LaunchShadow(_MP(), extra=ls.TRAIN_KINDS + ("linear_f32", "add")).wrapped
+    assert both == ls.LaunchShadow.WRAPPED + ("linear_f32", "add") + ls.TRAIN_KINDS and len(set(both)) == len(both)
+    assert set(ls.TRAIN_KINDS) <= set(ls.LAUNCH_KINDS.values()) and not set(ls.TRAIN_KINDS) & set(ls.EXTRA_KINDS)
+    assert all(hasattr(ls.LaunchShadow, "_" + k) and ls.LAUNCH_KINDS["mobi_" + k] == k for k in ls.TRAIN_KINDS)
+    for q in ("mobi_backward_partial_blocks", "mobi_groupnorm_bwd_workspace_floats", "mobi_loss_grad_blocks_per_sample"):
+        assert ls.is_query_only(q), q
+    assert not any(ls.is_query_only("mobi_" + k) for k in ls.TRAIN_KINDS)
+
+
+def test_census_reports_an_unwrapped_layernorm_bwd():
+    """A mobi_layernorm_bwd call no wrapper judged (a shadow without TRAIN_KINDS around a training step) is a census failure;
+    its partial-block query is not."""
+    class Lib:
+        def __getattr__(self, name):
+            return lambda *a: 0
+    sh = ls.LaunchShadow(_MP())
+    lib = ls.LibCensus(Lib(), sh.calls)
+    lib.mobi_backward_partial_blocks(1024)
+    assert sh.census_failures() == []
+    lib.mobi_layernorm_bwd(None, None)
+    assert sh.census_failures() == ["mobi_layernorm_bwd: 1 calls, 0 judged by the shadow"]
+    sh._count("layernorm_bwd")
+    assert sh.census_failures() == []
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_colsum_and_layernorm_bwd_judges(dtype):
+    """1,000 rows = 63 partial blocks, the last of 8 rows: column sums and d gamma that lost them; dx that lost dx_add in one
+    of four images."""
+    n, t, c = 4, 250, 64
+    x, dy, add = (_rand((n, t, c), s, sc).to(dtype) for s, sc in ((100, 2.0), (101, 1.0), (102, 1.0)))
+    gamma = _rand((c,), 103).float() * 0.2 + 1.0
+    assert R.partial_blocks(n * t) == 63 and n * t - 62 * 16 == 8
+    cs = R.colsum_ref(dy.reshape(-1, c))
+    _clean("colsum", ls.colsum_checks(dy.reshape(-1, c), cs.float()))
+    _faulty("colsum", ls.colsum_checks(dy.reshape(-1, c), R.colsum_ref(dy.reshape(-1, c)[:62 * 16]).float()), "out")
+    rdx, rdg, rdb = R.layernorm_bwd_ref(x.reshape(-1, c), dy.reshape(-1, c), gamma, 1e-5, dx_add=add.reshape(-1, c))
+    good = (rdx.reshape(n, t, c).to(dtype), rdg.float(), rdb.float())
+    _clean("layernorm_bwd", ls.layernorm_bwd_checks(x, dy, gamma, 1e-5, add, *good))
+    _, sdg, _ = R.layernorm_bwd_ref(x.reshape(-1, c)[:62 * 16], dy.reshape(-1, c)[:62 * 16], gamma, 1e-5)
+    bad = _faulty("layernorm_bwd", ls.layernorm_bwd_checks(x, dy, gamma, 1e-5, add, good[0], sdg.float(), good[2]), "dgamma")
+    assert len(bad) == 1
+    no_add = R.layernorm_bwd_ref(x.reshape(-1, c), dy.reshape(-1, c), gamma, 1e-5)[0].reshape(n, t, c)
+    dx = good[0].clone()
+    dx[2] = no_add[2].to(dtype)
+    bad = _faulty("layernorm_bwd", ls.layernorm_bwd_checks(x, dy, gamma, 1e-5, add, dx, good[1], good[2]), "dx")
+    assert len(bad) == 1 and "at (2, " in bad[0]                                  # the worst tile is in image 2
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_groupnorm_bwd_judge(dtype):
+    """One group of one image computed without its mean term: dx + rstd mean(dxh) there.  dy carries a common offset (a
+    gradient whose group means are not 0, as a bias' is): with zero-mean noise the dropped term is 1 / 16 of an element on 4 of a
+    tile's 64 channels, 1.5e-2 of the tile -- under the bf16 tile bound, so it is the offset that makes this fault visible."""
+    n, side, c = 2, 8, 128
+    x, dy, add = (_rand((n, side, side, c), s, sc).to(dtype) for s, sc in ((110, 1.5), (111, 1.0), (112, 1.0)))
+    dy = (dy.double() + 1.5).to(dtype)
+    g, b = _rand((c,), 113).float() * 0.2 + 1.0, _rand((c,), 114).float() * 0.1
+    ref = R.groupnorm_bwd_ref(x.reshape(n, -1, c), dy.reshape(n, -1, c), g, b, 1e-5, True, dx_add=add.reshape(n, -1, c))
+    _clean("groupnorm_bwd", ls.groupnorm_bwd_checks(x, dy, g, b, 1e-5, True, add, ref.reshape(x.shape).to(dtype)))
+    img, grp, cg = 1, 5, c // 32
+    sl = slice(grp * cg, (grp + 1) * cg)
+    xg, dyg = x[img, ..., sl].double(), dy[img, ..., sl].double()
+    rstd = (xg.var(unbiased=False) + 1e-5).rsqrt()
+    z = (xg - xg.mean()) * rstd * g[sl].double() + b[sl].double()
+    sg = torch.sigmoid(z)
+    dxh = dyg * sg * (1.0 + z * (1.0 - sg)) * g[sl].double()
+    bad_dx = ref.reshape(x.shape).clone()
+    bad_dx[img, ..., sl] += rstd * dxh.mean()
+    assert float((bad_dx - ref.reshape(x.shape)).abs().max()) > 0
+    bad = _faulty("groupnorm_bwd", ls.groupnorm_bwd_checks(x, dy, g, b, 1e-5, True, add, bad_dx.to(dtype)), "dx")
+    assert "at (1, " in bad[0]
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_geglu_sumpool2_silu_and_transpose_judges(dtype):
+    pre, dh = _rand((2, 100, 2 * 96), 120, 1.5).to(dtype), _rand((2, 100, 96), 121).to(dtype)
+    h, dpre = R.geglu_fwd_ref(pre), R.geglu_bwd_ref(pre, dh)
+    _clean("geglu_fwd", ls.geglu_fwd_checks(pre, h.to(dtype)))
+    _clean("geglu_bwd", ls.geglu_bwd_checks(pre, dh, dpre.to(dtype)))
+    swapped = torch.cat([dpre[..., 96:], dpre[..., :96]], -1)                    # d gate where d value belongs
+    _faulty("geglu_bwd", ls.geglu_bwd_checks(pre, dh, swapped.to(dtype)), "dpre")
+    _faulty("geglu_fwd", ls.geglu_fwd_checks(pre, (pre[..., :96].double() * F.silu(pre[..., 96:].double())).to(dtype)), "h")
+    # sumpool2: the corner (1, 1) of one 2 x 2 block left out
+    src = _rand((2, 8, 12, 64), 122).to(dtype)
+    pooled = R.sumpool2_ref(src)
+    _clean("sumpool2", ls.sumpool2_checks(src, pooled.to(dtype)))
+    short = pooled.clone()
+    short[1, 2, 3] -= src[1, 5, 7].double()
+    _faulty("sumpool2", ls.sumpool2_checks(src, short.to(dtype)), "out")
+    # silu_bwd_f32: the derivative without its z (1 - sigmoid) term
+    z, dz = _rand((6, 512), 123, 2.0).float(), _rand((6, 512), 124).float()
+    _clean("silu_bwd_f32", ls.silu_bwd_f32_checks(z, dz, R.silu_bwd_ref(z, dz).float()))
+    _faulty("silu_bwd_f32", ls.silu_bwd_f32_checks(z, dz, (dz * torch.sigmoid(z)).float()), "dx")
+    # transpose: one 8 x 8 block left untransposed
+    xt = _rand((64, 40), 125).to(dtype)
+    assert ls.check_failures("transpose", "clean", ls.transpose_checks(xt, xt.t().contiguous())) == []
+    out = xt.t().contiguous()
+    out[8:16, 16:24] = xt[8:16, 16:24]
+    assert not torch.equal(out, xt.t())
+    bad = _faulty("transpose", ls.transpose_checks(xt, out), "out")
+    assert "bit for bit" in bad[0]
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_attention_bwd_judge(dtype):
+    """Keys and values with a common offset three times the tokens' own spread (test_attention_backward_with_common_offsets):
+    the matrix-core restatement with the row term D from the pass's own P and dP passes; with D = do . o on the STORED output
+    (the 26 % finding of tests/test_gpu_backward.py) dq fails; one head's dk swapped with its dv fails on both."""
+    n, heads, dh, t = 2, 4, 16, 128
+    c, scale = heads * dh, dh ** -0.5
+    off = lambda s: 3.0 * _rand((1, 1, c), s)
+    q, do = _rand((n, t, c), 130).to(dtype), _rand((n, t, c), 131).to(dtype)
+    k, v = (_rand((n, t, c), 132) + off(133)).to(dtype), (_rand((n, t, c), 134) + off(135)).to(dtype)
+    ref = R.attention_bwd_ref(q, k, v, do, heads, scale)
+    for route in ("mfma", "vector"):
+        _clean("attention_bwd", ls.attention_bwd_checks(q, k, v, do, heads, scale, route, *(r.to(dtype) for r in ref)))
+    assert ls.check_failures("attention_bwd", "restated", ls.attention_bwd_checks(
+        q, k, v, do, heads, scale, "mfma", *R.attention_bwd_restated(q, k, v, do, heads, scale, dtype, "mfma"))) == []
+    o = R.attention_fwd_ref(q, k, v, heads, scale).to(dtype)
+    stored = R.attention_bwd_restated(q, k, v, do, heads, scale, dtype, "mfma", o_stored=o)
+    bad = _faulty("attention_bwd", ls.attention_bwd_checks(q, k, v, do, heads, scale, "mfma", *stored), "dq")
+    assert not any(" dv:" in m for m in bad)                                   # dv does not read the row term
+    dq, dk, dv = (r.to(dtype) for r in ref)
+    dk2, dv2 = dk.clone(), dv.clone()
+    dk2[..., dh:2 * dh], dv2[..., dh:2 * dh] = dv[..., dh:2 * dh], dk[..., dh:2 * dh]
+    bad = _faulty("attention_bwd", ls.attention_bwd_checks(q, k, v, do, heads, scale, "mfma", dq, dk2, dv2), "dk", "dv")
+    assert len(bad) == 2
+
+
+@pytest.mark.parametrize("dtype", DT)
+@pytest.mark.parametrize("loss_type", ["l2", "l1"])
+def test_loss_grad_and_timestep_embedding_judges(dtype, loss_type):
+    n, c, h, w = 3, 4, 5, 7
+    eps, target = _rand((n, c, h, w), 140).float(), _rand((n, c, h, w), 141).float()
+    t = torch.tensor([0, 1, 999])
+    logvar, lvlb = _rand((1000,), 142).float().clamp(-1, 1), _rand((1000,), 143).float().abs()
+    kw = dict(loss_type=loss_type, l_simple_weight=1.0, elbo_weight=0.25, loss_scale=4.0)
+    rdy, rper, rterms = loss_grad_ref.loss_grad_ref(eps, target, t, logvar, lvlb, **kw)
+    dy = loss_grad_ref.to_storage(rdy, dtype)
+    args = (eps, target, t, logvar, lvlb, kw, dtype, 32)
+    _clean("loss_grad", ls.loss_grad_checks(*args, dy, rper.float(), rterms.float()))
+    z = torch.zeros(1)                                                          # the default objective: loss_vlb is exactly 0
+    zdy, zper, zterms = loss_grad_ref.loss_grad_ref(eps, target, t, z, z, **dict(kw, elbo_weight=0.0))
+    zargs = (eps, target, t, z, z, dict(kw, elbo_weight=0.0), dtype, 32)
+    assert float(zterms[1]) == 0.0
+    assert ls.check_failures("loss_grad", "zero", ls.loss_grad_checks(*zargs, loss_grad_ref.to_storage(zdy, dtype), zper.float(), zterms.float())) == []
+    zbad = zterms.float().clone()
+    zbad[1] = 1e-9
+    _faulty("loss_grad", ls.loss_grad_checks(*zargs, loss_grad_ref.to_storage(zdy, dtype), zper.float(), zbad), "terms")
+    spill = dy.clone()
+    spill[1, 2, 3, c] = dy[1, 2, 3, c - 1]                                      # the last channel written once more, beyond out_channels
+    bad = _faulty("loss_grad", ls.loss_grad_checks(*args, spill, rper.float(), rterms.float()))
+    assert "beyond the 4 out_channels" in bad[0] and len(bad) == (2 if loss_type == "l1" else 1)      # (l1 is also bit-compared)
+    minus = dy.clone()
+    minus[..., c:] = -0.0
+    assert "beyond the 4 out_channels" in _faulty("loss_grad", ls.loss_grad_checks(*args, minus, rper.float(), rterms.float()))[0]
+    other = loss_grad_ref.to_storage(rdy * 1.01, dtype)                          # a wrong coefficient
+    _faulty("loss_grad", ls.loss_grad_checks(*args, other, rper.float(), rterms.float()), "dy")
+    _faulty("loss_grad", ls.loss_grad_checks(*args, dy, rper.float() * (1 + 1e-5), rterms.float()), "per_sample")
+    if loss_type == "l2":
+        from mobi_amd.ldm.modules.diffusionmodules.util import timestep_freqs
+        from oracle.unet import timestep_embedding as ref_temb
+        tt = torch.tensor([1, 21, 500, 981, 999])
+        freqs = timestep_freqs(64, 10000).float()
+        _clean("timestep_embedding", ls.timestep_embedding_checks(tt, freqs, ref_temb(tt, 64)))
+        _faulty("timestep_embedding", ls.timestep_embedding_checks(tt, freqs, ref_temb(tt, 64).roll(32, 1)), "out")     # [sin | cos]
+
+
+def _emulated_igemm(fault=None):
+    """Stands in for ops.igemm on the CPU: the shadow's own fp64 reference of the operands, rounded once to what the launch
+    stores, written through `out`; `fault(x, pw, y, out)` then plants one."""
+    from mobi_amd import ops
+
+    def run(x, pw, *, residual=None, out=None, out_mode=0, **kw):
+        n, h, w, _ = x.shape
+        op = dict(x=x, x2=None, w=pw.w, bias=None, kh=1, kw=1, stride=1, pad_h=0, pad_w=0, upsample=False, hout=h, wout=w,
+                  cout=pw.cout, n_packed=pw.n_packed, groups=1, geglu=False, ln=False, ln_eps=0.0, scale=1.0, rowvec=None,
+                  rowvec_has_bias=False, residual=None if residual is None else residual.reshape(n, h * w, pw.cout))
+        y = ls.igemm_reference(op).reshape(n, h, w, pw.cout).to(torch.float32 if out_mode == ops.OUT_ROWS_F32 else x.dtype)
+        if out is not None:
+            out.copy_(y)
+            y = out
+        return y if fault is None else fault(x, pw, y, out)
+    return run
+
+
+def _cpu_shadow(monkeypatch):
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a: None)
+    sh = ls.LaunchShadow(_MP(), label="cpu")
+    sh.sink = []
+    return sh
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_igemm_wrapper_judges_a_weight_gradient(dtype, monkeypatch):
+    """ops.linear_wgrad's launch as the wrapper sees it: dy^T [1, 1, n, rows] times x^T [k, rows] with the token rows as k and
+    fp32 output.  The clean launch passes a factor 4 inside its bound; with the last 32 token rows of k dropped it fails."""
+    from mobi_amd import ops
+    rows, n, k = 1024, 96, 64
+    dyt, xt = _rand((n, rows), 150).to(dtype), _rand((k, rows), 151).to(dtype)
+    pw = ops.Packed(xt, None, 1, 1, rows, k, k)
+    sh = _cpu_shadow(monkeypatch)
+    sh._igemm(_emulated_igemm(), dyt.view(1, 1, n, rows), pw, out_mode=ops.OUT_ROWS_F32)
+    assert sh.failures == [] and sh.counts == {"igemm": 1}
+    rec, = sh.records
+    assert rec["form"]["out_mode"] == ops.OUT_ROWS_F32 and rec["form"]["k"] == rows and rec["bound"] == ls.bound_f32_rows(dtype)
+    assert not (rec["form"]["src_strided"] or rec["form"]["out_strided"] or rec["form"]["res_strided"] or rec["form"]["zero_spread"])
+    assert 4.0 * rec["rel"] <= rec["bound"] and 4.0 * rec["tile"] <= ls.TILE_FACTOR * rec["bound"]
+
+    def drop_tail(x, pw, y, out):
+        return (x[0, 0, :, :-32].double() @ pw.w[:, :-32].double().t()).float().view(1, 1, n, k)
+    sh = _cpu_shadow(monkeypatch)
+    sh._igemm(_emulated_igemm(drop_tail), dyt.view(1, 1, n, rows), pw, out_mode=ops.OUT_ROWS_F32)
+    assert len(sh.failures) == 1 and sh.failures[0].startswith("cpu igemm") and f"x=(1, 1, {n}, {rows})" in sh.failures[0], sh.failures
+    assert sh.records[0]["rel"] > 0.1                                          # ~ sqrt(32 / 1024)
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_igemm_wrapper_judges_strided_views(dtype, monkeypatch):
+    """block_forward's `ops.linear(y, connector, residual=x3[::2], out=x4[::2])` on two camera / lidar pairs: source, residual
+    and output with two images each behind a doubled image stride.  Clean: passes, and the form says which operands were
+    strided.  A launch that also writes the partner image's first row fails by name."""
+    from mobi_amd import ops
+    t, c = 40, 64
+    src, x3, x4 = _rand((4, t, 1, c), 160).to(dtype), _rand((4, t, 1, c), 161).to(dtype), torch.zeros((4, t, 1, c), dtype=dtype)
+    pw = ops.Packed((_rand((c, c), 162) * c ** -0.5).to(dtype), None, 1, 1, c, c, c)
+    sh = _cpu_shadow(monkeypatch)
+    sh._igemm(_emulated_igemm(), src[::2], pw, residual=x3[::2], out=x4[::2])
+    assert sh.failures == []
+    form = sh.records[0]["form"]
+    assert form["src_strided"] and form["out_strided"] and form["res_strided"] and form["images"] == 2 and form["residual"]
+    assert not bool(x4[1::2].any()) and bool(x4[::2].any())
+
+    def spill(x, pw, y, out):
+        out._base[1, 0] = 1.0                                                  # the lidar image between the two camera images
+        return y
+    sh = _cpu_shadow(monkeypatch)
+    sh._igemm(_emulated_igemm(spill), src[::2], pw, residual=x3[::2], out=torch.zeros((4, t, 1, c), dtype=dtype)[::2])
+    assert len(sh.failures) == 1 and "wrote outside its out view" in sh.failures[0], sh.failures
+    # an image stride the launch ignored: image 1 of the view computed from the partner image (rows 1 instead of 2)
+    def wrong_image(x, pw, y, out):
+        y[1] = (src[1, :, 0].double() @ pw.w.double().t() + x3[2, :, 0].double()).to(dtype).view(t, 1, c)
+        return y
+    sh = _cpu_shadow(monkeypatch)
+    sh._igemm(_emulated_igemm(wrong_image), src[::2], pw, residual=x3[::2], out=torch.zeros((4, t, 1, c), dtype=dtype)[::2])
+    assert len(sh.failures) == 1 and sh.failures[0].startswith("cpu igemm") and "at (1, " in sh.failures[0], sh.failures
+
+
+def test_zero_spread_form(monkeypatch):
+    """The stride-2 data gradient's input (dy on the even pixels of a zero tensor) is recognised; a dense input is not."""
+    from mobi_amd import ops
+    c = 32
+    w = (_rand((c, 9 * c), 170) * (9 * c) ** -0.5).to(torch.float16)
+    pw = ops.Packed(w, None, 3, 3, c, c, c)
+
+    def conv(x, pw, **kw):
+        op = dict(x=x, x2=None, w=pw.w, bias=None, kh=3, kw=3, stride=1, pad_h=1, pad_w=1, upsample=False, hout=x.shape[1],
+                  wout=x.shape[2], cout=c, n_packed=c, groups=1, geglu=False, ln=False, ln_eps=0.0, scale=1.0, rowvec=None,
+                  rowvec_has_bias=False, residual=None)
+        return ls.igemm_reference(op).reshape(x.shape[0], x.shape[1], x.shape[2], c).to(x.dtype)
+    dz = torch.zeros((2, 8, 8, c), dtype=torch.float16)
+    dz[:, ::2, ::2] = _rand((2, 4, 4, c), 171).to(torch.float16)
+    for x, want in ((dz, True), (_rand((2, 8, 8, c), 172).to(torch.float16), False)):
+        sh = _cpu_shadow(monkeypatch)
+        sh._igemm(conv, x, pw)
+        assert sh.failures == [] and sh.records[0]["form"]["zero_spread"] is want
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_train_wrappers_run_on_emulated_launches(dtype, monkeypatch):
+    """Every TRAIN_KINDS wrapper around the storage restatement of its kernel (tests/backward_ref.py `*_restated`): counted,
+    recorded per output, no failure; a layernorm_bwd over `x3[1::2]` of two pairs whose launch read `x3[::2]` fails by name
+    with the operands' shapes and strides in the message."""
+    sh = _cpu_shadow(monkeypatch)
+    n, t, c, heads = 4, 48, 64, 4
+    x3, dy, add = _rand((n, t, c), 180, 2.0).to(dtype), _rand((2, t, c), 181).to(dtype), _rand((2, t, c), 182).to(dtype)
+    gamma = _rand((c,), 183).float() * 0.2 + 1.0
+    rows = lambda v: v.reshape(-1, c)
+
+    def ln_bwd(x, dy_, g, eps, dx_add=None):
+        dx, dg, db = R.layernorm_bwd_restated(rows(x), rows(dy_), g, eps, dtype, dx_add=None if dx_add is None else rows(dx_add))
+        return dx.reshape(x.shape).to(dtype), dg, db
+    sh._layernorm_bwd(ln_bwd, x3[1::2], dy, gamma, 1e-5, dx_add=add)
+    assert [r["extra"] for r in sh.records] == ["dx", "dgamma", "dbeta"] and sh.records[0]["form"]["x_strided"]
+    sh._colsum(lambda d: R.colsum_restated(d), rows(dy))
+    sh._transpose(lambda v: v.t().contiguous(), rows(dy)[:, :40])
+    g4 = lambda v: v.reshape(2, 6, 8, c)
+    gn = _rand((c,), 184).float() * 0.1
+    sh._groupnorm_bwd(lambda x, d, g, b, eps, silu, dx_add=None, one_block_per_group=False:
+                      R.groupnorm_bwd_restated(x.reshape(2, -1, c), d.reshape(2, -1, c), g, b, eps, silu, dtype,
+                                               dx_add=dx_add.reshape(2, -1, c)).reshape(x.shape).to(dtype),
+                      g4(x3[::2].contiguous()), g4(dy), gamma, gn, 1e-5, True, dx_add=g4(add))
+    pre = _rand((2, t, 2 * c), 185, 1.5).to(dtype)
+    sh._geglu_fwd(lambda p: R.geglu_fwd_restated(p, dtype).to(dtype), pre)
+    sh._geglu_bwd(lambda p, d: R.geglu_bwd_restated(p, d, dtype).to(dtype), pre, dy)
+    q, k, v = x3[::2], _rand((2, 2, c), 186).to(dtype), _rand((2, 2, c), 187).to(dtype)
+    sh._attention_bwd(lambda q_, k_, v_, o_, do_, h_, s_, force_vector=False:
+                      tuple(r.to(dtype) for r in R.attention_bwd_restated(q_, k_, v_, do_, h_, s_, dtype, "mfma")),
+                      q, k, v, torch.zeros_like(dy), dy, heads, (c // heads) ** -0.5)
+    assert [r["extra"] for r in sh.records[-3:]] == ["dq", "dk", "dv"] and sh.records[-1]["form"]["route"] == "mfma"
+    assert sh.records[-1]["bound"] == 1.5 * ls.TOL1[dtype] and sh.records[-1]["form"]["tk"] == 2
+    sh._sumpool2(lambda s: R.sumpool2_restated(s, dtype).to(dtype), g4(dy))
+    z = _rand((4, 512), 188, 2.0).float()
+    sh._silu_bwd_f32(lambda z_, d_: R.silu_bwd_restated(z_, d_), z, _rand((4, 512), 189).float())
+    from mobi_amd.ldm.modules.diffusionmodules.util import timestep_freqs
+    from oracle.unet import timestep_embedding as ref_temb
+    sh._timestep_embedding(lambda t_, f_: ref_temb(t_, 2 * f_.shape[0]), torch.tensor([741, 741, 21, 21]), timestep_freqs(64, 10000).float())
+    eps, target = _rand((4, 4, 8, 8), 190).float(), _rand((4, 4, 8, 8), 191).float()
+    zt = torch.zeros(1)
+
+    def loss(e, g, t_, lv, lw, dtype=None, c_pad=32, **kw):
+        rdy, per, terms = loss_grad_ref.loss_grad_ref(e, g, t_, lv, lw, **kw)
+        return loss_grad_ref.to_storage(rdy, dtype, c_pad), per.float(), terms.float()
+    out = sh._loss_grad(loss, eps, target, torch.tensor([741, 741, 21, 21]), zt, zt, loss_scale=256.0, dtype=dtype)
+    assert sh.thin[out[0].data_ptr()] == 1
+    assert sh.failures == [], sh.failures
+    assert sh.counts == {k: 1 for k in ls.TRAIN_KINDS}
+    # the wrong half of the pairs
+    sh = _cpu_shadow(monkeypatch)
+    sh._layernorm_bwd(lambda x, d, g, eps, dx_add=None: ln_bwd(x3[::2], d, g, eps, dx_add), x3[1::2], dy, gamma, 1e-5, dx_add=add)
+    assert sh.failures and all(m.startswith("cpu layernorm_bwd x=(2, 48, 64)/(6144, 64, 1)") for m in sh.failures), sh.failures
+
+
+def test_a_pinned_launch_is_judged_at_its_written_bound():
+    """`pinned={"<kind> #<ordinal> <output>": bound}`: that output of that launch alone is judged at the written bound, with the
+    storage restatement's own figure on the same operands recorded beside it; the unpinned launch keeps its unit test's bound and
+    its failure carries the operands' diagnosis; a pin whose launch never ran is a failure."""
+    dtype = torch.float16
+    q, k, v, do = (_rand((1, 64, 32), s).to(dtype) for s in (200, 201, 202, 203))
+
+    def off(q_, k_, v_, o_, do_, h_, s_, force_vector=False):
+        dq, dk, dv = (t.to(dtype) for t in R.attention_bwd_ref(q_, k_, v_, do_, h_, s_))
+        return (dq.double() * 1.002).to(dtype), dk, dv
+
+    def run(pinned):
+        with pytest.MonkeyPatch.context() as mp:
+            mp.setattr(torch.cuda, "synchronize", lambda *a: None)
+            sh = ls.LaunchShadow(mp, label="cpu", pinned=pinned)
+            sh.sink = []
+            sh._attention_bwd(off, q, k, v, torch.zeros_like(q), do, 4, 8 ** -0.5)
+            sh.__exit__(None, None, None)
+        return sh
+    sh = run(None)
+    assert len(sh.failures) == 1 and sh.failures[0].startswith("cpu attention_bwd #1 ") and " dq: " in sh.failures[0]
+    assert "restated mfma: dq" in sh.failures[0] and "below 2^-14" in sh.failures[0]
+    sh = run({"attention_bwd #1 dq": 5e-3})
+    assert sh.failures == [] and [r["bound"] for r in sh.records] == [5e-3, 1.5 * ls.TOL1[dtype], 1.5 * ls.TOL1[dtype]]
+    assert sh.records[0]["pinned"] == "attention_bwd #1 dq" and 0 < sh.records[0]["form"]["restated"]["dq"] < ls.TOL1[dtype]
+    sh = run({"attention_bwd #2 dq": 5e-3})
+    assert len(sh.failures) == 2 and "pinned launch 'attention_bwd #2 dq' did not run" in sh.failures[1]
