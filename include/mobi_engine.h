@@ -52,7 +52,8 @@ extern "C" {
  *      passes mobi_grad_stats / mobi_adamw_multi + mobi_multi_tensor_workspace_bytes (mobi_mt_tensor 23, mobi_mt_chunk 24,
  *      mobi_grad_stats_record 25); likewise the EMA / swap pass over tensor pairs, mobi_ema_multi (mobi_mt_pair 26); likewise
  *      the gradient accumulation over the same pair tables, mobi_accum_multi (no new struct); likewise the fused loss /
- *      entering-gradient launch mobi_loss_grad + mobi_loss_grad_blocks_per_sample (mobi_loss_grad_params 27) */
+ *      entering-gradient launch mobi_loss_grad + mobi_loss_grad_blocks_per_sample (mobi_loss_grad_params 27); likewise the
+ *      training splits' data side, mobi_ref_augment (mobi_ref_augment_params 28) and mobi_drop_context (no struct) */
 #define MOBI_ABI_VERSION 6
 
 enum { MOBI_OK = 0, MOBI_ERR_ARG = -1, MOBI_ERR_UNSUPPORTED = -2, MOBI_ERR_LAUNCH = -3, MOBI_ERR_ALIGN = -4 };
@@ -65,7 +66,8 @@ const char* mobi_error_string(int code);
  * 3 attention, 4 ctx_attention, 5 skinny_linear, 6 conv_small_cin, 7 conv_small_cout,
  * 8 ddim_step, 9 two_key_adapter, 10 range_paste, 11 lidar_metrics, 12 range_prepare, 13 image_prepare, 14 ff_geglu,
  * 15 row_chain, 16 chain_op, 17 layernorm_bwd, 18 attention_bwd, 19 split_source, 20 dpm_step, 21 lpips_distance,
- * 22 image_normalize, 23 mt_tensor, 24 mt_chunk, 25 grad_stats_record, 26 mt_pair, 27 loss_grad.  Returns 0 for an unknown id. */
+ * 22 image_normalize, 23 mt_tensor, 24 mt_chunk, 25 grad_stats_record, 26 mt_pair, 27 loss_grad, 28 ref_augment.
+ * Returns 0 for an unknown id. */
 size_t mobi_struct_size(int id);
 /* Development hook: the library reads its MOBI_* A/B environment variables once, at the first launch
  * (mobi_amd/csrc/tuning.h lists them); this re-reads them.  Not needed by a product caller. */
@@ -823,6 +825,31 @@ typedef struct mobi_image_prepare_params {
   int32_t batch, H, W, height, width;
 } mobi_image_prepare_params;
 int mobi_image_prepare(const mobi_image_prepare_params* p, void* stream);
+
+/* Dataset side of the train / val splits: the reference-image augmentation of a whole batch in one launch
+ * (ldm/data/nuscenes.py:239-250, albumentations 0.4.3 on OpenCV restated in integer arithmetic; the host form and the
+ * definition are mobi_amd/ldm/data/ref_aug.py), every stage on or off per sample:
+ *   flip     F[y][x] = src[y][size - 1 - x]                                               where flags[b][0] & 1
+ *   rotate   8-bit warpAffine, bilinear on a 1/32-pixel grid, border 0                    where flags[b][0] & 2:
+ *            X = (X0[y] + ax[x]) >> 5, Y = (Y0[y] + bx[x]) >> 5, sx = X >> 5, fx = X & 31 (sy, fy likewise),
+ *            R = ((32 - fy)(32 - fx) F(sy, sx) + (32 - fy) fx F(sy, sx + 1) + fy (32 - fx) F(sy + 1, sx)
+ *                 + fy fx F(sy + 1, sx + 1) + 512) >> 10, F = 0 outside the patch; warp[b] = {ax, bx, X0, Y0}
+ *   blur     k x k box, BORDER_REFLECT_101, (2 sum + k^2) / (2 k^2) rounded down, k = flags[b][1] in {3, 5, 7}; 0 = off
+ *   output   out[b][c][y][x] = table[b][c][value]: brightness / contrast look-up and the CLIP normalisation in one table
+ * src u8 [batch][size][size][3]; flags i32 [batch][2]; warp i32 [batch][4][size] (read only where the rotate bit is
+ * set); table f32 [batch][3][256]; out f32 [batch][3][size][size].  8 <= size <= 4096 (else MOBI_ERR_UNSUPPORTED). */
+typedef struct mobi_ref_augment_params {
+  const uint8_t* src; const int32_t* flags; const int32_t* warp; const float* table;
+  float* out;
+  int32_t batch, size;
+} mobi_ref_augment_params;
+int mobi_ref_augment(const mobi_ref_augment_params* p, void* stream);
+
+/* Context drop of a training batch (ldm/data/nuscenes.py:463-466, :588-591), in place, for the samples with flag[b] != 0:
+ *   inpaint[b] = 0,  gt[b][c] = gt[b][c] * (1 - mask[b])   (two fp32 operations, no contraction)
+ * gt / inpaint f32 [batch][channels][hw]; mask f32 [batch][1][hw]; flag i32 [batch]. */
+int mobi_drop_context(float* gt, float* inpaint, const float* mask, const int32_t* flag, int32_t batch, int32_t channels,
+                      int64_t hw, void* stream);
 
 /* Camera paste-back of one sample (scripts/inference_test_bench.py:478-510):
  *   mobi_paste_patch    F.interpolate(patch, (crop_h, crop_w), bilinear, align_corners=False), (((x + 1) / 2) * 255)

@@ -358,6 +358,131 @@ __global__ __launch_bounds__(256) void image_prepare_kernel(const mobi_image_pre
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Reference-image augmentation of a batch in one launch (ldm/data/nuscenes.py:239-250: albumentations 0.4.3
+// HorizontalFlip -> Rotate(border_mode=0) -> Blur -> RandomBrightnessContrast on the resized uint8 patch, then
+// get_tensor_clip), every stage on or off per sample.  Integer arithmetic up to the table look-up, the expressions of
+// mobi_amd/ldm/data/ref_aug.py (the host builds the warp tables and the [3][256] output table).
+// One block per 32 x 32 output tile: the flipped / rotated tile with a halo of the blur radius goes to LDS as one
+// packed dword per pixel (r | g << 8 | b << 16), one barrier, then the box sums are taken from LDS.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int RA_TILE = 32, RA_HALO = 3, RA_SIDE = RA_TILE + 2 * RA_HALO;
+
+// pixel (y, x) of the flipped patch, 0 outside it
+__device__ __forceinline__ unsigned ra_source(const unsigned char* __restrict__ img, int S, int flip, int y, int x) {
+  if ((unsigned)y >= (unsigned)S || (unsigned)x >= (unsigned)S) return 0u;
+  const unsigned char* p = img + ((long long)y * S + (flip ? S - 1 - x : x)) * 3;
+  return (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
+}
+
+// pixel (y, x), 0 <= y, x < S, of the flipped and rotated patch
+__device__ __forceinline__ unsigned ra_rotated(const unsigned char* __restrict__ img, const int* __restrict__ warp, int S,
+                                               int flip, int rotate, int y, int x) {
+  if (!rotate) return ra_source(img, S, flip, y, x);
+  const int X = (warp[2 * S + y] + warp[x]) >> 5, Y = (warp[3 * S + y] + warp[S + x]) >> 5;
+  const int sx = X >> 5, fx = X & 31, sy = Y >> 5, fy = Y & 31;
+  const unsigned w00 = (32 - fy) * (32 - fx), w01 = (32 - fy) * fx, w10 = fy * (32 - fx), w11 = fy * fx;
+  const unsigned p00 = ra_source(img, S, flip, sy, sx), p01 = ra_source(img, S, flip, sy, sx + 1);
+  const unsigned p10 = ra_source(img, S, flip, sy + 1, sx), p11 = ra_source(img, S, flip, sy + 1, sx + 1);
+  unsigned out = 0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int sh = 8 * c;
+    const unsigned v = (w00 * ((p00 >> sh) & 255u) + w01 * ((p01 >> sh) & 255u) + w10 * ((p10 >> sh) & 255u) +
+                        w11 * ((p11 >> sh) & 255u) + 512u) >> 10;
+    out |= v << sh;
+  }
+  return out;
+}
+
+// box sums of side 2 R + 1 around tile pixel (ly, lx): r and b in the 16-bit halves of one word (49 * 255 < 2^16), g apart
+template <int R>
+__device__ __forceinline__ void ra_box(const unsigned* __restrict__ tile, int ly, int lx, unsigned& r, unsigned& g, unsigned& b) {
+  unsigned rb = 0, gg = 0;
+#pragma unroll
+  for (int dy = -R; dy <= R; ++dy)
+#pragma unroll
+    for (int dx = -R; dx <= R; ++dx) {
+      const unsigned v = tile[(ly + RA_HALO + dy) * RA_SIDE + lx + RA_HALO + dx];
+      rb += v & 0x00ff00ffu;
+      gg += (v >> 8) & 255u;
+    }
+  constexpr unsigned K2 = (2 * R + 1) * (2 * R + 1);
+  r = (2 * (rb & 0xffffu) + K2) / (2 * K2);
+  g = (2 * gg + K2) / (2 * K2);
+  b = (2 * (rb >> 16) + K2) / (2 * K2);
+}
+
+__global__ __launch_bounds__(256) void ref_augment_kernel(const mobi_ref_augment_params a) {
+  __shared__ unsigned tile[RA_SIDE * RA_SIDE];
+  __shared__ float table[3 * 256];
+  const int S = a.size, b = blockIdx.z, ty0 = blockIdx.y * RA_TILE, tx0 = blockIdx.x * RA_TILE;
+  const int flip = a.flags[b * 2] & 1, rotate = (a.flags[b * 2] >> 1) & 1;
+  int rad = a.flags[b * 2 + 1] >> 1;                                    // box side 0 (off) | 3 | 5 | 7 -> radius 0 .. 3
+  rad = rad < 0 ? 0 : (rad > RA_HALO ? RA_HALO : rad);
+  const unsigned char* img = a.src + (long long)b * S * S * 3;
+  const int* warp = a.warp + (long long)b * 4 * S;
+  for (int i = threadIdx.x; i < 3 * 256; i += 256) table[i] = a.table[(long long)b * 3 * 256 + i];
+  const int side = RA_TILE + 2 * rad;
+  for (int i = threadIdx.x; i < side * side; i += 256) {
+    const int py = i / side - rad, px = i % side - rad;                // tile-relative, -rad .. 31 + rad
+    int y = ty0 + py, x = tx0 + px;
+    unsigned v = 0;
+    if (y < S + rad && x < S + rad) {                                   // (beyond: no output pixel of the patch reads it)
+      y = y < 0 ? -y : (y >= S ? 2 * S - 2 - y : y);                    // BORDER_REFLECT_101 (S >= 8 > rad)
+      x = x < 0 ? -x : (x >= S ? 2 * S - 2 - x : x);
+      v = ra_rotated(img, warp, S, flip, rotate, y, x);
+    }
+    tile[(py + RA_HALO) * RA_SIDE + px + RA_HALO] = v;
+  }
+  __syncthreads();
+  const long long plane = (long long)S * S;
+  float* out = a.out + (long long)b * 3 * plane;
+  for (int i = threadIdx.x; i < RA_TILE * RA_TILE; i += 256) {
+    const int ly = i / RA_TILE, lx = i % RA_TILE, y = ty0 + ly, x = tx0 + lx;
+    if (y >= S || x >= S) continue;
+    unsigned r, g, bl;
+    if (rad == 1) ra_box<1>(tile, ly, lx, r, g, bl);
+    else if (rad == 2) ra_box<2>(tile, ly, lx, r, g, bl);
+    else if (rad == 3) ra_box<3>(tile, ly, lx, r, g, bl);
+    else ra_box<0>(tile, ly, lx, r, g, bl);
+    const long long o = (long long)y * S + x;
+    out[o] = table[r];
+    out[plane + o] = table[256 + g];
+    out[2 * plane + o] = table[512 + bl];
+  }
+}
+
+// Context drop of the flagged samples (ldm/data/nuscenes.py:463-466 / :588-591): inpaint = 0, gt = gt * (1 - mask), the mask
+// [batch][1][hw] broadcast over the channels; two fp32 operations as torch computes them (no contraction in this file).
+__device__ __forceinline__ float dc_keep(float v, float m) { return v * (1.0f - m); }
+__device__ __forceinline__ float4 dc_keep(float4 v, float4 m) {
+  return make_float4(dc_keep(v.x, m.x), dc_keep(v.y, m.y), dc_keep(v.z, m.z), dc_keep(v.w, m.w));
+}
+__device__ __forceinline__ void dc_zero(float& z) { z = 0.0f; }
+__device__ __forceinline__ void dc_zero(float4& z) { z = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+
+template <typename V>                                                    // V = float4 (hw % 4 == 0, aligned) | float
+__global__ __launch_bounds__(256) void drop_context_kernel(float* __restrict__ gt, float* __restrict__ inpaint,
+                                                            const float* __restrict__ mask, const int* __restrict__ flag,
+                                                            int channels, long long hw) {
+  const int b = blockIdx.y;
+  if (!flag[b]) return;
+  const long long nv = hw / (long long)(sizeof(V) / sizeof(float));
+  V zero;
+  dc_zero(zero);
+  const V* m = reinterpret_cast<const V*>(mask + b * hw);
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long long)gridDim.x * 256) {
+    const V keep = m[i];
+    for (int c = 0; c < channels; ++c) {
+      const long long plane = ((long long)b * channels + c) * hw;
+      V* g = reinterpret_cast<V*>(gt + plane) + i;
+      *g = dc_keep(*g, keep);
+      reinterpret_cast<V*>(inpaint + plane)[i] = zero;
+    }
+  }
+}
+
 }  // namespace mobi
 
 using namespace mobi;
@@ -440,6 +565,34 @@ extern "C" int mobi_image_prepare(const mobi_image_prepare_params* p, void* stre
   if (p->batch <= 0 || p->H <= 0 || p->W <= 0 || p->height <= 0 || p->width <= 0) return MOBI_ERR_ARG;
   hipLaunchKernelGGL(image_prepare_kernel, dim3(egrid_pp((long long)p->batch * p->height * p->width)), dim3(256), 0,
                      ST(stream), *p);
+  MOBI_CHECK_LAUNCH();
+  return MOBI_OK;
+}
+
+extern "C" int mobi_ref_augment(const mobi_ref_augment_params* p, void* stream) {
+  if (!p || !p->src || !p->flags || !p->warp || !p->table || !p->out) return MOBI_ERR_ARG;
+  if (p->batch <= 0 || p->size <= 0) return MOBI_ERR_ARG;
+  if (p->size < 8 || p->size > 4096 || p->batch > 65535) return MOBI_ERR_UNSUPPORTED;   // (reflection needs size > halo)
+  const int tiles = (p->size + RA_TILE - 1) / RA_TILE;
+  hipLaunchKernelGGL(ref_augment_kernel, dim3(tiles, tiles, p->batch), dim3(256), 0, ST(stream), *p);
+  MOBI_CHECK_LAUNCH();
+  return MOBI_OK;
+}
+
+extern "C" int mobi_drop_context(float* gt, float* inpaint, const float* mask, const int32_t* flag, int32_t batch,
+                                 int32_t channels, int64_t hw, void* stream) {
+  if (!gt || !inpaint || !mask || !flag || batch <= 0 || channels <= 0 || hw <= 0) return MOBI_ERR_ARG;
+  if (batch > 65535) return MOBI_ERR_UNSUPPORTED;
+  const bool wide = hw % 4 == 0 && ((reinterpret_cast<uintptr_t>(gt) | reinterpret_cast<uintptr_t>(inpaint) |
+                                     reinterpret_cast<uintptr_t>(mask)) & 15) == 0;
+  int gx = egrid_pp(wide ? hw / 4 : hw);
+  gx = gx > 256 ? 256 : gx;
+  if (wide)
+    hipLaunchKernelGGL(drop_context_kernel<float4>, dim3(gx, batch), dim3(256), 0, ST(stream), gt, inpaint, mask, flag,
+                       channels, (long long)hw);
+  else
+    hipLaunchKernelGGL(drop_context_kernel<float>, dim3(gx, batch), dim3(256), 0, ST(stream), gt, inpaint, mask, flag,
+                       channels, (long long)hw);
   MOBI_CHECK_LAUNCH();
   return MOBI_OK;
 }

@@ -276,6 +276,7 @@ extern "C" size_t mobi_struct_size(int id) {
     case 25: return sizeof(mobi_grad_stats_record);
     case 26: return sizeof(mobi_mt_pair);
     case 27: return sizeof(mobi_loss_grad_params);
+    case 28: return sizeof(mobi_ref_augment_params);
     default: return 0;
   }
 }

@@ -15,8 +15,12 @@ whole batch in one launch.
 Third-party pieces of the reference that are absent here are restated from their documentation (parity unpinned for
 exactly these): torchvision 0.11 `ToTensor` / `Normalize` / tensor `Resize` (bilinear, align_corners=False, no
 antialias), albumentations 0.4 `Resize` = `cv2.resize(..., INTER_LINEAR)` on uint8 (`resize_linear_u8`), cv2.fillPoly
-(`utils.fill_box_faces`), cv2.resize INTER_NEAREST (`LidarConverter._nearest`).  The reference-image augmentations
-(`ref_aug=True`: flip / rotate / blur / brightness-contrast) belong to the training row and are not built."""
+(`utils.fill_box_faces`), cv2.resize INTER_NEAREST (`LidarConverter._nearest`), and the reference-image augmentations
+of the train / val splits (`ref_aug=True`: albumentations 0.4.3 flip / rotate / blur / brightness-contrast on OpenCV,
+`ref_aug.py`; on the device `ops.ref_augment`, one launch per batch inside `collate_device`).
+
+Training batches come from `NuScenesDataset.device_loader`: DataLoader workers build `raw_item`s and only gather them
+into lists; `collate_device` runs in the consuming process, so no worker process ever opens the GPU."""
 import json
 import os
 import pickle
@@ -30,6 +34,7 @@ import torch.nn.functional as F
 import torch.utils.data as data
 
 from .lidar_converter import LidarConverter
+from .ref_aug import device_form, draw_ref_aug, ref_augment_u8
 from .utils import (depth_normalization, expand_bbox_corners, fill_box_faces, get_2d_bbox, get_image_coords,
                     get_inpaint_mask, rotate_bbox, translate_bbox)
 
@@ -104,9 +109,9 @@ class NuScenesDataset(data.Dataset):
                  use_lidar=False, use_camera=True, random_range_crop=False, num_samples_per_class=None, prob_erase_box=0,
                  fixed_sampling=True, sample_each_frame=False, return_original_image=False, range_object_norm=True,
                  range_object_norm_scale=0.75, range_int_norm=False, object_meta_dump_path=None, specific_object=None):
-        if ref_aug:
-            raise NotImplementedError("reference-image augmentation (ref_aug=True) is the training row's; the sampling "
-                                      "configs (data.params.test / rotation_test) use ref_aug: false")
+        if ref_aug and state == "test":
+            raise NotImplementedError("reference-image augmentation (ref_aug=True) is for the train / val splits; the "
+                                      "sampling configs (data.params.test / rotation_test) use ref_aug: false")
         self.state, self.ref_aug, self.ref_mode = state, ref_aug, ref_mode
         self.expand_mask_ratio, self.expand_ref_ratio = expand_mask_ratio, expand_ref_ratio
         self.prob_use_3d_edit_mask, self.prob_drop_context = prob_use_3d_edit_mask, prob_drop_context
@@ -194,7 +199,12 @@ class NuScenesDataset(data.Dataset):
 
     def raw_item(self, index):
         """`__getitem__` without the range view's per-pixel work: the lidar part carries the untouched sweep, the crop
-        window and the edit region's corner pixels; `collate_device` finishes a list of these on the GPU."""
+        window and the edit region's corner pixels; `collate_device` finishes a list of these on the GPU.  It consumes the
+        draws of `random` that `__getitem__` consumes, at the same places (erase box, the augmentation record, the two
+        context drops); only a random crop window (`object_random_crop`) is placed by `collate_device`, which alone
+        knows the edit region's extent.  With `ref_aug` the item carries `ref_aug` = {patch uint8 [224, 224, 3], flags,
+        warp, table} (`ref_aug.device_form`) instead of `cond.ref_image`; with `prob_drop_context` each modality carries
+        its `drop_context` draw."""
         return self._build(index, raw=True)
 
     def _build(self, index, raw):
@@ -203,19 +213,22 @@ class NuScenesDataset(data.Dataset):
             scene, cam_idx = self.scenes_info[self.rot_test_scene], self.rot_test_cam_idx
         else:
             scene, cam_idx = self.scenes_info[meta["scene_token"]], meta["cam_idx"]
-        ref_image, ref_box, ref_class = self.get_reference(meta, index)
+        ref_image, ref_box, ref_class = self.get_reference(meta, index, raw=raw)
+        cond_ref = {} if raw and self.ref_aug else {"ref_image": ref_image}
         if self.rot_test_scene is None:
             box = scene["gt_bboxes_3d_corners"][meta["scene_obj_idx"]]
         else:
             box = translate_bbox(ref_box, self.rot_test_bbox_coord)
         box = rotate_bbox(box, meta.get("bbox_rot_angle", 0))
         item = {"id_name": self.get_id_name(meta), "bbox_3d": box, "ref_class": ref_class, "image": {}, "lidar": {}}
+        if raw and self.ref_aug:
+            item["ref_aug"] = ref_image                      # (patch + draws; `collate_device` makes cond.ref_image)
         if self.use_camera:
             item["image"] = self.get_image_data(scene, cam_idx, box, raw=raw)
-            item["image"]["cond"]["ref_image"] = ref_image
+            item["image"]["cond"].update(cond_ref)
         if self.use_lidar:
             item["lidar"] = self.get_range_data(scene, box, meta["scene_obj_idx"], raw=raw)
-            item["lidar"]["cond"]["ref_image"] = ref_image
+            item["lidar"]["cond"].update(cond_ref)
             if self.use_camera and not raw:                  # the camera box token carries the RANGE-view depth code
                 item["image"]["cond"]["ref_bbox"][..., 2] = item["lidar"]["cond"]["ref_bbox"][..., 2]
         erase = bool(meta["is_erase_box"] or self.ref_mode == "erase-ref")
@@ -260,7 +273,9 @@ class NuScenesDataset(data.Dataset):
             self.__dict__["_last_frame"] = hit
         return hit[1]
 
-    def get_reference(self, current_object_meta, index):
+    def get_reference(self, current_object_meta, index, raw=False):
+        """(ref_image, box, class); raw=True with `ref_aug`: the resized patch and the draws' device form instead of
+        the finished image (`ops.ref_augment` runs the chain for the whole batch)."""
         meta = self._reference_meta(current_object_meta, index)
         scene = self.scenes_info[meta["scene_token"]]
         cam = meta["cam_idx"]
@@ -274,8 +289,13 @@ class NuScenesDataset(data.Dataset):
             x1, y1, x2, y2 = get_2d_bbox(box, scene["lidar2image_transforms"][cam], H, W, self.expand_ref_ratio)
             w, h = np.maximum(x2 - x1 + 1, 1), np.maximum(y2 - y1 + 1, 1)
             patch = frame[y1:y1 + h, x1:x1 + w]
-        patch = resize_linear_u8(patch, 224, 224)
-        return get_tensor_clip()(patch), box, ref_class
+        patch = resize_linear_u8(patch, 224, 224)          # (an erase item's zero patch goes through the chain too)
+        if not self.ref_aug:
+            return get_tensor_clip()(patch), box, ref_class
+        draw = draw_ref_aug()
+        if raw:
+            return dict(device_form(draw), patch=torch.from_numpy(patch)), box, ref_class
+        return get_tensor_clip()(ref_augment_u8(patch, draw)), box, ref_class
 
     def get_id_name(self, object_meta):
         name = "sample-{}_track-{}_time-{}_{}_{}_rot-{}".format(
@@ -336,6 +356,9 @@ class NuScenesDataset(data.Dataset):
                "file_name": scene_info["lidar_path"].split("/")[-1]}
         if raw:
             out["range_mask_corners"] = torch.from_numpy(mcoords[:, :2].astype(np.int32))
+            drop = random.random() < self.prob_drop_context  # (drawn where the host path draws it)
+            if self.prob_drop_context:
+                out["drop_context"] = drop
             return out
         mask = (1. - torch.tensor(fill_box_faces(mcoords[:, :2].astype(np.int32), self.range_height, self.range_width) > 0.5).float()).unsqueeze(0)
         out["range_mask"] = mask
@@ -399,8 +422,12 @@ class NuScenesDataset(data.Dataset):
         corners = self._edit_corners(bbox_3d, lidar2image, H, W)
         extra = {"file_name": path.split("/")[-1], "cam_type": scene_info["cam_types"][cam_idx], "lidar2image": lidar2image}
         if raw:                                               # the pixels are `collate_device`'s
-            return {"frame": torch.from_numpy(frame), "mask_corners": torch.from_numpy(corners),
-                    "token": torch.from_numpy(token), "cond": {}, "orig": extra}
+            out = {"frame": torch.from_numpy(frame), "mask_corners": torch.from_numpy(corners),
+                   "token": torch.from_numpy(token), "cond": {}, "orig": extra}
+            drop = random.random() < self.prob_drop_context
+            if self.prob_drop_context:
+                out["drop_context"] = drop
+            return out
         image = get_tensor()(frame)
         mask = 1. - torch.tensor(fill_box_faces(corners, H, W) > 0.5).float()
         if self.return_original_image:
@@ -436,16 +463,23 @@ class NuScenesDataset(data.Dataset):
         edit region's pixel count and extent (one small read-back), the host places the crop windows, `mobi_image_prepare`
         normalises / masks / crops / resizes all frames in one launch.  Lidar: `mobi_box_mask` rasterises the edit regions,
         `mobi_range_prepare` does tile x 3 -> window -> nearest resize, depth / intensity normalisation and the edit-mask
-        product in one launch."""
+        product in one launch.  Reference images of `ref_aug` items: `mobi_ref_augment`, the whole chain for the batch in
+        one launch.  Context drops (`prob_drop_context`): `mobi_drop_context` per modality, launched only when a sample
+        of the batch drew one."""
         from torch.utils.data import default_collate
         from ... import ops
         batch = default_collate(items)
+        aug = batch.pop("ref_aug", None)                      # (flags stay on the host: `ops.ref_augment` checks them)
+        drops = {k: [bool(it[k].get("drop_context", False)) for it in items] for k in ("image", "lidar")}
         move = lambda d: {k: move(v) if isinstance(v, dict) else (v.to(device) if isinstance(v, torch.Tensor) else v)
                           for k, v in d.items()}
         batch = move(batch)
-        if self.prob_drop_context:
-            raise NotImplementedError("context dropping is a training-side option")
         erase = batch.pop("erase")
+        if aug is not None:
+            ref = ops.ref_augment(aug["patch"].to(device), aug["flags"], aug["warp"].to(device), aug["table"].to(device))
+            for k in ("image", "lidar"):
+                if batch[k]:
+                    batch[k]["cond"]["ref_image"] = ref
         if self.use_camera:
             img = batch["image"]
             frames, corners, token = img.pop("frame"), img.pop("mask_corners"), img.pop("token").cpu().numpy()
@@ -460,6 +494,9 @@ class NuScenesDataset(data.Dataset):
             crop_t = torch.tensor(crops, dtype=torch.int32)
             img["GT"], img["inpaint_image"], img["inpaint_mask"] = ops.image_prepare(
                 frames, corners, invert, crop_t, height=self.image_height, width=self.image_width)
+            img.pop("drop_context", None)
+            if any(drops["image"]):
+                ops.drop_context(img["GT"], img["inpaint_image"], img["inpaint_mask"], drops["image"])
             token = token - np.array([[[c[0], c[1], 0]] for c in crops], dtype=np.float64)
             token[..., 0] /= np.array([c[2] for c in crops], dtype=np.float64)[:, None]
             token[..., 1] /= np.array([c[3] for c in crops], dtype=np.float64)[:, None]
@@ -483,5 +520,43 @@ class NuScenesDataset(data.Dataset):
             lid["range_shift_left"], lid["width_crop"], lid["min_depth_obj"].float(), lid["max_depth_obj"].float(),
             lid["range_mask"], height=self.range_height, width=self.range_width,
             alpha=self.range_object_norm_scale, object_norm=bool(self.range_object_norm), int_norm=bool(self.range_int_norm))
+        lid.pop("drop_context", None)
+        if any(drops["lidar"]):
+            ops.drop_context(rd, rdi, lid["range_mask"], drops["lidar"])
         lid.update(range_data=rd, range_data_inpaint=rdi, range_instance_mask=inst)
         return batch
+
+    def device_loader(self, batch_size, num_workers=0, shuffle=False, drop_last=False, device="cuda"):
+        """Batches finished on the device, with the GPU kept out of worker processes: a DataLoader over `raw_item` whose
+        collate only gathers each batch's items into a list (`.inner`; its workers never import `mobi_amd.ops` or touch
+        the device), and `collate_device` on every list in the process that iterates."""
+        return DeviceLoader(self, batch_size, num_workers, shuffle, drop_last, device)
+
+
+class _RawItems(data.Dataset):
+    def __init__(self, dataset):
+        self.dataset = dataset
+
+    def __len__(self):
+        return len(self.dataset)
+
+    def __getitem__(self, index):
+        return self.dataset.raw_item(index)
+
+
+def _gather(items):
+    return items
+
+
+class DeviceLoader:
+    def __init__(self, dataset, batch_size, num_workers=0, shuffle=False, drop_last=False, device="cuda"):
+        self.dataset, self.device = dataset, device
+        self.inner = data.DataLoader(_RawItems(dataset), batch_size=batch_size, num_workers=num_workers, shuffle=shuffle,
+                                     drop_last=drop_last, collate_fn=_gather)
+
+    def __len__(self):
+        return len(self.inner)
+
+    def __iter__(self):
+        for items in self.inner:
+            yield self.dataset.collate_device(items, device=self.device)

@@ -1564,6 +1564,46 @@ def image_prepare(frames, corners_xy, invert, crop, *, height, width):
     return gt, inp, mask
 
 
+def ref_augment(patches, flags, warp, table):
+    """Dataset side of the train / val splits, a whole batch in one launch (include/mobi_engine.h, mobi_ref_augment):
+    patches uint8 [B, S, S, 3], flags int [B, 2] = (1: flip | 2: rotate, box side 0 | 3 | 5 | 7), warp int32 [B, 4, S],
+    table fp32 [B, 3, 256] (`ldm.data.ref_aug.device_form` per sample) -> fp32 [B, 3, S, S]."""
+    lib = _lib.load()
+    patches = _dev(patches).contiguous()
+    assert patches.dtype == torch.uint8 and patches.dim() == 4 and patches.shape[3] == 3 and patches.shape[1] == patches.shape[2]
+    b, s = patches.shape[:2]
+    dev = patches.device
+    fl = torch.as_tensor(flags)
+    if not fl.is_cuda:                                                   # (device-resident flags: the kernel clamps)
+        fl = fl.reshape(b, 2)
+        if bool(((fl[:, 0] < 0) | (fl[:, 0] > 3)).any()) or any(int(k) not in (0, 3, 5, 7) for k in fl[:, 1]):
+            raise ValueError("ref_augment: flags are (flip | 2 * rotate, box side 0 | 3 | 5 | 7)")
+    fl = _i32(flags, dev)
+    warp, table = torch.as_tensor(warp).to(dev).contiguous(), torch.as_tensor(table).to(dev).contiguous()
+    assert fl.numel() == 2 * b and warp.dtype == torch.int32 and tuple(warp.shape) == (b, 4, s)
+    assert table.dtype == torch.float32 and tuple(table.shape) == (b, 3, 256)
+    out = torch.empty((b, 3, s, s), device=dev, dtype=torch.float32)
+    p = _lib.RefAugmentParams()
+    p.src, p.flags, p.warp, p.table, p.out = _ptr(patches), _ptr(fl), _ptr(warp), _ptr(table), _ptr(out)
+    p.batch, p.size = b, s
+    _lib.check(lib.mobi_ref_augment(C.byref(p), _stream()), "mobi_ref_augment")
+    return out
+
+
+def drop_context(gt, inpaint, mask, flags):
+    """In place, for the samples with flags[b] set (include/mobi_engine.h, mobi_drop_context): inpaint[b] = 0 and
+    gt[b] = gt[b] * (1 - mask[b]); gt / inpaint fp32 [B, C, H, W], mask fp32 [B, 1, H, W]."""
+    lib = _lib.load()
+    for t in (gt, inpaint, mask):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 4
+    b, c, h, w = gt.shape
+    assert inpaint.shape == gt.shape and tuple(mask.shape) == (b, 1, h, w)
+    fl = _i32(torch.as_tensor(flags).to(torch.int32), gt.device)
+    assert fl.numel() == b
+    _lib.check(lib.mobi_drop_context(_ptr(gt), _ptr(inpaint), _ptr(mask), _ptr(fl), b, c, h * w, _stream()), "mobi_drop_context")
+    return gt, inpaint
+
+
 def lidar_metrics(pred, gt, inst_mask, box_mask, width_crop, pool_h=32):
     """fp32 [B, H, W] each (0/1 masks) -> fp32 [B, 2 regions (object, mask), 3 (rmse, median, count)] on the device."""
     lib = _lib.load()
