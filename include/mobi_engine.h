@@ -53,7 +53,8 @@ extern "C" {
  *      mobi_grad_stats_record 25); likewise the EMA / swap pass over tensor pairs, mobi_ema_multi (mobi_mt_pair 26); likewise
  *      the gradient accumulation over the same pair tables, mobi_accum_multi (no new struct); likewise the fused loss /
  *      entering-gradient launch mobi_loss_grad + mobi_loss_grad_blocks_per_sample (mobi_loss_grad_params 27); likewise the
- *      training splits' data side, mobi_ref_augment (mobi_ref_augment_params 28) and mobi_drop_context (no struct) */
+ *      training splits' data side, mobi_ref_augment (mobi_ref_augment_params 28) and mobi_drop_context (no struct); likewise the checkpoint
+ *      snapshot over the pair tables, mobi_snapshot_multi (mobi_snapshot_record 29) */
 #define MOBI_ABI_VERSION 6
 
 enum { MOBI_OK = 0, MOBI_ERR_ARG = -1, MOBI_ERR_UNSUPPORTED = -2, MOBI_ERR_LAUNCH = -3, MOBI_ERR_ALIGN = -4 };
@@ -66,7 +67,7 @@ const char* mobi_error_string(int code);
  * 3 attention, 4 ctx_attention, 5 skinny_linear, 6 conv_small_cin, 7 conv_small_cout,
  * 8 ddim_step, 9 two_key_adapter, 10 range_paste, 11 lidar_metrics, 12 range_prepare, 13 image_prepare, 14 ff_geglu,
  * 15 row_chain, 16 chain_op, 17 layernorm_bwd, 18 attention_bwd, 19 split_source, 20 dpm_step, 21 lpips_distance,
- * 22 image_normalize, 23 mt_tensor, 24 mt_chunk, 25 grad_stats_record, 26 mt_pair, 27 loss_grad, 28 ref_augment.
+ * 22 image_normalize, 23 mt_tensor, 24 mt_chunk, 25 grad_stats_record, 26 mt_pair, 27 loss_grad, 28 ref_augment, 29 snapshot_record.
  * Returns 0 for an unknown id. */
 size_t mobi_struct_size(int id);
 /* Development hook: the library reads its MOBI_* A/B environment variables once, at the first launch
@@ -495,6 +496,21 @@ int mobi_ema_multi(const mobi_mt_pair* pairs, int32_t n_pairs, const mobi_mt_chu
 enum { MOBI_MT_ACCUM = 0, MOBI_MT_ASSIGN = 1 };
 int mobi_accum_multi(const mobi_mt_pair* pairs, int32_t n_pairs, const mobi_mt_chunk* chunks, int32_t n_chunks, float w,
                      int32_t op, void* stream);
+
+/* The checkpoint snapshot: one launch over the same pair tables and chunk map.  a = a tensor a training step mutates (read
+ * only), b = its place in a staging buffer: b[i] <- a[i] as a move of 32-bit words, no arithmetic (MOBI_MT_ASSIGN with w = 1 is
+ * a multiply, which may touch denormals and NaN payloads).  b == NULL for a pair: statistics only, nothing is written for it.
+ *   out[p].digest    = sum_i uint64(u_i ^ 0x9E3779B9) * uint64((2 i + 1) mod 2^32)  (mod 2^64), u_i the bit pattern of element i
+ *                      of pair p, i its index in the tensor: one 32 x 32 -> 64 multiply-add per element
+ *   out[p].nonfinite = 1 if any element of pair p has all exponent bits set (inf or nan), else 0
+ * out: DEVICE, [n_pairs], 8-byte aligned (MOBI_ERR_ALIGN otherwise); zeroed on the stream, then every wave adds what it summed
+ * for a tensor with ONE 64-bit vector atomic add (and ors the flag in): wrapping integer sums commute, so the records are
+ * bit-equal run to run and independent of grid and map order.  `workspace` is not used (may be NULL): nothing is staged.
+ * NULL pairs / chunks / out, n_pairs <= 0 or n_chunks <= 0: MOBI_ERR_ARG before anything is enqueued.  Addition to ABI 6 (struct
+ * id 29). */
+typedef struct mobi_snapshot_record { uint64_t digest; int32_t nonfinite; int32_t reserved; } mobi_snapshot_record;
+int mobi_snapshot_multi(const mobi_mt_pair* pairs, int32_t n_pairs, const mobi_mt_chunk* chunks, int32_t n_chunks,
+                        void* workspace, mobi_snapshot_record* out, void* stream);
 
 typedef struct mobi_attention_bwd_params {
   const void* q; int64_t q_img_stride, q_row_stride;       /* T [image][tq][>= heads*dh], strides in elements */

@@ -2,10 +2,12 @@
 // AdamW.step_scaled): the gradient statistics (sum of squares + non-finite flag) and the AdamW update of EVERY listed tensor in one
 // launch each, instead of one launch per tensor (432 adapter tensors + the conditioning stage's: ~880 launches of a few hundred KB
 // to a few MB each); the EMA update / swap of every (parameter, shadow) pair (mobi_amd/ldm/modules/ema.py); and the gradient
-// accumulation of a window of micro-batches (mobi_amd/train.py GradAccumulator).  All kernels walk a device-resident table of tensors through a device-resident chunk map: every tensor is cut
+// accumulation of a window of micro-batches (mobi_amd/train.py GradAccumulator); and the checkpoint snapshot (mobi_amd/checkpoint.py): a
+// word-for-word copy of every mutable tensor with a 64-bit digest and a non-finite flag per tensor.  All kernels walk a device-resident table of tensors through a device-resident chunk map: every tensor is cut
 // into chunks of kMtChunk elements, one 256-thread block takes chunks in a grid-stride walk, the grid follows the CU count.  Pure
 // streaming: 16-byte accesses on the 16-byte-aligned body of a chunk, 4-byte accesses on its head and tail (a tensor may start at
-// any 4-byte boundary); no atomics, LDS only for the block reduction of the statistics.
+// any 4-byte boundary); no atomics, LDS only for the block reduction of the statistics -- except the snapshot,
+// whose per-tensor integer sums meet by one 64-bit vector atomic add per wave and tensor (order-free: wrapping sums commute).
 #include "adamw.h"
 #include "common.h"
 
@@ -232,6 +234,90 @@ __global__ __launch_bounds__(kMtBlock) void pair_multi_kernel(const mobi_mt_pair
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Snapshot: b <- a as a move of 32-bit words (no arithmetic: denormals, both zeros and NaN payloads arrive as they left; where
+// b is NULL nothing is written) while every word enters its tensor's digest, sum_i uint64(u_i ^ 0x9E3779B9) * uint64((2 i + 1)
+// mod 2^32) mod 2^64 (i: the element's index in its tensor), and the non-finite flag (exponent bits all set).  One 32 x 32 -> 64
+// multiply-add per element.  A thread keeps its sum across the chunks of its walk for as long as they belong to one tensor;
+// when the tensor changes, and at the end, every wave adds its lanes up and lane 0 issues ONE 64-bit vector atomic add into
+// the tensor's record (and one atomic or of the flag, only where it is set).  Wrapping integer sums commute: the records do
+// not depend on the grid, the order of the map or the order in which the atomics land.  The records are zeroed on the stream
+// in front of the launch.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kDigestXor = 0x9E3779B9u;
+
+__device__ __forceinline__ void snapshot_flush(mobi_snapshot_record* __restrict__ out, int tensor, unsigned long long s, int bad) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    s += (unsigned long long)__shfl_xor((long long)s, o, 64);
+    bad |= __shfl_xor(bad, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (s) atomicAdd(reinterpret_cast<unsigned long long*>(&out[tensor].digest), s);
+    if (bad) atomicOr(&out[tensor].nonfinite, 1);
+  }
+}
+
+// one chunk: [0, head) and [tail0, len) word by word, the 16-byte aligned body between them four words at a time.  COPY is
+// decided per chunk, outside the loops: with the test inside, every store waits for its load before the next load is issued
+template <bool COPY>
+__device__ __forceinline__ void snapshot_chunk(const uint32_t* __restrict__ a, uint32_t* __restrict__ b, long long off, int len,
+                                               int head, unsigned long long& s, int& bad) {
+  const int tid = threadIdx.x;
+  const int nvec = (len - head) >> 2, tail0 = head + (nvec << 2);
+  auto word = [&](uint32_t u, long long i) {         // i: the index in the tensor
+    s += (unsigned long long)(u ^ kDigestXor) * (unsigned long long)(uint32_t)(2ull * (unsigned long long)i + 1ull);
+    bad |= (u & 0x7f800000u) == 0x7f800000u;
+  };
+  auto one = [&](int i) {
+    const uint32_t u = a[i];
+    if (COPY) b[i] = u;
+    word(u, off + i);
+  };
+  for (int i = tid; i < head; i += kMtBlock) one(i);
+  for (int i = tail0 + tid; i < len; i += kMtBlock) one(i);
+  const u32x4* __restrict__ av = reinterpret_cast<const u32x4*>(a + head);
+  u32x4* __restrict__ bv = COPY ? reinterpret_cast<u32x4*>(b + head) : nullptr;
+#pragma unroll 4
+  for (int i = tid; i < nvec; i += kMtBlock) {
+    const u32x4 q = av[i];
+    if (COPY) bv[i] = q;
+    const long long i0 = off + head + ((long long)i << 2);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) word(q[j], i0 + j);
+  }
+}
+
+__global__ __launch_bounds__(kMtBlock) void snapshot_multi_kernel(const mobi_mt_pair* __restrict__ pairs, int n_pairs,
+                                                                  const mobi_mt_chunk* __restrict__ chunks, int n_chunks,
+                                                                  mobi_snapshot_record* __restrict__ out) {
+  const int tid = threadIdx.x;
+  unsigned long long s = 0;
+  int bad = 0, cur = -1;                             // cur: the tensor `s` and `bad` belong to (the same for every thread of the block)
+  for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+    mobi_mt_pair t;
+    long long off;
+    int len;
+    if (!mt_chunk(pairs, n_pairs, chunks, c, t, off, len)) continue;
+    const int tensor = chunks[c].tensor;
+    if (tensor != cur) {
+      if (cur >= 0) snapshot_flush(out, cur, s, bad);
+      s = 0, bad = 0, cur = tensor;
+    }
+    const uint32_t* __restrict__ a = reinterpret_cast<const uint32_t*>(t.a) + off;
+    uint32_t* __restrict__ b = t.b ? reinterpret_cast<uint32_t*>(t.b) + off : nullptr;
+    const int ph = mt_phase(a);
+    const bool same = !b || ph == mt_phase(b);
+    const int head = same && ph < len ? ph : len;
+    if (b) {
+      snapshot_chunk<true>(a, b, off, len, head, s, bad);
+    } else {
+      snapshot_chunk<false>(a, b, off, len, head, s, bad);
+    }
+  }
+  if (cur >= 0) snapshot_flush(out, cur, s, bad);
+}
+
 static int mt_grid(int n_chunks) {
   static int cus = 0;
   if (!cus) {
@@ -305,4 +391,15 @@ extern "C" int mobi_accum_multi(const mobi_mt_pair* pairs, int32_t n_pairs, cons
   if (op == MOBI_MT_ACCUM) return launch_pairs<kPairAccum>(pairs, n_pairs, chunks, n_chunks, w, stream);
   if (op == MOBI_MT_ASSIGN) return launch_pairs<kPairAssign>(pairs, n_pairs, chunks, n_chunks, w, stream);
   return MOBI_ERR_ARG;
+}
+
+extern "C" int mobi_snapshot_multi(const mobi_mt_pair* pairs, int32_t n_pairs, const mobi_mt_chunk* chunks, int32_t n_chunks,
+                                   void* workspace, mobi_snapshot_record* out, void* stream) {
+  (void)workspace;                                   // the per-tensor sums meet by atomics: nothing is staged
+  if (!pairs_args_ok(pairs, n_pairs, chunks, n_chunks) || !out) return MOBI_ERR_ARG;
+  if (reinterpret_cast<uintptr_t>(out) & 7) return MOBI_ERR_ALIGN;
+  if (hipMemsetAsync(out, 0, (size_t)n_pairs * sizeof(mobi_snapshot_record), ST(stream)) != hipSuccess) return MOBI_ERR_LAUNCH;
+  hipLaunchKernelGGL(snapshot_multi_kernel, dim3(mt_grid(n_chunks)), dim3(kMtBlock), 0, ST(stream), pairs, n_pairs, chunks, n_chunks, out);
+  MOBI_CHECK_LAUNCH();
+  return MOBI_OK;
 }

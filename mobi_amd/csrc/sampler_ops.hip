@@ -277,6 +277,7 @@ extern "C" size_t mobi_struct_size(int id) {
     case 26: return sizeof(mobi_mt_pair);
     case 27: return sizeof(mobi_loss_grad_params);
     case 28: return sizeof(mobi_ref_augment_params);
+    case 29: return sizeof(mobi_snapshot_record);
     default: return 0;
   }
 }

@@ -526,11 +526,13 @@ class NuScenesDataset(data.Dataset):
         lid.update(range_data=rd, range_data_inpaint=rdi, range_instance_mask=inst)
         return batch
 
-    def device_loader(self, batch_size, num_workers=0, shuffle=False, drop_last=False, device="cuda"):
+    def device_loader(self, batch_size, num_workers=0, shuffle=False, drop_last=False, device="cuda", sampler=None):
         """Batches finished on the device, with the GPU kept out of worker processes: a DataLoader over `raw_item` whose
         collate only gathers each batch's items into a list (`.inner`; its workers never import `mobi_amd.ops` or touch
-        the device), and `collate_device` on every list in the process that iterates."""
-        return DeviceLoader(self, batch_size, num_workers, shuffle, drop_last, device)
+        the device), and `collate_device` on every list in the process that iterates.  sampler: an iterable of index lists, one
+        per batch (`train.EpochSampler`), in place of batch_size / shuffle / drop_last; the loader then seeds its workers from
+        `sampler.loader_seed` (0 without one) and never draws from torch's global generator."""
+        return DeviceLoader(self, batch_size, num_workers, shuffle, drop_last, device, sampler)
 
 
 class _RawItems(data.Dataset):
@@ -549,10 +551,18 @@ def _gather(items):
 
 
 class DeviceLoader:
-    def __init__(self, dataset, batch_size, num_workers=0, shuffle=False, drop_last=False, device="cuda"):
+    def __init__(self, dataset, batch_size, num_workers=0, shuffle=False, drop_last=False, device="cuda", sampler=None):
         self.dataset, self.device = dataset, device
-        self.inner = data.DataLoader(_RawItems(dataset), batch_size=batch_size, num_workers=num_workers, shuffle=shuffle,
-                                     drop_last=drop_last, collate_fn=_gather)
+        if sampler is not None:
+            # A DataLoader draws the base seed of its worker processes whenever an iterator is made, with or without workers,
+            # from torch's global CPU generator unless it has one of its own.  Under a sampler it has: making the iterator
+            # leaves the global generator where a checkpoint recorded it, and a worker's seed depends on the sampler's alone.
+            own = torch.Generator().manual_seed(int(getattr(sampler, "loader_seed", 0)))
+            self.inner = data.DataLoader(_RawItems(dataset), batch_sampler=sampler, num_workers=num_workers, collate_fn=_gather,
+                                         generator=own)
+        else:
+            self.inner = data.DataLoader(_RawItems(dataset), batch_size=batch_size, num_workers=num_workers, shuffle=shuffle,
+                                         drop_last=drop_last, collate_fn=_gather)
 
     def __len__(self):
         return len(self.inner)

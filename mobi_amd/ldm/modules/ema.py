@@ -28,6 +28,7 @@ class LitEma(nn.Module):
         self.collected_params = []
         self._host = None               # (decay: np.float32, num_updates: int) as the buffers hold them, read once
         self._pairs = None              # ops.MultiTensorTable over (parameter, shadow), built at the first launch
+        self.swapped = False            # True between the two swaps of an `ema_scope`: the buffers then hold the live weights
 
     def _load_from_state_dict(self, *args, **kwargs):
         self._host = None               # a checkpoint brings its own decay and update count
@@ -74,9 +75,12 @@ class LitEma(nn.Module):
     def swap(self, model):
         """Exchange every parameter with its shadow, one launch, no copy of either.  The parameters change under the packed
         16-bit copies and captured step graphs that are keyed on them: every swapped parameter's version and the weights
-        epoch are bumped, as `train.AdamW.step` does."""
+        epoch are bumped, as `train.AdamW.step` does.  Every call toggles `swapped`, not only `ema_scope`'s two: after a single
+        swap made on purpose the buffers hold the live weights, and `checkpoint.Checkpointer.save` refuses until a second
+        swap puts them back."""
         pairs, params = self._table(model)
         ops.swap_multi(pairs)
+        self.swapped = not self.swapped
         weights_changed(params)
 
     @torch.no_grad()

@@ -640,8 +640,9 @@ class MultiTensorTable:
     chunk map {element offset, tensor index} (`multi_tensor_chunk_map`'s, or `chunk_map`: one of the caller's own in its format).
     columns: lists of dense fp32 tensors on one device, row i of every column of numel n_i -- [params, LIVE, exp_avgs,
     exp_avg_sqs] for `grad_stats` / `adamw_multi`, [a_list, b_list] for `ema_multi` / `swap_multi`, [LIVE, b_list] for
-    `accum_multi`.  The listed tensors are kept alive and their pointers are stable (`ptrs`, per row, is what a caller compares
-    to notice that one moved): without a LIVE column everything is uploaded once.  A LIVE column (one at most) holds pointers
+    `accum_multi`, [a_list, b_list] with None wherever a pair has no destination for `snapshot_multi` (`has_null`: `ready`
+    refuses such a table to every other kernel).  The listed tensors are kept alive and their pointers are stable (`ptrs`,
+    per row, is what a caller compares to notice that one moved): without a LIVE column everything is uploaded once.  A LIVE column (one at most) holds pointers
     that change every call (this step's gradients): the rows then live in pinned host memory and `set_live` rewrites the column
     and copies the rows on the current stream.  The host rows are not rewritten before that copy has completed: `set_live`
     waits on the copy's event first (already signalled where a step read a result back, as `AdamW.step_scaled` does)."""
@@ -652,12 +653,17 @@ class MultiTensorTable:
         assert fixed and len(fixed) >= len(columns) - 1 and len(fixed[0]) > 0 and all(len(c) == len(fixed[0]) for c in fixed)
         self.device, self.count, self.width = fixed[0][0].device, len(fixed[0]), len(columns)
         self.numels = [t_.numel() for t_ in fixed[0]]
-        for c in fixed:
+        self.has_null = False
+        for col, c in enumerate(fixed):
             for t_, n in zip(c, self.numels):
+                if t_ is None and col > 0:             # a NULL pointer in the row (`snapshot_multi`: statistics only for this pair)
+                    self.has_null = True               # (`ready` refuses the table to every other kernel)
+                    continue
                 assert _dev(t_).dtype == torch.float32 and t_.is_contiguous() and t_.numel() == n > 0 and t_.device == self.device
         self._keep = fixed
-        self.ptrs = tuple(zip(*[[t_.data_ptr() for t_ in c] for c in fixed]))
-        rows = multi_tensor_rows([LIVE if c is LIVE else [t_.data_ptr() for t_ in c] for c in columns], self.numels)
+        ptr = lambda t_: 0 if t_ is None else t_.data_ptr()
+        self.ptrs = tuple(zip(*[[ptr(t_) for t_ in c] for c in fixed]))
+        rows = multi_tensor_rows([LIVE if c is LIVE else [ptr(t_) for t_ in c] for c in columns], self.numels)
         cmap = multi_tensor_chunk_map(self.numels) if chunk_map is None else chunk_map
         self.n_chunks = len(cmap)
         self.chunks = torch.from_numpy(cmap.view(np.uint8)).to(self.device)        # (a blocking copy, once)
@@ -688,9 +694,11 @@ class MultiTensorTable:
         self._copied.record()
         self._live = tensors
 
-    def ready(self, width):
-        """What every launch asserts: the table has the kernel's row layout and its LIVE column, if any, has been set."""
+    def ready(self, width, null_ok=False):
+        """What every launch asserts: the table has the kernel's row layout, its LIVE column, if any, has been set, and it holds
+        no NULL pointer unless the kernel tests for one (null_ok: `snapshot_multi` alone; the others would dereference it)."""
         assert self.width == width, f"a table of {self.width} pointer columns where the kernel reads {width}"
+        assert null_ok or not self.has_null, "a table with a None (`snapshot_multi`'s) for a kernel that reads every pointer"
         assert self._live_col is None or self._live is not None, "set_live() first"
 
 
@@ -744,6 +752,25 @@ def accum_multi(table, w, op):
     table.ready(2)
     _lib.check(lib.mobi_accum_multi(_ptr(table.rows), table.count, _ptr(table.chunks), table.n_chunks, float(w), int(op),
                                     _stream()), "mobi_accum_multi")
+
+
+def snapshot_multi(table):
+    """b <- a word for word for every pair of `table` (a MultiTensorTable [a_list, b_list]; a None in b_list: nothing is written
+    for that pair) and, per pair, the 64-bit digest of a and its non-finite flag (`mobi_snapshot_multi`), one launch -> the device
+    records, int64 [count, 2] (`_lib.SnapshotRecord`, a fresh tensor per call); `read_snapshot_records` brings them to the host."""
+    lib = _lib.load()
+    table.ready(2, null_ok=True)
+    rec = torch.empty((table.count, C.sizeof(_lib.SnapshotRecord) // 8), dtype=torch.int64, device=table.device)
+    _lib.check(lib.mobi_snapshot_multi(_ptr(table.rows), table.count, _ptr(table.chunks), table.n_chunks, None, _ptr(rec), _stream()),
+               "mobi_snapshot_multi")
+    return rec
+
+
+def read_snapshot_records(rec):
+    """The device records of `snapshot_multi` -> [(digest: int in [0, 2^64), nonfinite: bool)] per pair.  One blocking copy of
+    16 bytes per pair."""
+    host = rec.cpu().numpy()
+    return [(int(d) & 0xffffffffffffffff, bool(int(f) & 0xffffffff)) for d, f in host]
 
 
 def geglu_fwd(pre):

@@ -443,6 +443,15 @@ class LambdaLR:
     def get_last_lr(self):
         return [self.optimizer.lr]
 
+    def state_dict(self):
+        """`last_epoch` and `base_lrs` (the schedule function itself is code, rebuilt by `configure_optimizers`)."""
+        return {"last_epoch": int(self.last_epoch), "base_lrs": [float(x) for x in self.base_lrs]}
+
+    def load_state_dict(self, sd):
+        """Restores the position and re-applies `optimizer.lr = base_lr * lr_lambda(last_epoch)`."""
+        self.last_epoch, self.base_lrs = int(sd["last_epoch"]), [float(x) for x in sd["base_lrs"]]
+        self.optimizer.lr = self.base_lrs[0] * self.lr_lambda(self.last_epoch)
+
 
 def static_loss_scale(numel):
     """The loss scale `training_step` picks for fp16 from the element count of the UNet's output: a power of two near numel / 4
@@ -542,6 +551,63 @@ class AdamW:
         weights_changed(stepped.values())
         return self
 
+    def state_dict(self):
+        """torch.optim.AdamW's format: {"state": {index: {"step", "exp_avg", "exp_avg_sq"}}, "param_groups": [one group]}, the
+        index a tensor's position in `self.params` (`configure_optimizers`' order, the reference's).  The moments are the live
+        tensors, not copies.  A tensor that never had a gradient has no entry, as in torch.  The engine keeps ONE step count:
+        `self.steps` goes into every entry (an fp32 0-d tensor, as torch writes it)."""
+        state = {i: {"step": torch.tensor(float(self.steps)), "exp_avg": self.state[n][0], "exp_avg_sq": self.state[n][1]}
+                 for i, n in enumerate(self.params) if n in self.state}
+        group = {"lr": float(self.lr), "betas": tuple(float(b) for b in self.betas), "eps": float(self.eps),
+                 "weight_decay": float(self.weight_decay), "amsgrad": False,
+                 "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+                 "params": list(range(len(self.params)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, sd):
+        """The inverse of `state_dict`, also for a torch.optim.AdamW's over the same tensors in the same order.  All entries must
+        carry the same step count (ValueError otherwise: per-tensor counts have no place in one launch over all tensors).  Moments
+        are copied INTO the existing tensors where there are some -- the multi-tensor tables hold their addresses; where one is
+        created or removed the tables are dropped and rebuilt at the next step."""
+        groups = sd["param_groups"]
+        names = list(self.params)
+        if len(groups) != 1 or len(groups[0]["params"]) != len(names):
+            raise ValueError(f"an optimizer state of {len(groups)} groups / {sum(len(g['params']) for g in groups)} tensors where "
+                             f"this optimizer holds one group of {len(names)}")
+        group = groups[0]
+        if group.get("amsgrad", False):
+            raise ValueError("amsgrad=True: the engine's AdamW keeps no running maximum")
+        position = {pid: k for k, pid in enumerate(group["params"])}
+        entries = {names[position[pid]]: e for pid, e in sd["state"].items()}
+        steps = sorted({float(e["step"]) for e in entries.values()})
+        if len(steps) > 1:
+            raise ValueError(f"the optimizer state carries {len(steps)} different step counts ({steps[:4]} ...): the engine keeps "
+                             "ONE step count for all tensors and cannot load per-tensor counts")
+        if steps and (steps[0] != int(steps[0]) or steps[0] < 0):
+            raise ValueError(f"step count {steps[0]!r}")
+        for n, e in entries.items():
+            for key in ("exp_avg", "exp_avg_sq"):
+                if tuple(e[key].shape) != tuple(self.params[n].shape):
+                    raise ValueError(f"{n}: {key} of shape {tuple(e[key].shape)} for a tensor of shape {tuple(self.params[n].shape)}")
+        rebuilt = False
+        for n in [k for k in self.state if k not in entries]:
+            del self.state[n]
+            rebuilt = True
+        for n, e in entries.items():
+            if n in self.state:
+                self.state[n][0].copy_(e["exp_avg"])
+                self.state[n][1].copy_(e["exp_avg_sq"])
+            else:
+                dev = self.params[n].device
+                self.state[n] = tuple(e[key].detach().to(device=dev, dtype=torch.float32, copy=True).contiguous()
+                                      for key in ("exp_avg", "exp_avg_sq"))
+                rebuilt = True
+        if rebuilt:
+            self._multi = _TableCache()
+        self.steps = int(steps[0]) if steps else 0
+        self.lr, self.betas = float(group["lr"]), tuple(float(b) for b in group["betas"])
+        self.eps, self.weight_decay = float(group["eps"]), float(group["weight_decay"])
+
     def step_scaled(self, grads, scaler=None, max_norm=None):
         """`step()` for gradients that are still multiplied by `scaler.scale` (`training_step(..., scaler=s)`), with overflow
         skipping and gradient-norm clipping, in two launches whatever the number of tensors: `mobi_grad_stats` (fp64 sum of squares
@@ -633,6 +699,19 @@ class GradAccumulator:
         self._seen.update(first)
         self._adds, self._scale = self._adds + 1, float(scale)
 
+    def state_dict(self):
+        """Between windows the accumulator holds nothing a later window reads (its first add is an ASSIGN): {}.  Inside a window
+        it raises: a checkpoint is taken between optimizer steps."""
+        if self._adds != 0:
+            raise RuntimeError(f"state_dict() after {self._adds} of {self.micro_batches} micro-batches of a window: a checkpoint is "
+                               "taken between optimizer steps")
+        return {}
+
+    def load_state_dict(self, sd):
+        if sd:
+            raise ValueError(f"a GradAccumulator has no state between windows, got keys {sorted(sd)[:4]}")
+        self._clear()
+
     def step(self, scaler=None, max_norm=None):
         """The optimizer step of the window: `optimizer.step_scaled` on the accumulators of every tensor some rank saw (a tensor
         nobody saw is left out and so left alone -- no weight decay, no decay of its moments), after the one collective of the
@@ -648,3 +727,204 @@ class GradAccumulator:
             return self.optimizer.step_scaled({k: self.views[k] for k in present}, scaler=scaler, max_norm=max_norm)
         finally:
             self._clear()
+
+
+# ======================================================================================================================
+# The loop (main.py of the reference: Lightning's Trainer + ModelCheckpoint, `scripts/train.sh`)
+# ======================================================================================================================
+def scaled_lr(base_lr, accumulate=1, nodes=1, gpus=1, batch_size=1):
+    """The reference's `--scale_lr` arithmetic (main.py:690-694): accumulate * nodes * gpus * batch_size * base_lr."""
+    return accumulate * nodes * gpus * batch_size * base_lr
+
+
+def epoch_order(n, seed, epoch):
+    """The order in which epoch `epoch` visits a dataset of n items: a permutation that depends on (seed, epoch) only."""
+    return torch.randperm(n, generator=torch.Generator().manual_seed(int(seed) + int(epoch))).tolist()
+
+
+class EpochSampler:
+    """A batch sampler for one (seed, epoch): `epoch_order` cut into batches of `batch_size`, beginning at batch `start_batch`
+    -- the indices in front of it are dropped here, their items are never built.  `loader_seed` is what `device_loader` seeds
+    its DataLoader's own generator with (the base seed of worker processes): (seed, epoch) again, nothing of the global state."""
+
+    def __init__(self, n, batch_size, seed, epoch, start_batch=0, drop_last=True):
+        self.loader_seed = int(seed) + int(epoch)
+        order = epoch_order(n, seed, epoch)
+        if drop_last:
+            order = order[:len(order) // batch_size * batch_size]
+        order = order[start_batch * batch_size:]
+        self.batches = [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
+
+    def __iter__(self):
+        return iter(self.batches)
+
+    def __len__(self):
+        return len(self.batches)
+
+
+def epoch_loader(dataset, batch_size, seed, num_workers=0, drop_last=True, device="cuda"):
+    """`train_batches` for `Trainer.fit` over a `NuScenesDataset`: (epoch, start_batch) -> its `device_loader` under an
+    `EpochSampler`.  The order depends on (seed, epoch) only and a resumed epoch begins at `start_batch`."""
+    def train_batches(epoch, start_batch=0):
+        sampler = EpochSampler(len(dataset), batch_size, seed, epoch, start_batch, drop_last)
+        return dataset.device_loader(batch_size, num_workers=num_workers, device=device, sampler=sampler)
+    return train_batches
+
+
+class Trainer:
+    """The loop the reference runs under Lightning (main.py; `scripts/train.sh`: `--save_top_k`, `--resume`), for ONE model on the
+    engine: `training_step(batch, scaler=s, allreduce=k == 1)`, `acc.add` / `acc.step` (or `opt.step_scaled` directly),
+    `model.on_train_batch_end()`, `scheduler.step()`; at the end of every epoch `validation_step` over `val_batches`, every key
+    averaged, `epoch=NNNNNN.ckpt` saved and the `save_top_k` best by `model.monitor` (lower is better; -1 keeps all; without a
+    monitored value: the most recent) kept next to `last.ckpt`, which is always there; `every_n_steps` adds `last.ckpt` saves
+    inside an epoch.  Only files this trainer wrote are pruned; an epoch outside the top k is written once, as `last.ckpt`.  The optimizer, the schedule and the rate come from
+    `model.configure_optimizers()` / `model.learning_rate`.
+
+    train_batches(epoch, start_batch) -> an iterable of batch dicts whose order depends on (seed, epoch) only and which begins
+    at batch `start_batch` (`epoch_loader`); val_batches() -> an iterable of batch dicts, or None.  With
+    accumulate_grad_batches = k > 1 an optimizer step takes k consecutive batches; batches at an epoch's end that do not fill a
+    window are not used.  A checkpoint's (`epoch`, `batch_in_epoch`) is the position the run continues at: `resume=path`
+    loads through `checkpoint.Checkpointer.load` and continues there.  `max_steps` ends `fit` after that many optimizer steps
+    (nothing is saved at that point).
+
+    `model.loss_dict` stays on the device: the 0-d tensors of `log_every` steps are read back together, once, into one row of
+    `history` ({"step": the last of them, key: the mean over them}); what is left at the end of `fit` makes a last, shorter row.
+    More than one process: every rank loads, rank 0 alone writes, a barrier follows `wait()` (not run on more than one GPU)."""
+
+    def __init__(self, model, max_epochs, accumulate_grad_batches=1, max_norm=None, scaler=None, ckpt_dir=None, every_n_steps=None,
+                 save_top_k=3, seed=0, log_every=50, max_steps=None):
+        self.model, self.max_epochs, self.accumulate = model, int(max_epochs), int(accumulate_grad_batches)
+        self.max_norm, self.scaler, self.ckpt_dir, self.every_n_steps = max_norm, scaler, ckpt_dir, every_n_steps
+        self.save_top_k, self.seed, self.log_every, self.max_steps = int(save_top_k), int(seed), int(log_every), max_steps
+        self.monitor = getattr(model, "monitor", None)
+        self.history, self.val_history = [], []
+        self.global_step = 0
+        self.best = {}                                # {file name: monitored value (None without one), epoch} of the epoch files kept
+        self._pending = []
+
+    # -- logging
+    def _flush_log(self):
+        if not self._pending:
+            return
+        keys = sorted(self._pending[0][1])
+        vals = torch.stack([torch.stack([d[k].detach().float().reshape(()) for k in keys]) for _, d in self._pending]).cpu()
+        row = {"step": self._pending[-1][0]}
+        row.update({k: float(vals[:, j].double().mean()) for j, k in enumerate(keys)})
+        self.history.append(row)
+        self._pending = []
+
+    # -- checkpoints
+    def _save(self, name, epoch, batch_in_epoch):
+        import os
+        from . import dist as mdist
+        path = os.path.join(self.ckpt_dir, name)
+        if mdist.world()[0] == 0:
+            self.checkpointer.save(path, self.global_step, epoch, batch_in_epoch, monitor={"name": self.monitor, "best": dict(self.best)})
+        return path
+
+    def _wait(self):
+        from . import dist as mdist
+        self.checkpointer.wait()
+        if mdist.world()[1] > 1:
+            import torch.distributed as tdist
+            tdist.barrier()
+
+    def _end_of_epoch(self, epoch, val_batches):
+        import os
+        import shutil
+        from . import dist as mdist
+        metrics = {}
+        if val_batches is not None:
+            self.model.eval()
+            sums, count = {}, 0
+            for batch in val_batches():
+                out = self.model.validation_step(batch, count)
+                for k, v in out.items():
+                    sums[k] = v.detach().double() if k not in sums else sums[k] + v.detach().double()
+                count += 1
+            if count:
+                keys = sorted(sums)
+                vals = (torch.stack([sums[k].reshape(()) for k in keys]) / count).cpu()
+                metrics = {k: float(v) for k, v in zip(keys, vals)}
+            self.model.train()
+        self.val_history.append({"epoch": epoch, **metrics})
+        if self.ckpt_dir is None:
+            return
+        name = f"epoch={epoch:06d}.ckpt"
+        value = metrics.get(self.monitor)
+        self.best[name] = {"value": value, "epoch": epoch}
+        drop = []
+        if self.save_top_k >= 0:
+            rank_of = lambda kv: (kv[1]["value"] is None, kv[1]["value"] if kv[1]["value"] is not None else 0.0, -kv[1]["epoch"])
+            ranked = sorted(self.best.items(), key=rank_of)
+            drop = [k for k, _ in ranked[self.save_top_k:]]
+            for k in drop:
+                del self.best[k]
+        kept = name not in drop                        # (an epoch outside the top k is written once, as `last.ckpt`)
+        path = self._save(name if kept else "last.ckpt", epoch + 1, 0)
+        self._wait()
+        if mdist.world()[0] == 0:
+            if kept:
+                last = os.path.join(self.ckpt_dir, "last.ckpt")
+                shutil.copyfile(path, last + ".tmp")
+                os.replace(last + ".tmp", last)
+            for k in drop:
+                if os.path.exists(os.path.join(self.ckpt_dir, k)):
+                    os.remove(os.path.join(self.ckpt_dir, k))
+
+    def fit(self, train_batches, val_batches=None, resume=None):
+        import os
+        import random
+        import numpy as np
+        from . import checkpoint
+        model, k = self.model, self.accumulate
+        if not hasattr(model, "learning_rate"):
+            raise AttributeError("set model.learning_rate first (`scaled_lr` is the reference's --scale_lr arithmetic)")
+        made = model.configure_optimizers()
+        self.optimizer, self.scheduler = (made[0][0], made[1][0]["scheduler"]) if isinstance(made, tuple) else (made, None)
+        self.accumulator = GradAccumulator(self.optimizer, k) if k > 1 else None
+        self.checkpointer = checkpoint.Checkpointer(model, self.optimizer, self.scheduler, self.scaler, self.accumulator)
+        if self.ckpt_dir is not None:
+            os.makedirs(self.ckpt_dir, exist_ok=True)
+        epoch0 = batch0 = 0
+        if resume is not None:
+            at = self.checkpointer.load(resume)
+            self.global_step, epoch0, batch0 = at["global_step"], at["epoch"], at["batch_in_epoch"]
+            self.best = dict((at.get("monitor") or {}).get("best") or {})
+        else:
+            random.seed(self.seed)
+            np.random.seed(self.seed)
+            torch.manual_seed(self.seed)
+        model.train()
+        done = lambda: self.max_steps is not None and self.global_step >= self.max_steps
+        for epoch in range(epoch0, self.max_epochs):
+            start = batch0 if epoch == epoch0 else 0
+            for i, batch in enumerate(train_batches(epoch, start), start):
+                if done():
+                    break
+                model.training_step(batch, i, scaler=self.scaler, allreduce=k == 1)
+                self._pending.append((self.global_step + 1, dict(model.loss_dict)))
+                if self.accumulator is not None:
+                    self.accumulator.add(model.adapter_grads, scale=model.adapter_grads_scale)
+                    if (i + 1) % k:
+                        self._pending.pop()            # (a row of the log is an optimizer step: the window's last micro-batch)
+                        continue
+                    self.accumulator.step(scaler=self.scaler, max_norm=self.max_norm)
+                else:
+                    self.optimizer.step_scaled(model.adapter_grads, scaler=self.scaler, max_norm=self.max_norm)
+                model.on_train_batch_end()
+                if self.scheduler is not None:
+                    self.scheduler.step()
+                self.global_step += 1
+                if len(self._pending) >= self.log_every:
+                    self._flush_log()
+                if self.every_n_steps and self.ckpt_dir is not None and self.global_step % self.every_n_steps == 0:
+                    self._save("last.ckpt", epoch, i + 1)
+            if done():
+                break
+            if self.accumulator is not None:
+                self.accumulator._clear()              # (batches that did not fill a window)
+            self._end_of_epoch(epoch, val_batches)
+        self._flush_log()
+        self._wait()
+        return self
