@@ -54,7 +54,8 @@ extern "C" {
  *      the gradient accumulation over the same pair tables, mobi_accum_multi (no new struct); likewise the fused loss /
  *      entering-gradient launch mobi_loss_grad + mobi_loss_grad_blocks_per_sample (mobi_loss_grad_params 27); likewise the
  *      training splits' data side, mobi_ref_augment (mobi_ref_augment_params 28) and mobi_drop_context (no struct); likewise the checkpoint
- *      snapshot over the pair tables, mobi_snapshot_multi (mobi_snapshot_record 29) */
+ *      snapshot over the pair tables, mobi_snapshot_multi (mobi_snapshot_record 29); likewise the image logger's picture launch,
+ *      mobi_image_grid (mobi_image_grid_source 30) */
 #define MOBI_ABI_VERSION 6
 
 enum { MOBI_OK = 0, MOBI_ERR_ARG = -1, MOBI_ERR_UNSUPPORTED = -2, MOBI_ERR_LAUNCH = -3, MOBI_ERR_ALIGN = -4 };
@@ -866,6 +867,29 @@ int mobi_ref_augment(const mobi_ref_augment_params* p, void* stream);
  * gt / inpaint f32 [batch][channels][hw]; mask f32 [batch][1][hw]; flag i32 [batch]. */
 int mobi_drop_context(float* gt, float* inpaint, const float* mask, const int32_t* flag, int32_t batch, int32_t channels,
                       int64_t hw, void* stream);
+
+/* The image logger's per-key chore (main.py:353-370 of the reference: make_grid(nrow), (g + 1) / 2, two transposes, * 255,
+ * astype(uint8), after a .cpu() per key) for EVERY key of a log dict in one launch: source s, a dense NCHW tensor, becomes a
+ * finished HWC uint8 picture at out + out_offset of s.  torchvision's make_grid restated from its source (parity unpinned):
+ *   n = min(N, max_images) images; C = 1 is written to all three channels; n == 1: the picture is the image, no padding;
+ *   otherwise xmaps = min(nrow, n), ymaps = ceil(n / xmaps), the canvas is ymaps (H + padding) + padding rows by
+ *   xmaps (W + padding) + padding columns of the SOURCE value 0 and image k sits at cell (k / xmaps, k % xmaps), offset by
+ *   padding; the canvas is converted like the images, as in the reference, where the rescale follows make_grid: its bytes are 127
+ *   in a rescaled fp32 picture and 0 otherwise.
+ * elem_bytes 1 (uint8): bytes pass through.  elem_bytes 4 (fp32, finite): x -> clamp(x, -1, 1) where `clamp`, (x + 1.0f) / 2.0f
+ * where `rescale`, * 255.0f (each operation rounded to fp32, no contraction), truncated towards zero, low 8 bits: numpy's
+ * ((x.clip(-1, 1) + 1) / 2 * 255).astype(np.uint8) in float32.  elem_bytes 2: MOBI_ERR_UNSUPPORTED, as C outside {1, 3}.
+ * `sources` is a HOST array of 1 .. 16 entries (more: MOBI_ERR_UNSUPPORTED); it is checked here and travels to the device
+ * inside the launch's own argument block, which the kernel reads with scalar loads: no copy of the table, nothing to keep alive.
+ * Every picture must lie inside [out, out + out_bytes) at an offset that is a multiple of 4 (MOBI_ERR_ARG / MOBI_ERR_ALIGN); all
+ * checks come before the launch.  Addition to ABI 6 (struct id 30). */
+typedef struct mobi_image_grid_source {
+  const void* data;                                         /* DEVICE, [n][c][h][w] dense */
+  int32_t elem_bytes, n, c, h, w, reserved;
+  int64_t out_offset;                                       /* bytes; the picture is [hg][wg][3] uint8 */
+} mobi_image_grid_source;
+int mobi_image_grid(const mobi_image_grid_source* sources, int32_t n_sources, int32_t max_images, int32_t nrow,
+                    int32_t padding, int32_t clamp, int32_t rescale, uint8_t* out, int64_t out_bytes, void* stream);
 
 /* Camera paste-back of one sample (scripts/inference_test_bench.py:478-510):
  *   mobi_paste_patch    F.interpolate(patch, (crop_h, crop_w), bilinear, align_corners=False), (((x + 1) / 2) * 255)

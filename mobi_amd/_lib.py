@@ -212,13 +212,18 @@ class RefAugmentParams(C.Structure):
     _fields_ = [("src", vp), ("flags", vp), ("warp", vp), ("table", vp), ("out", vp), ("batch", i32), ("size", i32)]
 
 
+class ImageGridSource(C.Structure):
+    _fields_ = [("data", vp), ("elem_bytes", i32), ("n", i32), ("c", i32), ("h", i32), ("w", i32), ("reserved", i32),
+                ("out_offset", i64)]
+
+
 STRUCT_IDS = {0: IgemmParams, 1: GroupNormParams, 2: LayerNormParams, 3: AttentionParams, 4: CtxAttentionParams,
               5: SkinnyLinearParams, 6: ConvSmallCinParams, 7: ConvSmallCoutParams, 8: DdimStepParams, 9: TwoKeyAdapterParams,
               10: RangePasteParams, 11: LidarMetricsParams, 12: RangePrepareParams, 13: ImagePrepareParams,
               14: FfGegluParams, 15: RowChainParams, 16: ChainOp,
               17: LayerNormBwdParams, 18: AttentionBwdParams, 19: SplitSource, 20: DpmStepParams,
               21: LpipsDistanceParams, 22: ImageNormalizeParams, 23: MtTensor, 24: MtChunk, 25: GradStatsRecord,
-              26: MtPair, 27: LossGradParams, 28: RefAugmentParams, 29: SnapshotRecord}
+              26: MtPair, 27: LossGradParams, 28: RefAugmentParams, 29: SnapshotRecord, 30: ImageGridSource}
 
 # every symbol include/mobi_engine.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -296,6 +301,7 @@ SYMBOLS = {
     "mobi_image_prepare": (C.c_int, [C.POINTER(ImagePrepareParams), vp]),
     "mobi_ref_augment": (C.c_int, [C.POINTER(RefAugmentParams), vp]),
     "mobi_drop_context": (C.c_int, [vp, vp, vp, vp, i32, i32, i64, vp]),
+    "mobi_image_grid": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, vp, i64, vp]),
     "mobi_paste_patch": (C.c_int, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
     "mobi_gaussian_blur": (C.c_int, [vp, vp, vp, i32, i32, vp, i32, vp]),
     "mobi_blend_frame": (C.c_int, [vp, vp, vp, vp, i32, i32, vp]),

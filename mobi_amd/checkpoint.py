@@ -61,6 +61,20 @@ def _numpy_rng_set(st):
     np.random.set_state((st["name"], st["keys"].numpy().astype(np.uint32), st["pos"], st["has_gauss"], st["cached_gaussian"]))
 
 
+def rng_get(device=None):
+    """The four generator states a run depends on: Python `random`, numpy, torch CPU and (device given) the torch device generator."""
+    return {"python": random.getstate(), "numpy": _numpy_rng_get(), "torch": torch.get_rng_state(),
+            "device": None if device is None else torch.cuda.get_rng_state(device)}
+
+
+def rng_set(rng, device=None):
+    random.setstate(rng["python"])
+    _numpy_rng_set(rng["numpy"])
+    torch.set_rng_state(rng["torch"])
+    if device is not None and rng.get("device") is not None:
+        torch.cuda.set_rng_state(rng["device"], device)
+
+
 def _plain(x):
     """numpy scalars (a schedule's rate, a mean) as python numbers, through dicts, lists and tuples: see `_numpy_rng_get`."""
     if isinstance(x, dict):
@@ -243,8 +257,7 @@ class Checkpointer:
                 "scheduler": None if self.scheduler is None else _plain(copy.deepcopy(self.scheduler.state_dict())),
                 "mobi_amd": {"format": FORMAT, "scaler": None if self.scaler is None else _plain(copy.deepcopy(self.scaler.state_dict())),
                              "batch_in_epoch": int(batch_in_epoch), "monitor": _plain(copy.deepcopy(monitor)), "extra": _plain(copy.deepcopy(extra)),
-                             "rng": {"python": random.getstate(), "numpy": _numpy_rng_get(), "torch": torch.get_rng_state(),
-                                     "device": torch.cuda.get_rng_state(plan.staging.device)},
+                             "rng": rng_get(plan.staging.device),
                              "digests": digests}}
         head["optimizer"] = {"state": {i: {"step": e["step"].clone()} for i, e in head["optimizer"]["state"].items()},
                              "param_groups": _plain(copy.deepcopy(head["optimizer"]["param_groups"]))}
@@ -317,12 +330,8 @@ class Checkpointer:
             raise ValueError(f"{path}: checkpoint format {own['format']!r}, this reader knows {FORMAT}")
         if self.scaler is not None and own.get("scaler") is not None:
             self.scaler.load_state_dict(own["scaler"])
-        rng = own["rng"]
-        random.setstate(rng["python"])
-        _numpy_rng_set(rng["numpy"])
-        torch.set_rng_state(rng["torch"])
         named = [(k, t) for k, t in self._named_tensors()[0] if _digested(t)]
-        torch.cuda.set_rng_state(rng["device"], named[0][1].device)
+        rng_set(own["rng"], named[0][1].device)
         table = ops.MultiTensorTable([[t.reshape(-1) for _, t in named], [None] * len(named)])
         records = ops.read_snapshot_records(ops.snapshot_multi(table))
         digests, bad = own["digests"], []

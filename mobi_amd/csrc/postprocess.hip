@@ -483,6 +483,65 @@ __global__ __launch_bounds__(256) void drop_context_kernel(float* __restrict__ g
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The image logger's pictures (main.py:353-370: make_grid(nrow), (g + 1) / 2, two transposes, * 255, astype(uint8) per key):
+// every key of a log dict in one launch.  blockIdx.y = the source, so its table entry -- part of the launch's argument block --
+// is read with scalar loads; a thread writes one dword (4 bytes, 1 1/3 pixels) of the source's HWC picture, a plain gather.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int IG_MAX_SOURCES = 16;
+struct ig_entry {
+  const void* data;
+  int n, c, h, w;                                            // n: images used (<= max_images)
+  int hg, wg, xmaps, is_u8;
+  long long out_offset;
+};
+struct ig_table {
+  ig_entry e[IG_MAX_SOURCES];
+  int padding, clamp, rescale;
+};
+
+// byte gb of the picture [hg][wg][3] of source s.  The canvas between and around the cells holds the SOURCE value 0, as make_grid
+// fills it, and goes through the same conversion as the images: 127 in a rescaled fp32 picture (the reference's grey frame), else 0.
+__device__ __forceinline__ unsigned ig_byte(const ig_entry& s, int padding, int clamp, int rescale, int gb) {
+  const int pix = gb / 3, ch = gb - pix * 3;
+  int y = pix / s.wg, x = pix - y * s.wg, k = 0;
+  bool inside = true;
+  if (s.n > 1) {                                             // (one image: the picture is the image)
+    const int cell_h = s.h + padding, cell_w = s.w + padding;
+    y -= padding;
+    x -= padding;
+    const int cy = y / cell_h, cx = x / cell_w;
+    y -= cy * cell_h;
+    x -= cx * cell_w;
+    k = cy * s.xmaps + cx;
+    inside = y >= 0 && x >= 0 && y < s.h && x < s.w && k < s.n;    // not: the frame, the gaps, the cells past the last image
+  }
+  const long long i = (((long long)k * s.c + (s.c == 3 ? ch : 0)) * s.h + y) * s.w + x;
+  if (s.is_u8) return inside ? (unsigned)static_cast<const unsigned char*>(s.data)[i] : 0u;
+  float v = inside ? static_cast<const float*>(s.data)[i] : 0.0f;
+  if (clamp) v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);
+  if (rescale) v = (v + 1.0f) / 2.0f;
+  v = v * 255.0f;
+  return (unsigned)(int)v & 255u;                            // astype(uint8): towards zero, the low 8 bits
+}
+
+__global__ __launch_bounds__(256) void image_grid_kernel(const ig_table t, unsigned char* __restrict__ out) {
+  const ig_entry& s = t.e[blockIdx.y];
+  const int bytes = s.hg * s.wg * 3, words = (bytes + 3) >> 2;
+  unsigned char* dst = out + s.out_offset;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < words; i += gridDim.x * 256) {
+    const int b0 = i * 4;
+    if (b0 + 3 < bytes) {
+      unsigned word = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) word |= ig_byte(s, t.padding, t.clamp, t.rescale, b0 + j) << (8 * j);
+      reinterpret_cast<unsigned*>(dst)[i] = word;
+    } else {
+      for (int b = b0; b < bytes; ++b) dst[b] = (unsigned char)ig_byte(s, t.padding, t.clamp, t.rescale, b);
+    }
+  }
+}
+
 }  // namespace mobi
 
 using namespace mobi;
@@ -504,6 +563,37 @@ extern "C" int mobi_lidar_metrics(const mobi_lidar_metrics_params* p, void* stre
   if (p->max_width > p->w) return MOBI_ERR_ARG;                                      // a window wider than the view
   if ((long long)p->pool_h * p->max_width > 16384) return MOBI_ERR_UNSUPPORTED;      // the sort space in LDS
   hipLaunchKernelGGL(lidar_metrics_kernel, dim3(p->batch, 2), dim3(1024), 0, ST(stream), *p);
+  MOBI_CHECK_LAUNCH();
+  return MOBI_OK;
+}
+
+extern "C" int mobi_image_grid(const mobi_image_grid_source* sources, int32_t n_sources, int32_t max_images, int32_t nrow,
+                               int32_t padding, int32_t clamp, int32_t rescale, uint8_t* out, int64_t out_bytes, void* stream) {
+  if (!sources || !out || n_sources <= 0 || max_images <= 0 || nrow <= 0 || padding < 0 || out_bytes <= 0) return MOBI_ERR_ARG;
+  if (n_sources > IG_MAX_SOURCES) return MOBI_ERR_UNSUPPORTED;
+  ig_table t = {};
+  t.padding = padding, t.clamp = clamp != 0, t.rescale = rescale != 0;
+  long long most = 0;
+  for (int i = 0; i < n_sources; ++i) {
+    const mobi_image_grid_source& s = sources[i];
+    if (!s.data || s.n <= 0 || s.c <= 0 || s.h <= 0 || s.w <= 0) return MOBI_ERR_ARG;
+    if (s.elem_bytes == 2 || (s.c != 1 && s.c != 3)) return MOBI_ERR_UNSUPPORTED;
+    if (s.elem_bytes != 1 && s.elem_bytes != 4) return MOBI_ERR_ARG;
+    ig_entry& e = t.e[i];
+    e.data = s.data, e.n = s.n < max_images ? s.n : max_images, e.c = s.c, e.h = s.h, e.w = s.w, e.is_u8 = s.elem_bytes == 1;
+    e.xmaps = e.n < nrow ? e.n : nrow;
+    const long long ymaps = (e.n + e.xmaps - 1) / e.xmaps;
+    const long long hg = e.n == 1 ? s.h : ymaps * ((long long)s.h + padding) + padding;
+    const long long wg = e.n == 1 ? s.w : e.xmaps * ((long long)s.w + padding) + padding;
+    const long long bytes = hg * wg * 3;
+    if (hg > 0x7fffffffLL || wg > 0x7fffffffLL || bytes > 0x7ffffff0LL) return MOBI_ERR_UNSUPPORTED;   // (32-bit byte index)
+    if (s.out_offset < 0 || s.out_offset > out_bytes || bytes > out_bytes - s.out_offset) return MOBI_ERR_ARG;
+    if ((s.out_offset & 3) || (reinterpret_cast<uintptr_t>(out) & 3)) return MOBI_ERR_ALIGN;
+    if (s.elem_bytes == 4 && (reinterpret_cast<uintptr_t>(s.data) & 3)) return MOBI_ERR_ALIGN;
+    e.hg = (int)hg, e.wg = (int)wg, e.out_offset = s.out_offset;
+    most = bytes > most ? bytes : most;
+  }
+  hipLaunchKernelGGL(image_grid_kernel, dim3(egrid_pp((most + 3) / 4), n_sources), dim3(256), 0, ST(stream), t, out);
   MOBI_CHECK_LAUNCH();
   return MOBI_OK;
 }

@@ -278,6 +278,7 @@ extern "C" size_t mobi_struct_size(int id) {
     case 27: return sizeof(mobi_loss_grad_params);
     case 28: return sizeof(mobi_ref_augment_params);
     case 29: return sizeof(mobi_snapshot_record);
+    case 30: return sizeof(mobi_image_grid_source);
     default: return 0;
   }
 }

@@ -193,6 +193,8 @@ class DDPM(nn.Module):
 
 
 class LatentDiffusion(DDPM):
+    last_lidar_metrics = None                    # the lidar error scores of the last `log_images` call
+
     def __init__(self, cond_stage_config, first_stage_config=None, lidar_stage_config=None, num_timesteps_cond=None,
                  cond_stage_key="image", cond_stage_trainable=False, concat_mode=True, cond_stage_forward=None,
                  conditioning_key=None, scale_factor=1.0, lidar_scale_factor=1.0, scale_by_std=False,
@@ -576,6 +578,37 @@ class LatentDiffusion(DDPM):
                 z_lidar[..., c - self.image_size // 2: c + self.image_size // 2] = h_lidar
                 h_lidar = z_lidar
         return h_camera, h_lidar
+
+    @torch.no_grad()
+    def sample_log(self, cond, batch_size, ddim, ddim_steps, **kwargs):
+        """ddpm.py:1405-1417: DDIM through ONE sampler per model (`self._log_sampler`), so its captured step graph is reused
+        between calls that see unchanged weights; every run re-reads the weights fingerprint, so weights the optimizer (or an
+        EMA swap) has moved since make a new graph.  `ddim=False` is the reference's ancestral `sample()`, which calls
+        `apply_model` on the 4-channel latent alone: it cannot run a 9-channel inpainting UNet there either, and is not built."""
+        if not ddim:
+            raise NotImplementedError("sample_log(ddim=False): the reference's ancestral sample() feeds apply_model the 4-channel "
+                                      "latent and cannot run MObI's 9-channel inpainting UNet either; pass ddim_steps")
+        from .ddim import DDIMSampler
+        sampler = self.__dict__.get("_log_sampler")
+        if sampler is None:
+            sampler = self.__dict__["_log_sampler"] = DDIMSampler(self)      # (not a sub-module: kept out of nn.Module's tables)
+        shape = (self.channels, self.image_size, self.image_size)
+        return sampler.sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)
+
+    @torch.no_grad()
+    def log_images(self, batch, log_metrics=True, ddim_steps=50, ddim_eta=1., split="train", **kwargs):
+        """ddpm.py:1451-1468: encode the batch, sample it again under the EMA weights (DDIM, `ddim_eta`), decode both modalities,
+        and hand everything to `log_data` -> the log dict of pictures.  There is no Lightning `log_dict` here: the lidar error
+        scores of this call are left in `self.last_lidar_metrics` (None for a camera-only model) when `log_metrics`."""
+        data = self.get_input(batch, self.first_stage_key, force_c_encode=True, return_vae_rec=True)
+        with self.ema_scope("Plotting"):
+            samples, _ = self.sample_log(cond=data["cond"], batch_size=data["z"].shape[0], ddim=ddim_steps is not None,
+                                         ddim_steps=ddim_steps, eta=ddim_eta, rest=data["z"][:, 4:, :, :])
+            h_camera, h_lidar = self.decode_sample(samples, data.get("z_lidar"))
+        log, lidar_metrics = self.log_data(batch, data, h_camera, h_lidar, log_metrics=log_metrics, split=split)
+        if log_metrics:
+            self.last_lidar_metrics = lidar_metrics
+        return log
 
     @torch.no_grad()
     def log_data(self, batch, data, h_camera, h_lidar, log_metrics=True, return_sample=False, split="train"):

@@ -1649,6 +1649,50 @@ def lidar_metrics(pred, gt, inst_mask, box_mask, width_crop, pool_h=32):
     return out
 
 
+def image_grid_shape(n, h, w, max_images, nrow=4, padding=2):
+    """(Hg, Wg) of the picture `image_grid` makes of [n, C, h, w]: torchvision's make_grid geometry (include/mobi_engine.h)."""
+    n = min(int(n), int(max_images))
+    if n == 1:
+        return h, w
+    xmaps = min(int(nrow), n)
+    ymaps = -(-n // xmaps)
+    return ymaps * (h + padding) + padding, xmaps * (w + padding) + padding
+
+
+def image_grid(tensors, max_images, nrow=4, padding=2, *, clamp=True, rescale=True):
+    """{key: NCHW tensor on the device, fp32 in [-1, 1] or uint8, C = 1 | 3} -> {key: numpy uint8 [Hg, Wg, 3]}: what the
+    reference's image logger does per key with make_grid, a rescale, two transposes and astype after a .cpu() (main.py:353-370),
+    as ONE launch into one buffer and ONE copy to pinned host memory (include/mobi_engine.h, mobi_image_grid).  The grid's frame
+    is make_grid's 0 converted like the images: 127 around a rescaled fp32 picture, 0 otherwise.  At most 16 keys;
+    a 16-bit tensor is refused (no kernel for it: an error, not a conversion)."""
+    lib = _lib.load()
+    keys = list(tensors)
+    if not keys:
+        return {}
+    srcs = (_lib.ImageGridSource * len(keys))()
+    held, shapes, offset = [], [], 0
+    for s, key in zip(srcs, keys):
+        t = tensors[key]
+        assert isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 4, key
+        t = t.detach().contiguous()
+        held.append(t)
+        n, c, h, w = t.shape
+        s.data, s.elem_bytes, s.n, s.c, s.h, s.w, s.out_offset = _ptr(t), t.element_size(), n, c, h, w, offset
+        if t.dtype not in (torch.float32, torch.uint8, torch.float16, torch.bfloat16):
+            raise TypeError(f"image_grid: {key} is {t.dtype}; fp32 or uint8")
+        hg, wg = image_grid_shape(n, h, w, max_images, nrow, padding)
+        shapes.append((offset, hg, wg))
+        offset += (hg * wg * 3 + 3) // 4 * 4
+    out = torch.empty(offset, device=held[0].device, dtype=torch.uint8)
+    _lib.check(lib.mobi_image_grid(srcs, len(keys), int(max_images), int(nrow), int(padding), int(bool(clamp)), int(bool(rescale)),
+                                   _ptr(out), offset, _stream()), "mobi_image_grid")
+    host = torch.empty(offset, dtype=torch.uint8, pin_memory=True)
+    host.copy_(out, non_blocking=True)
+    torch.cuda.current_stream(out.device).synchronize()
+    flat = host.numpy()
+    return {key: flat[o:o + hg * wg * 3].reshape(hg, wg, 3) for key, (o, hg, wg) in zip(keys, shapes)}
+
+
 def paste_patch(patch, frame, top, left, crop_h, crop_w):
     """patch: fp32 [3, hs, ws] RGB in [-1, 1]; frame: uint8 [H, W, 3] BGR (written in place)."""
     lib = _lib.load()

@@ -771,6 +771,120 @@ def epoch_loader(dataset, batch_size, seed, num_workers=0, drop_last=True, devic
     return train_batches
 
 
+def _clone_tensors(x):
+    if isinstance(x, dict):
+        return {k: _clone_tensors(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return type(x)(_clone_tensors(v) for v in x)
+    return x.clone() if isinstance(x, torch.Tensor) else x
+
+
+class ImageLogger:
+    """The reference's `ImageLogger` callback (main.py:319-422; always installed there with batch_frequency=400, max_images=8,
+    clamp=False, log_on_batch_idx=True, log_first_step=True, main.py:604-613) for `Trainer`: every `batch_frequency` batches, and
+    on validation batches, `model.log_images(batch, split=split, **log_images_kwargs)` samples the batch again (DDIM, under the EMA
+    weights) and the tensor entries of its log dict become pictures under
+    `save_dir/images/<split>/<key>_gs-<global_step:06>_e-<epoch:06>_b-<batch_idx:06>.png` (`log_local`'s naming) -- all keys
+    through ONE `ops.image_grid` launch and one read-back, with `max_images`, `clamp` and `rescale` honoured by that launch
+    (`rescale=False`: an fp32 entry is taken as [0, 1]; uint8 entries, `log_data`'s camera collages, pass through, where the
+    reference's rescale would destroy them).  `log_img` returns {"step", "epoch", "batch_idx", "split",
+    **model.last_lidar_metrics} in Python floats: the lidar error scores of the SAMPLED objects.
+
+    A logging call does not move the run: the four generator states `checkpoint.Checkpointer` saves (Python, numpy, torch CPU,
+    torch device) are captured before the call, all four are seeded from (seed, global_step, split == "val", batch_idx) -- the VAE
+    posteriors `get_input` samples and the noise DDIM draws at every step with eta = 1 come from that stream -- and put back
+    after it, also when it raises; so does the model's train / eval mode.  The model sees a copy of the batch (`get_input` edits
+    `ref_bbox` in place).  As in the reference the hook runs AFTER the training step has made that edit once already.
+    More than one process: every rank runs the call (no collective inside it, the ranks stay in step), rank 0 alone writes files
+    (not run on more than one GPU)."""
+
+    def __init__(self, save_dir, batch_frequency=400, max_images=8, clamp=True, increase_log_steps=True, rescale=True,
+                 disabled=False, log_on_batch_idx=False, log_first_step=False, log_images_kwargs=None, seed=0):
+        self.save_dir, self.batch_freq, self.max_images = save_dir, int(batch_frequency), int(max_images)
+        self.clamp, self.rescale, self.disabled = clamp, rescale, disabled
+        self.log_steps = []                       # (the reference's doubling steps are commented out there, main.py:330)
+        if not increase_log_steps:
+            self.log_steps = [self.batch_freq]
+        self.log_on_batch_idx, self.log_first_step = log_on_batch_idx, log_first_step
+        self.log_images_kwargs = log_images_kwargs if log_images_kwargs else {}
+        self.seed = int(seed)
+        self.last_images = None                   # {key: uint8 [Hg, Wg, 3]} of the last call
+
+    def check_frequency(self, check_idx):
+        """main.py:406-414 as it stands."""
+        if (check_idx % self.batch_freq == 0 or check_idx in self.log_steps) and (check_idx > 0 or self.log_first_step):
+            if self.log_steps:
+                self.log_steps.pop(0)
+            return True
+        return False
+
+    def _seed(self, global_step, split, batch_idx, device):
+        import random
+        import numpy as np
+        words = np.random.SeedSequence([self.seed, int(global_step), int(split == "val"), int(batch_idx)]).generate_state(4)
+        random.seed(int(words[0]))
+        np.random.seed(int(words[1]))
+        torch.default_generator.manual_seed(int(words[2]))
+        if device is not None:
+            index = device.index if device.index is not None else torch.cuda.current_device()
+            torch.cuda.default_generators[index].manual_seed(int(words[3]))
+
+    def pictures(self, images):
+        """The tensor entries of a log dict -> {key: uint8 [Hg, Wg, 3]}: one launch per 16 keys."""
+        keys = [k for k, v in images.items() if isinstance(v, torch.Tensor) and v.dim() == 4]
+        out = {}
+        for i in range(0, len(keys), 16):
+            out.update(ops.image_grid({k: images[k] for k in keys[i:i + 16]}, self.max_images, nrow=4, padding=2,
+                                      clamp=self.clamp, rescale=self.rescale))
+        return out
+
+    def log_local(self, split, pictures, global_step, current_epoch, batch_idx):
+        import os
+        from PIL import Image
+        root = os.path.join(self.save_dir, "images", split)
+        for k, grid in pictures.items():
+            path = os.path.join(root, "{}_gs-{:06}_e-{:06}_b-{:06}.png".format(k, global_step, current_epoch, batch_idx))
+            os.makedirs(os.path.split(path)[0], exist_ok=True)             # (a `/` in a key is a directory, as in the reference)
+            Image.fromarray(grid).save(path)
+
+    def log_img(self, trainer, model, batch, batch_idx, split="train"):
+        from . import checkpoint
+        from . import dist as mdist
+        global_step, epoch = int(trainer.global_step), int(getattr(trainer, "current_epoch", 0))
+        check_idx = batch_idx if self.log_on_batch_idx else global_step
+        if not (self.check_frequency(check_idx) and callable(getattr(model, "log_images", None)) and self.max_images > 0):
+            return None
+        if getattr(trainer, "checkpointer", None) is not None:
+            trainer.checkpointer.wait()           # (a step graph may be captured below: not while the writer thread copies)
+        device = getattr(model, "device", None)
+        device = device if isinstance(device, torch.device) and device.type == "cuda" else None
+        was_training, rng = model.training, checkpoint.rng_get(device)
+        try:
+            self._seed(global_step, split, batch_idx, device)
+            model.eval()
+            with torch.no_grad():
+                images = model.log_images(_clone_tensors(batch), split=split, **self.log_images_kwargs)
+                self.last_images = self.pictures(images)
+        finally:
+            model.train(was_training)
+            checkpoint.rng_set(rng, device)
+        if mdist.world()[0] == 0:
+            self.log_local(split, self.last_images, global_step, epoch, batch_idx)
+        metrics = getattr(model, "last_lidar_metrics", None) or {}
+        return {"step": global_step, "epoch": epoch, "batch_idx": int(batch_idx), "split": split,
+                **{k: float(v) for k, v in metrics.items()}}
+
+    def on_train_batch_end(self, trainer, model, batch, batch_idx):
+        if not self.disabled and (trainer.global_step > 0 or self.log_first_step):
+            return self.log_img(trainer, model, batch, batch_idx, split="train")
+        return None
+
+    def on_validation_batch_end(self, trainer, model, batch, batch_idx):
+        if not self.disabled and (trainer.global_step > 0 or self.log_first_step):
+            return self.log_img(trainer, model, batch, batch_idx, split="val")
+        return None
+
+
 class Trainer:
     """The loop the reference runs under Lightning (main.py; `scripts/train.sh`: `--save_top_k`, `--resume`), for ONE model on the
     engine: `training_step(batch, scaler=s, allreduce=k == 1)`, `acc.add` / `acc.step` (or `opt.step_scaled` directly),
@@ -789,10 +903,16 @@ class Trainer:
 
     `model.loss_dict` stays on the device: the 0-d tensors of `log_every` steps are read back together, once, into one row of
     `history` ({"step": the last of them, key: the mean over them}); what is left at the end of `fit` makes a last, shorter row.
-    More than one process: every rank loads, rank 0 alone writes, a barrier follows `wait()` (not run on more than one GPU)."""
+    More than one process: every rank loads, rank 0 alone writes, a barrier follows `wait()` (not run on more than one GPU).
+
+    `image_logger` (an `ImageLogger`) is called after every optimizer step (`on_train_batch_end(self, model, batch, i)`, once
+    `global_step` has moved; in an accumulation window after the window's step only) and after every `validation_step`; the rows it
+    returns go to `image_history`.  `log_dir`: every row of `history`, `val_history` and `image_history` is also appended to
+    `log_dir/metrics.jsonl` as it is made.  `current_epoch` is the epoch `fit` is in.  With neither, nothing changes."""
 
     def __init__(self, model, max_epochs, accumulate_grad_batches=1, max_norm=None, scaler=None, ckpt_dir=None, every_n_steps=None,
-                 save_top_k=3, seed=0, log_every=50, max_steps=None):
+                 save_top_k=3, seed=0, log_every=50, max_steps=None, image_logger=None, log_dir=None):
+        self.image_logger, self.log_dir, self.image_history, self.current_epoch = image_logger, log_dir, [], 0
         self.model, self.max_epochs, self.accumulate = model, int(max_epochs), int(accumulate_grad_batches)
         self.max_norm, self.scaler, self.ckpt_dir, self.every_n_steps = max_norm, scaler, ckpt_dir, every_n_steps
         self.save_top_k, self.seed, self.log_every, self.max_steps = int(save_top_k), int(seed), int(log_every), max_steps
@@ -803,6 +923,28 @@ class Trainer:
         self._pending = []
 
     # -- logging
+    def _emit(self, kind, row):
+        """One JSON line per row of `history` / `val_history` / `image_history` ("kind": train | val | images), appended to
+        `log_dir/metrics.jsonl` when the row is made: a resumed run continues the file.  Rank 0 alone writes."""
+        if self.log_dir is None:
+            return
+        import json
+        import os
+        from . import dist as mdist
+        if mdist.world()[0] != 0:
+            return
+        os.makedirs(self.log_dir, exist_ok=True)
+        with open(os.path.join(self.log_dir, "metrics.jsonl"), "a") as f:
+            f.write(json.dumps({"kind": kind, **row}) + "\n")
+
+    def _log_images(self, hook, batch, batch_idx):
+        if self.image_logger is None:
+            return
+        row = getattr(self.image_logger, hook)(self, self.model, batch, batch_idx)
+        if row is not None:
+            self.image_history.append(row)
+            self._emit("images", row)
+
     def _flush_log(self):
         if not self._pending:
             return
@@ -811,6 +953,7 @@ class Trainer:
         row = {"step": self._pending[-1][0]}
         row.update({k: float(vals[:, j].double().mean()) for j, k in enumerate(keys)})
         self.history.append(row)
+        self._emit("train", row)
         self._pending = []
 
     # -- checkpoints
@@ -839,6 +982,7 @@ class Trainer:
             sums, count = {}, 0
             for batch in val_batches():
                 out = self.model.validation_step(batch, count)
+                self._log_images("on_validation_batch_end", batch, count)
                 for k, v in out.items():
                     sums[k] = v.detach().double() if k not in sums else sums[k] + v.detach().double()
                 count += 1
@@ -848,6 +992,7 @@ class Trainer:
                 metrics = {k: float(v) for k, v in zip(keys, vals)}
             self.model.train()
         self.val_history.append({"epoch": epoch, **metrics})
+        self._emit("val", self.val_history[-1])
         if self.ckpt_dir is None:
             return
         name = f"epoch={epoch:06d}.ckpt"
@@ -898,6 +1043,7 @@ class Trainer:
         model.train()
         done = lambda: self.max_steps is not None and self.global_step >= self.max_steps
         for epoch in range(epoch0, self.max_epochs):
+            self.current_epoch = epoch
             start = batch0 if epoch == epoch0 else 0
             for i, batch in enumerate(train_batches(epoch, start), start):
                 if done():
@@ -916,6 +1062,7 @@ class Trainer:
                 if self.scheduler is not None:
                     self.scheduler.step()
                 self.global_step += 1
+                self._log_images("on_train_batch_end", batch, i)       # (in a window: after its optimizer step only)
                 if len(self._pending) >= self.log_every:
                     self._flush_log()
                 if self.every_n_steps and self.ckpt_dir is not None and self.global_step % self.every_n_steps == 0:
