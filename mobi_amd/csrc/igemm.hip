@@ -97,6 +97,39 @@ __device__ unsigned long long* g_phase = nullptr;
 #define MOBI_PHASE_ACC() ((void)0)
 #endif
 
+#if MOBI_STAMP == 5
+// igemm_ring64_kernel, per wave (tools/phase_ring64.py): shader cycles of a k-step in  counted wait | barrier | fragment reads |
+// request issue | LDS wait | MFMAs  (the overlapped loop deals its requests between the MFMAs: columns 3 and 4 are zero),
+// the number of steps, entry -> end; second row: entry -> first step, last step -> end (drain + epilogue).  [block][4 waves][2][8]
+#define MOBI_SP_ENTRY const unsigned long long sp_t0 = __builtin_amdgcn_s_memtime()
+#define MOBI_SP_DECL unsigned long long sp_t[7], sp_acc[6] = {0, 0, 0, 0, 0, 0}, sp_n = 0, sp_first = 0, sp_last = 0
+#define MOBI_SP(i) sp_t[i] = __builtin_amdgcn_s_memtime()
+#define MOBI_SP_ACC()                                                              \
+  do {                                                                             \
+    for (int i_ = 0; i_ < 6; ++i_) sp_acc[i_] += sp_t[i_ + 1] - sp_t[i_];          \
+    if (!sp_n) sp_first = sp_t[0];                                                 \
+    sp_last = sp_t[6];                                                             \
+    ++sp_n;                                                                        \
+  } while (0)
+#define MOBI_SP_WRITE()                                                                                                   \
+  do {                                                                                                                    \
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                                      \
+    const unsigned long long sp_end = __builtin_amdgcn_s_memtime();                                                       \
+    if (g_phase && lane == 0) {                                                                                           \
+      unsigned long long* d_ = g_phase + ((size_t)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) * 8 + wave * 2) * 8; \
+      for (int i_ = 0; i_ < 6; ++i_) d_[i_] = sp_acc[i_];                                                                 \
+      d_[6] = sp_n; d_[7] = sp_end - sp_t0;                                                                               \
+      d_[8] = sp_n ? sp_first - sp_t0 : 0; d_[9] = sp_n ? sp_end - sp_last : 0;                                           \
+    }                                                                                                                     \
+  } while (0)
+#else
+#define MOBI_SP_ENTRY ((void)0)
+#define MOBI_SP_DECL ((void)0)
+#define MOBI_SP(i) ((void)0)
+#define MOBI_SP_ACC() ((void)0)
+#define MOBI_SP_WRITE() ((void)0)
+#endif
+
 // 16 zero bytes in the code object: the source of every padded / out-of-range 16-byte piece of an operand tile
 // (a plain load from here instead of a load + select; the library allocates nothing).
 __device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
@@ -2422,8 +2455,23 @@ __global__ __launch_bounds__(NW * 64, 2) void igemm_ring_kernel(const IgemmArgs 
 // One raw s_barrier per k-step, three steps of prefetch, every wave issues R = 4 + NT requests per step (all-zero
 // pieces past its k range), counted waits.  Epilogues: the ring kernel's (registers / register slab stores for full tiles,
 // else LDS-staged through the drained ring).
+//
+// OVL (the default; MOBI_IGEMM_SM64_OVL=0 keeps the strictly sequential step for the A/B): the same ring, slots, requests and
+// counted waits, but (a) a step's 4 + NT requests are dealt out one behind every four MFMAs instead of as a burst in front of
+// them -- a request holds the wave's issue for 60-70 cycles (tools/phase_ring64.py: 590 cycles of issue + 730 of MFMAs per
+// step, one after the other; with one wave per SIMD nobody fills the holes), four MFMAs are 64 cycles of matrix pipe -- (b)
+// the fragment reads of ks = 1 land under the MFMAs of ks = 0 (hipcc's counted lgkmcnt instead of lgkmcnt(0)), and (c) the
+// kernel has ONE __shared__ object (arrival flag and row statistics behind the ring): beside a second one hipcc drains vmcnt
+// to 0 in front of the first fragment read of every step, which is what the sequential step still does.
+// RAW / WAR are the sequential step's: slot s % 4 is read behind the wait that retires the wave's own requests of step s and
+// the barrier behind every wave's such wait; the requests of step s + 3 go to slot (s - 1) % 4 behind that same barrier, which
+// every wave passes after its last read of the slot (its MFMAs of step s - 1 waited for them).  Same MFMAs, same order: the
+// sums are bit-identical.
+// Measured and NOT built: weights straight into registers (each wave its own B fragments by 16-byte buffer loads, LDS for
+// activations only).  A fragment load is 16 rows x 64 B, which the request path takes at half the rate of 128-byte rows, and
+// the two waves of a column range fetch the same rows: 2,000 cycles per step against 1,750 (profiles/sm64_wreg_stamps.txt).
 // =========================================================================================================
-template <typename T, int NT, bool TR, bool LNF = false>
+template <typename T, int NT, bool TR, bool LNF = false, bool OVL = false>
 __global__ __launch_bounds__(256, 1) void igemm_ring64_kernel(const IgemmArgs a) {
   typedef typename Vec8<T>::type frag_t;
   constexpr int NW = 4, MT = 4, BM = 128, SL = 4;
@@ -2435,12 +2483,17 @@ __global__ __launch_bounds__(256, 1) void igemm_ring64_kernel(const IgemmArgs a)
   constexpr int STAGE_BYTES = EpiGeom<32, TR, NT>::BYTES;
   constexpr int LDS_BYTES = RING > NW * STAGE_BYTES ? RING : NW * STAGE_BYTES;
   constexpr unsigned OOB = 0x80000000u;
-  __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
-  __shared__ int s_arrive;                                   // split-K finished inside the launch: the arrival order
-  __shared__ float s_rowstat[LNF ? BM * 2 : 2];              // LayerNorm folded into the launch: {mean, rstd} of the block's rows
+  // (OVL: one __shared__ object, the arrival flag and the row statistics behind the ring)
+  constexpr int TAIL_BYTES = OVL ? 16 + (LNF ? BM * 2 * 4 : 0) : 0;
+  __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES + TAIL_BYTES];
+  __shared__ int s_arrive_obj;                               // split-K finished inside the launch: the arrival order
+  __shared__ float s_rowstat_obj[LNF ? BM * 2 : 2];          // LayerNorm folded into the launch: {mean, rstd} of the block's rows
+  int* const s_arrive = OVL ? reinterpret_cast<int*>(lds + LDS_BYTES) : &s_arrive_obj;
+  float* const s_rowstat = OVL ? reinterpret_cast<float*>(lds + LDS_BYTES + 16) : s_rowstat_obj;
   static_assert(!(LNF && TR), "the LayerNorm fold has no transposed-output form");
   typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
+  MOBI_SP_ENTRY;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wave_s = __builtin_amdgcn_readfirstlane(wave);
   const int wm = wave & 1, wn = wave >> 1;
@@ -2492,11 +2545,16 @@ __global__ __launch_bounds__(256, 1) void igemm_ring64_kernel(const IgemmArgs a)
   for (int j = 0; j < APW; ++j) f_row[j] = OOB;
   int f_tap = -1, f_src = -1, f_ks = ks_begin;
 
-  auto issue_step = [&]() {
-    unsigned char* st = lds + (f_ks & (SL - 1)) * SLOT;
-    const bool live = f_ks < ks_end;
+  // the requests of one step: prep_step (slot, source rows, k offsets of step f_ks; then f_ks moves on), req_x(j) x APW and
+  // the step's weight requests (the overlapped loop deals all of them out one by one between its MFMAs)
+  unsigned char* p_st = lds;
+  bool p_live = false;
+  int p_src = 0, p_soff = 0, p_kb = 0;
+  auto prep_step = [&]() __attribute__((always_inline)) {
+    p_st = lds + (f_ks & (SL - 1)) * SLOT;
+    p_live = f_ks < ks_end;
     const int src = u_c >= a.c0 ? 1 : 0;
-    if (live && (u_tap != f_tap || src != f_src)) {
+    if (p_live && (u_tap != f_tap || src != f_src)) {
       f_tap = u_tap; f_src = src;
       const unsigned cs2 = (unsigned)(src ? a.c1 : a.c0) * 2u;
 #pragma unroll
@@ -2506,23 +2564,28 @@ __global__ __launch_bounds__(256, 1) void igemm_ring64_kernel(const IgemmArgs a)
         f_row[j] = ok ? (unsigned)(x_base[j] + (hi >> a.up) * a.win + (wi >> a.up)) * cs2 + chunk16 : OOB;
       }
     }
-    const int soff = (src ? u_c - a.c0 : u_c) * 2;
-#pragma unroll
-    for (int j = 0; j < APW; ++j) {
-      const unsigned vo = live ? f_row[j] : OOB;
-      if (src) __builtin_amdgcn_raw_ptr_buffer_load_lds(rx1, (lds_ptr_t)(st + 8 * (APW * wave_s + j) * 128), 16, vo, soff, 0, 0);
-      else     __builtin_amdgcn_raw_ptr_buffer_load_lds(rx0, (lds_ptr_t)(st + 8 * (APW * wave_s + j) * 128), 16, vo, soff, 0, 0);
-    }
-    const int kb = f_ks * 128;
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-      const unsigned vo = live ? w_off[i] : OOB;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(st + BM * 128 + 8 * (wave_s + NW * i) * 128), 16, vo, kb, 0, 0);
-    }
+    p_src = src;
+    p_soff = (src ? u_c - a.c0 : u_c) * 2;
+    p_kb = f_ks * 128;
     ++f_ks;
-    if (live) {
+    if (p_live) {
       u_c += 64;
       if (u_c >= a.C) { u_c = 0; ++u_tap; if (++u_kx == a.kw) { u_kx = 0; ++u_ky; } }
+    }
+  };
+  auto req_x = [&](int j) __attribute__((always_inline)) {
+    const unsigned vo = p_live ? f_row[j] : OOB;
+    if (p_src) __builtin_amdgcn_raw_ptr_buffer_load_lds(rx1, (lds_ptr_t)(p_st + 8 * (APW * wave_s + j) * 128), 16, vo, p_soff, 0, 0);
+    else       __builtin_amdgcn_raw_ptr_buffer_load_lds(rx0, (lds_ptr_t)(p_st + 8 * (APW * wave_s + j) * 128), 16, vo, p_soff, 0, 0);
+  };
+  auto issue_step = [&]() {
+    prep_step();
+#pragma unroll
+    for (int j = 0; j < APW; ++j) req_x(j);
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+      const unsigned vo = p_live ? w_off[i] : OOB;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(p_st + BM * 128 + 8 * (wave_s + NW * i) * 128), 16, vo, p_kb, 0, 0);
     }
   };
   // own requests of the two youngest steps may stay in flight: R = 4 + NT
@@ -2545,15 +2608,78 @@ __global__ __launch_bounds__(256, 1) void igemm_ring64_kernel(const IgemmArgs a)
   const unsigned char* xrd = lds + (wm * 64 + r16) * 128;
   const unsigned char* wrd = lds + BM * 128 + (wn * WAVE_N + r16) * 128;
 
+  MOBI_SP_DECL;
+  if constexpr (OVL) {
+    // one request of the step prep_step has just described: the four activation pieces, then the NT weight pieces
+    auto req = [&](int g) __attribute__((always_inline)) {
+      if (g < APW) { req_x(g); return; }
+      const int i = g - APW;
+      const unsigned vo = p_live ? w_off[i] : OOB;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(p_st + BM * 128 + 8 * (wave_s + NW * i) * 128), 16, vo, p_kb, 0, 0);
+    };
+    issue_step(); issue_step(); issue_step();
+    auto k_loop = [&](auto wnc) __attribute__((always_inline)) {
+      constexpr int WNC = decltype(wnc)::value;
+#pragma clang loop unroll(disable)
+      for (int s = ks_begin; s < ks_end; ++s) {
+        MOBI_SP(0);
+        wait_step();
+        MOBI_SP(1);
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        MOBI_SP(2);
+        const int so = (s & (SL - 1)) * SLOT;
+        frag_t xf[2][MT], wf[2][NT];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          const int sw = ((ks * 4 + g4) ^ (r16 & 7)) << 4;
+#pragma unroll
+          for (int mi = 0; mi < MT; ++mi) xf[ks][mi] = __builtin_bit_cast(frag_t, ld16(xrd + so + mi * 16 * 128 + sw));
+#pragma unroll
+          for (int ni = 0; ni < NT; ++ni) wf[ks][ni] = __builtin_bit_cast(frag_t, ld16(wrd + so + ni * 16 * 128 + sw));
+        }
+        prep_step();                                         // step s + 3
+        __builtin_amdgcn_sched_barrier(0);
+        MOBI_SP(3);
+#if MOBI_STAMP == 5
+        sp_t[4] = sp_t[5] = sp_t[3];
+#endif
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)                       // (the reads of ks = 1 land under the MFMAs of ks = 0: hipcc's counted lgkmcnt)
+#pragma unroll
+          for (int ni = 0; ni < NT; ++ni) {
+#pragma unroll
+            for (int mi = 0; mi < MT; ++mi) {
+              acc[ni][mi] = TR ? mfma16(xf[ks][mi], wf[ks][ni], acc[ni][mi]) : mfma16(wf[ks][ni], xf[ks][mi], acc[ni][mi]);
+              if constexpr (lnf) if (ni == 0 && mi < SPW) rowstat_acc(xf[ks][SPW * WNC + mi], ls_sum[mi], ls_sq[mi]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (ks * NT + ni < APW + NT) req(ks * NT + ni);  // one request of step s + 3 behind every four MFMAs
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        MOBI_SP(6);
+        MOBI_SP_ACC();
+      }
+    };
+    if constexpr (lnf) {
+      if ((wave_s >> 1) == 0) k_loop(std::integral_constant<int, 0>{}); else k_loop(std::integral_constant<int, 1>{});
+    } else {
+      k_loop(std::integral_constant<int, 0>{});
+    }
+  } else {
   issue_step(); issue_step(); issue_step();
   auto k_loop = [&](auto wnc) {                              // (compiled once per wave column: LayerNorm fold, see igemm_ring_kernel)
   constexpr int WNC = decltype(wnc)::value;
 #pragma clang loop unroll(disable)
   for (int s = ks_begin; s < ks_end; ++s) {
+    MOBI_SP(0);
     wait_step();
+    MOBI_SP(1);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
+    MOBI_SP(2);
     const int so = (s & (SL - 1)) * SLOT;
     frag_t xf[2][MT], wf[2][NT];
 #pragma unroll
@@ -2565,9 +2691,12 @@ __global__ __launch_bounds__(256, 1) void igemm_ring64_kernel(const IgemmArgs a)
       for (int ni = 0; ni < NT; ++ni) wf[ks][ni] = __builtin_bit_cast(frag_t, ld16(wrd + so + ni * 16 * 128 + sw));
     }
     __builtin_amdgcn_sched_barrier(0);
+    MOBI_SP(3);
     issue_step();                                            // step s + 3, behind the reads' latency
     __builtin_amdgcn_sched_barrier(0);
+    MOBI_SP(4);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    MOBI_SP(5);
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
@@ -2588,12 +2717,15 @@ __global__ __launch_bounds__(256, 1) void igemm_ring64_kernel(const IgemmArgs a)
       for (int i = 0; i < SPW; ++i) asm volatile("" : "+v"(ls_sum[i]), "+v"(ls_sq[i]));
     }
     __builtin_amdgcn_s_setprio(0);
+    MOBI_SP(6);
+    MOBI_SP_ACC();
   }
   };
   if constexpr (lnf) {
     if ((wave_s >> 1) == 0) k_loop(std::integral_constant<int, 0>{}); else k_loop(std::integral_constant<int, 1>{});
   } else {
     k_loop(std::integral_constant<int, 0>{});
+  }
   }
   if constexpr (lnf) ln_fold_acc<NT, MT, SPW>(a, acc, ls_sum, ls_sq, s_rowstat, lane, wm, wave_s >> 1, n0 + wn * WAVE_N, false);
   if constexpr (!TR) {
@@ -2609,7 +2741,7 @@ __global__ __launch_bounds__(256, 1) void igemm_ring64_kernel(const IgemmArgs a)
           for (int ni = 0; ni < NT; ++ni) slab_store16(a.sync_mode == 1, rowp + ni * 16, __builtin_bit_cast(u32x4, acc[ni][mi]));
         }
         if (a.sync) {                                          // split-K finished inside the launch by the tile's last block
-          splitk_arrive_and_finish<T, NW * 64>(a, tile_m * a.tiles_n + tile_n, m0, BM, n0, BN, &s_arrive);
+          splitk_arrive_and_finish<T, NW * 64>(a, tile_m * a.tiles_n + tile_n, m0, BM, n0, BN, s_arrive);
         }
       } else {
         DirectEpiRegs<NT> q;
@@ -2620,6 +2752,7 @@ __global__ __launch_bounds__(256, 1) void igemm_ring64_kernel(const IgemmArgs a)
         if (a.epilogue == MOBI_EPI_GEGLU) direct_epilogue<T, NT, true>(a, acc, q, lane, group, nw0, mw0);
         else direct_epilogue<T, NT, false>(a, acc, q, lane, group, nw0, mw0);
       }
+      MOBI_SP_WRITE();
       return;
     }
   }
@@ -2629,9 +2762,10 @@ __global__ __launch_bounds__(256, 1) void igemm_ring64_kernel(const IgemmArgs a)
   igemm_epilogue<T, NT, TR, 32, true>(a, stage, acc, lane, group, n0 + wn * WAVE_N, m0 + wm * 64);
   if constexpr (!TR) {
     if (a.split_ws && a.sync) {
-      splitk_arrive_and_finish<T, NW * 64>(a, tile_m * a.tiles_n + tile_n, m0, BM, n0, BN, &s_arrive);
+      splitk_arrive_and_finish<T, NW * 64>(a, tile_m * a.tiles_n + tile_n, m0, BM, n0, BN, s_arrive);
     }
   }
+  MOBI_SP_WRITE();
 }
 
 // split-K finish: sum the partial slabs, then the ordinary epilogue (bias, per-image vector, residual)
@@ -2794,14 +2928,16 @@ static int launch_igemm(const mobi_igemm_params* p, const IgemmArgs& a, int grou
 #endif
   else if (a.wm == 4) { if (nt5) MOBI_IGEMM_BY_TR(5, 4); else MOBI_IGEMM_BY_TR(4, 4); }
   else if (a.sm && a.sm64) {
-#define MOBI_SM64_LAUNCH(NT_, TR_) hipLaunchKernelGGL((igemm_ring64_kernel<T, NT_, TR_>), grid, dim3(256), 0, st, a)
-    if (a.ln_svec) {
-      if (nt5) hipLaunchKernelGGL((igemm_ring64_kernel<T, 5, false, true>), grid, dim3(256), 0, st, a);
-      else     hipLaunchKernelGGL((igemm_ring64_kernel<T, 4, false, true>), grid, dim3(256), 0, st, a);
-    }
-    else if (nt5) { if (tr) MOBI_SM64_LAUNCH(5, true); else MOBI_SM64_LAUNCH(5, false); }
-    else     { if (tr) MOBI_SM64_LAUNCH(4, true); else MOBI_SM64_LAUNCH(4, false); }
+    // requests dealt out between the MFMAs (MOBI_IGEMM_SM64_OVL=0: the sequential step, the A/B partner)
+#define MOBI_SM64_LAUNCH_W(NT_, TR_, LNF_, OVL_) \
+  hipLaunchKernelGGL((igemm_ring64_kernel<T, NT_, TR_, LNF_, OVL_>), grid, dim3(256), 0, st, a)
+#define MOBI_SM64_LAUNCH(NT_, TR_, LNF_) \
+  do { if (tuning().sm64_ovl != 0) MOBI_SM64_LAUNCH_W(NT_, TR_, LNF_, true); else MOBI_SM64_LAUNCH_W(NT_, TR_, LNF_, false); } while (0)
+    if (a.ln_svec) { if (nt5) MOBI_SM64_LAUNCH(5, false, true); else MOBI_SM64_LAUNCH(4, false, true); }
+    else if (nt5) { if (tr) MOBI_SM64_LAUNCH(5, true, false); else MOBI_SM64_LAUNCH(5, false, false); }
+    else     { if (tr) MOBI_SM64_LAUNCH(4, true, false); else MOBI_SM64_LAUNCH(4, false, false); }
 #undef MOBI_SM64_LAUNCH
+#undef MOBI_SM64_LAUNCH_W
   }
   else if (a.sm) {
 #define MOBI_SM_LAUNCH(NT_, TR_) hipLaunchKernelGGL((igemm_ring_kernel<T, NT_, TR_, 4, 4>), grid, dim3(256), 0, st, a)

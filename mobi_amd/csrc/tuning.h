@@ -20,6 +20,7 @@ struct Tuning {
   int w_tiled;          // MOBI_IGEMM_WTILED          0: ring kernels fetch weights as row segments even when request images are given (A/B)
   int n_major;          // MOBI_IGEMM_N_MAJOR         0: igemm work lists always walk the channel tiles of a pixel tile first (A/B); 1: never
   int sm64;             // MOBI_IGEMM_SM64            0: 128-pixel tiles always on the 32-deep-step ring kernel (A/B)
+  int sm64_ovl;         // MOBI_IGEMM_SM64_OVL        0: the 64-deep-step kernel issues a step's requests as a burst in front of its MFMAs (A/B)
   int split_target;     // MOBI_IGEMM_SPLIT_TARGET    blocks the split-K plan aims at (default 512; sweeps)
   int fused_split;      // MOBI_IGEMM_FUSED_SPLIT     0: split-K launches always finish in igemm_splitk_reduce_kernel, also with `sync` given (A/B)
   int split_longk;      // MOBI_IGEMM_SPLIT_LONGK     0: no extra doubling of the splits on one-round launches with >= 80 k-tiles per split (A/B)

@@ -30,6 +30,7 @@ void read_env() {
   g_tuning.sm_direct = env_int("MOBI_IGEMM_SM_DIRECT");
   g_tuning.w_tiled = env_int("MOBI_IGEMM_WTILED");
   g_tuning.sm64 = env_int("MOBI_IGEMM_SM64");
+  g_tuning.sm64_ovl = env_int("MOBI_IGEMM_SM64_OVL");
   g_tuning.n_major = env_int("MOBI_IGEMM_N_MAJOR");
   g_tuning.split_target = env_int("MOBI_IGEMM_SPLIT_TARGET");
   g_tuning.split_longk = env_int("MOBI_IGEMM_SPLIT_LONGK");
