@@ -55,7 +55,8 @@ extern "C" {
  *      entering-gradient launch mobi_loss_grad + mobi_loss_grad_blocks_per_sample (mobi_loss_grad_params 27); likewise the
  *      training splits' data side, mobi_ref_augment (mobi_ref_augment_params 28) and mobi_drop_context (no struct); likewise the checkpoint
  *      snapshot over the pair tables, mobi_snapshot_multi (mobi_snapshot_record 29); likewise the image logger's picture launch,
- *      mobi_image_grid (mobi_image_grid_source 30) */
+ *      mobi_image_grid (mobi_image_grid_source 30); likewise the test bench's camera pictures, mobi_camera_export
+ *      (mobi_camera_export_params 31) */
 #define MOBI_ABI_VERSION 6
 
 enum { MOBI_OK = 0, MOBI_ERR_ARG = -1, MOBI_ERR_UNSUPPORTED = -2, MOBI_ERR_LAUNCH = -3, MOBI_ERR_ALIGN = -4 };
@@ -68,7 +69,8 @@ const char* mobi_error_string(int code);
  * 3 attention, 4 ctx_attention, 5 skinny_linear, 6 conv_small_cin, 7 conv_small_cout,
  * 8 ddim_step, 9 two_key_adapter, 10 range_paste, 11 lidar_metrics, 12 range_prepare, 13 image_prepare, 14 ff_geglu,
  * 15 row_chain, 16 chain_op, 17 layernorm_bwd, 18 attention_bwd, 19 split_source, 20 dpm_step, 21 lpips_distance,
- * 22 image_normalize, 23 mt_tensor, 24 mt_chunk, 25 grad_stats_record, 26 mt_pair, 27 loss_grad, 28 ref_augment, 29 snapshot_record.
+ * 22 image_normalize, 23 mt_tensor, 24 mt_chunk, 25 grad_stats_record, 26 mt_pair, 27 loss_grad, 28 ref_augment, 29 snapshot_record,
+ * 30 image_grid_source, 31 camera_export.
  * Returns 0 for an unknown id. */
 size_t mobi_struct_size(int id);
 /* Development hook: the library reads its MOBI_* A/B environment variables once, at the first launch
@@ -905,6 +907,44 @@ int mobi_gaussian_blur(const float* src, float* tmp, float* dst, int32_t H, int3
                        void* stream);
 int mobi_blend_frame(const float* mask_blur, const float* image, const uint8_t* pred, float* out, int32_t H, int32_t W,
                      void* stream);
+
+/* Camera results of a whole sampled batch (scripts/inference_test_bench.py:478-527), every picture of every object finished as
+ * HWC uint8 in RGB byte order in ONE buffer: a small box-reduction launch over the masks, then one export launch; the launch
+ * count does not depend on batch.  Per object b, with the arithmetic of mobi_paste_patch / mobi_gaussian_blur / mobi_blend_frame
+ * (same expressions, same operation order, no contraction):
+ *   P(patch)     bilinear resize to (crop_h, crop_w), align_corners = False, ((v + 1) / 2) * 255 clamped to [0, 255], truncated
+ *   pred         P(patch_pred) inside the crop window, 0 elsewhere;  I = the frame converted the same way
+ *   m            15-tap separable blur of mask (taps ascending, horizontal then vertical, BORDER_REFLECT_101 at the frame edges)
+ *   recon        m * I + (1 - m) * pred in fp32, rounded to nearest even, clamped (OpenCV's saturating conversion on write)
+ * pictures: 0 frame [H][W][3] = recon (only when frames != 0); 1 patch_pred [crop_h][crop_w][3] = recon on the crop window;
+ *   2 patch_gt [crop_h][crop_w][3] = P(patch_gt); 3 object_pred [224][224][3] = cv2.resize(pred[y1:y2, x1:x2], (224, 224)) with
+ *   y1, y2, x1, x2 the min / max row and column of the pixels with 1 - mask != 0 (max EXCLUSIVE, as the reference slices) and
+ *   cv2's 8-bit INTER_LINEAR restated in integers (positions (d + 0.5) * scale - 0.5 in fp64, each operation rounded; fraction
+ *   rounded to fp32; weights rint(frac * 2048); (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2);
+ *   4 object_ref [224][224][3] = (ref * std[c] + mean[c]) * 255 (CLIP's constants; a multiply, an add, a multiply, each rounded
+ *   to fp32), clamped to [0, 255], truncated.
+ * status i32 [batch] at out + status_offset: 1 where the box's exclusive slice is empty (object_pred is then not written), else 0.
+ * crop and offsets are HOST arrays: they are checked here and travel to the device inside the launch's own argument block, so
+ * what was checked is what the kernel uses; 1 <= batch <= 32 (more: MOBI_ERR_UNSUPPORTED; a caller splits the batch).
+ * A crop (left, top, crop_w, crop_h) that is not inside the frame, or a picture that is not inside [out, out + out_bytes):
+ * MOBI_ERR_ARG; an offset (or out) that is not a multiple of 4: MOBI_ERR_ALIGN; ref_h, ref_w != 224: MOBI_ERR_UNSUPPORTED; all
+ * before any launch.  With frames == 0 the export launch reads only each crop window and its 7-pixel blur halo of image / mask
+ * (the box reduction reads the masks once, whole).  Parity with cv2 unpinned, as the paste-back above.
+ * Addition to ABI 6 (struct id 31). */
+typedef struct mobi_camera_export_params {
+  const float* patch_pred; const float* patch_gt;           /* DEVICE [batch][3][hs][ws] in [-1, 1] */
+  const float* ref;                                         /* DEVICE [batch][3][ref_h][ref_w], CLIP-normalised */
+  const float* image;                                       /* DEVICE [batch][3][H][W] in [-1, 1] */
+  const float* mask;                                        /* DEVICE [batch][H][W], 1 = keep */
+  const float* taps;                                        /* DEVICE [15] */
+  const int32_t* crop;                                      /* HOST [batch][4] = (left, top, crop_w, crop_h) */
+  const int64_t* offsets;                                   /* HOST [batch][5] bytes: frame, patch_pred, patch_gt, object_pred, object_ref */
+  int32_t* box_ws;                                          /* DEVICE [batch][64][4] workspace of the box reduction */
+  uint8_t* out;                                             /* DEVICE */
+  int64_t out_bytes, status_offset;
+  int32_t batch, hs, ws, ref_h, ref_w, H, W, frames;
+} mobi_camera_export_params;
+int mobi_camera_export(const mobi_camera_export_params* p, void* stream);
 
 /* ddim.py:145-148 with q_sample (ddpm.py:284-287):
  *   img = (sa[t]*x0 + s1ma[t]*noise) * mask + (1 - mask) * img

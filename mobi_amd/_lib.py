@@ -217,13 +217,23 @@ class ImageGridSource(C.Structure):
                 ("out_offset", i64)]
 
 
+CAMERA_EXPORT_MAX_OBJECTS = 32    # per mobi_camera_export launch
+
+
+class CameraExportParams(C.Structure):
+    _fields_ = [("patch_pred", vp), ("patch_gt", vp), ("ref", vp), ("image", vp), ("mask", vp), ("taps", vp), ("crop", vp),
+                ("offsets", vp), ("box_ws", vp), ("out", vp), ("out_bytes", i64), ("status_offset", i64), ("batch", i32),
+                ("hs", i32), ("ws", i32), ("ref_h", i32), ("ref_w", i32), ("H", i32), ("W", i32), ("frames", i32)]
+
+
 STRUCT_IDS = {0: IgemmParams, 1: GroupNormParams, 2: LayerNormParams, 3: AttentionParams, 4: CtxAttentionParams,
               5: SkinnyLinearParams, 6: ConvSmallCinParams, 7: ConvSmallCoutParams, 8: DdimStepParams, 9: TwoKeyAdapterParams,
               10: RangePasteParams, 11: LidarMetricsParams, 12: RangePrepareParams, 13: ImagePrepareParams,
               14: FfGegluParams, 15: RowChainParams, 16: ChainOp,
               17: LayerNormBwdParams, 18: AttentionBwdParams, 19: SplitSource, 20: DpmStepParams,
               21: LpipsDistanceParams, 22: ImageNormalizeParams, 23: MtTensor, 24: MtChunk, 25: GradStatsRecord,
-              26: MtPair, 27: LossGradParams, 28: RefAugmentParams, 29: SnapshotRecord, 30: ImageGridSource}
+              26: MtPair, 27: LossGradParams, 28: RefAugmentParams, 29: SnapshotRecord, 30: ImageGridSource,
+              31: CameraExportParams}
 
 # every symbol include/mobi_engine.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -302,6 +312,7 @@ SYMBOLS = {
     "mobi_ref_augment": (C.c_int, [C.POINTER(RefAugmentParams), vp]),
     "mobi_drop_context": (C.c_int, [vp, vp, vp, vp, i32, i32, i64, vp]),
     "mobi_image_grid": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, vp, i64, vp]),
+    "mobi_camera_export": (C.c_int, [C.POINTER(CameraExportParams), vp]),
     "mobi_paste_patch": (C.c_int, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
     "mobi_gaussian_blur": (C.c_int, [vp, vp, vp, i32, i32, vp, i32, vp]),
     "mobi_blend_frame": (C.c_int, [vp, vp, vp, vp, i32, i32, vp]),

@@ -542,6 +542,375 @@ __global__ __launch_bounds__(256) void image_grid_kernel(const ig_table t, unsig
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The test bench's camera pictures of a sampled batch (scripts/inference_test_bench.py:478-527) in one launch: per object the
+// recomposed frame, its crop window, the resized ground-truth patch, the object crop of the pasted prediction at 224 x 224 and
+// the un-normalised reference image, all HWC uint8 RGB in one buffer (include/mobi_engine.h, mobi_camera_export).
+// blockIdx.y = the object; a block walks that object's 64 x 32 pixel tiles, of four kinds, and leaves each tile's bytes in LDS,
+// from where whole rows go out as dwords (single bytes only up to a row's first and after its last 4-byte boundary).
+// The blend tile holds the mask with its 7-pixel halo in LDS and takes both blur passes from there.  The expressions are those
+// of paste_patch_kernel / blur_pass_kernel / blend_kernel above; this file is compiled without FMA contraction.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int CE_TW = 64, CE_TH = 32, CE_R = 7, CE_K = 15;
+constexpr int CE_MW = CE_TW + 16, CE_MH = CE_TH + 2 * CE_R;          // mask tile: columns x0 - 8 .. x0 + 71, rows y0 - 7 .. y0 + 38
+constexpr int CE_OBW = CE_TW * 3;
+constexpr int CE_MAX_OBJECTS = 32, CE_BOX_PARTS = 64, CE_REF = 224;
+struct ce_object {
+  int left, top, cw, ch;
+  long long off[5];                                          // frame, patch_pred, patch_gt, object_pred, object_ref
+};
+struct ce_table { ce_object o[CE_MAX_OBJECTS]; };
+struct ce_args {
+  const float* patch_pred; const float* patch_gt; const float* ref; const float* image; const float* mask; const float* taps;
+  int* box_ws; unsigned char* out; int* status;
+  int hs, ws, H, W, frames;
+};
+
+// rows / columns of the pixels with 1 - mask != 0: block (j, b) reduces its stripe of rows to {min x, max x, min y, max y}
+// (W, -1, H, -1 when it has none); the export launch folds an object's CE_BOX_PARTS records.  No atomics, nothing to pre-set.
+__global__ __launch_bounds__(256) void camera_box_kernel(const float* __restrict__ mask, int* __restrict__ box_ws, int H, int W) {
+  __shared__ int part[4][4];
+  const int b = blockIdx.y, rows = (H + CE_BOX_PARTS - 1) / CE_BOX_PARTS;
+  const int r0 = blockIdx.x * rows, r1 = r0 + rows < H ? r0 + rows : H;
+  const float* m = mask + (long long)b * H * W;
+  int lox = W, hix = -1, loy = H, hiy = -1;
+  const long long i0 = (long long)r0 * W, i1 = (long long)(r1 > r0 ? r1 : r0) * W;
+  for (long long i = i0 + threadIdx.x; i < i1; i += 256) {
+    if (1.0f - m[i] != 0.0f) {
+      const int y = (int)(i / W), x = (int)(i - (long long)y * W);
+      lox = x < lox ? x : lox; hix = x > hix ? x : hix; loy = y < loy ? y : loy; hiy = y > hiy ? y : hiy;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int a = __shfl_xor(lox, o, 64), c = __shfl_xor(hix, o, 64), d = __shfl_xor(loy, o, 64), e = __shfl_xor(hiy, o, 64);
+    lox = a < lox ? a : lox; hix = c > hix ? c : hix; loy = d < loy ? d : loy; hiy = e > hiy ? e : hiy;
+  }
+  if ((threadIdx.x & 63) == 0) {
+    int* p = part[threadIdx.x >> 6];
+    p[0] = lox; p[1] = hix; p[2] = loy; p[3] = hiy;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) {
+      lox = part[w][0] < lox ? part[w][0] : lox; hix = part[w][1] > hix ? part[w][1] : hix;
+      loy = part[w][2] < loy ? part[w][2] : loy; hiy = part[w][3] > hiy ? part[w][3] : hiy;
+    }
+    int* o = box_ws + ((long long)b * CE_BOX_PARTS + blockIdx.x) * 4;
+    o[0] = lox; o[1] = hix; o[2] = loy; o[3] = hiy;
+  }
+}
+
+__device__ __forceinline__ int ce_reflect(int q, int n) {    // BORDER_REFLECT_101, as blur_pass_kernel
+  if (n == 1) return 0;
+  while (q < 0 || q >= n) q = q < 0 ? -q : 2 * (n - 1) - q;
+  return q;
+}
+
+// source taps of output index d of the align_corners = False resize, as paste_patch_kernel
+__device__ __forceinline__ void ce_taps(float scale, int d, int n, int& i0, int& i1, float& l) {
+  float f = scale * ((float)d + 0.5f) - 0.5f;
+  if (f < 0.f) f = 0.f;
+  i0 = (int)f;
+  i1 = i0 + (i0 < n - 1 ? 1 : 0);
+  l = f - (float)i0;
+}
+
+// P: one channel of the resized patch as a byte value, as paste_patch_kernel
+__device__ __forceinline__ int ce_patch_byte(const float* __restrict__ pc, int ws, int y0, int y1, int x0, int x1, float ly,
+                                             float lx) {
+  const float hy = 1.0f - ly, hx = 1.0f - lx;
+  const float v = hy * (hx * pc[(long long)y0 * ws + x0] + lx * pc[(long long)y0 * ws + x1]) +
+                  ly * (hx * pc[(long long)y1 * ws + x0] + lx * pc[(long long)y1 * ws + x1]);
+  float u = ((v + 1.0f) / 2.0f) * 255.0f;
+  u = u < 0.f ? 0.f : (u > 255.f ? 255.f : u);
+  return (int)u;
+}
+
+// rows [ry0, ry1) x columns [rx0, rx1) of the tile at (tx0, ty0) -> the picture at dst whose pixel (0, 0) is (ox, oy) of the
+// same coordinates and whose rows are `pitch` bytes; dst is 4-byte aligned.  One wave per row, at most 48 dwords.
+__device__ __forceinline__ void ce_store(const unsigned char* ob, int tx0, int ty0, int rx0, int ry0, int rx1, int ry1,
+                                         unsigned char* dst, long long pitch, int ox, int oy) {
+  if (rx1 <= rx0) return;
+  const int lane = threadIdx.x & 63, nb = (rx1 - rx0) * 3;
+  for (int y = ry0 + (threadIdx.x >> 6); y < ry1; y += 4) {
+    const unsigned char* src = ob + (y - ty0) * CE_OBW + (rx0 - tx0) * 3;
+    const long long g0 = (long long)(y - oy) * pitch + (long long)(rx0 - ox) * 3;
+    int head = (int)((4 - (g0 & 3)) & 3);
+    head = head > nb ? nb : head;
+    const int ndw = (nb - head) >> 2, tail = nb - head - ndw * 4;
+    if (lane < ndw) {
+      const unsigned char* s = src + head + lane * 4;
+      const unsigned word = (unsigned)s[0] | ((unsigned)s[1] << 8) | ((unsigned)s[2] << 16) | ((unsigned)s[3] << 24);
+      *reinterpret_cast<unsigned*>(dst + g0 + head + lane * 4) = word;
+    } else if (lane >= 56 && lane < 56 + head) {
+      dst[g0 + (lane - 56)] = src[lane - 56];
+    } else if (lane >= 60 && lane < 60 + tail) {
+      const int k = head + ndw * 4 + (lane - 60);
+      dst[g0 + k] = src[k];
+    }
+  }
+}
+
+// tile kind 0: recon = m * I + (1 - m) * pred on the tile at (x0, y0) of the frame, x0 % 64 == 0; written to the frame picture
+// (frames) and, where the tile meets the crop window, to patch_pred.  Only what the tile's part of the region (the frame, or the
+// crop window when no frame is written) needs is read: its pixels of image, its pixels and a 7-pixel halo of mask.
+__device__ __forceinline__ void ce_tile_blend(const ce_args& a, const ce_object& o, int b, int x0, int y0, float* mt, float* hb,
+                                              unsigned char* ob) {
+  const int tid = threadIdx.x;
+  const int gx0 = a.frames ? 0 : o.left, gy0 = a.frames ? 0 : o.top;
+  const int gx1 = a.frames ? a.W : o.left + o.cw, gy1 = a.frames ? a.H : o.top + o.ch;
+  const int ax0 = x0 > gx0 ? x0 : gx0, ax1 = x0 + CE_TW < gx1 ? x0 + CE_TW : gx1;
+  const int ay0 = y0 > gy0 ? y0 : gy0, ay1 = y0 + CE_TH < gy1 ? y0 + CE_TH : gy1;
+  const long long plane = (long long)a.H * a.W;
+  const float* mask = a.mask + (long long)b * plane;
+  const float* image = a.image + (long long)b * 3 * plane;
+  const bool vec = (a.W & 3) == 0 && ((reinterpret_cast<uintptr_t>(a.mask) | reinterpret_cast<uintptr_t>(a.image)) & 15) == 0;
+  for (int i = tid; i < CE_MH * (CE_MW / 4); i += 256) {                 // the mask and its halo, 16 bytes a lane where whole
+    const int j = i / (CE_MW / 4), c4 = (i - j * (CE_MW / 4)) * 4;
+    const int y = y0 - CE_R + j, q0 = x0 - 8 + c4;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (y >= ay0 - CE_R && y < ay1 + CE_R) {
+      const float* row = mask + (long long)ce_reflect(y, a.H) * a.W;
+      if (vec && q0 >= 0 && q0 + 3 < a.W && q0 >= ax0 - CE_R && q0 + 3 < ax1 + CE_R) {
+        v = *reinterpret_cast<const float4*>(row + q0);
+      } else {
+        v.x = (q0 >= ax0 - CE_R && q0 < ax1 + CE_R) ? row[ce_reflect(q0, a.W)] : 0.f;
+        v.y = (q0 + 1 >= ax0 - CE_R && q0 + 1 < ax1 + CE_R) ? row[ce_reflect(q0 + 1, a.W)] : 0.f;
+        v.z = (q0 + 2 >= ax0 - CE_R && q0 + 2 < ax1 + CE_R) ? row[ce_reflect(q0 + 2, a.W)] : 0.f;
+        v.w = (q0 + 3 >= ax0 - CE_R && q0 + 3 < ax1 + CE_R) ? row[ce_reflect(q0 + 3, a.W)] : 0.f;
+      }
+    }
+    *reinterpret_cast<float4*>(mt + j * CE_MW + c4) = v;
+  }
+  __syncthreads();
+  for (int i = tid; i < CE_MH * (CE_TW / 4); i += 256) {                 // horizontal pass: pixel lx reads mask columns lx + 1 + k
+    const int j = i / (CE_TW / 4), i4 = (i - j * (CE_TW / 4)) * 4;
+    float s[20];
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+      const float4 t = *reinterpret_cast<const float4*>(mt + j * CE_MW + i4 + 4 * q);
+      s[4 * q] = t.x; s[4 * q + 1] = t.y; s[4 * q + 2] = t.z; s[4 * q + 3] = t.w;
+    }
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < CE_K; ++k) {
+      const float t = a.taps[k];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[e] += t * s[e + k + 1];
+    }
+    *reinterpret_cast<float4*>(hb + j * CE_TW + i4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+  }
+  __syncthreads();
+  const float sy = (float)a.hs / (float)o.ch, sx = (float)a.ws / (float)o.cw;
+  const float* patch = a.patch_pred + (long long)b * 3 * a.hs * a.ws;
+  for (int p = 0; p < 2; ++p) {                                          // vertical pass and the blend, four pixels a lane
+    const int ly = (tid >> 4) + 16 * p, lx4 = (tid & 15) * 4, y = y0 + ly, x = x0 + lx4;
+    if (y < ay0 || y >= ay1 || x >= ax1 || x + 3 < ax0) continue;
+    float m[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < CE_K; ++k) {
+      const float t = a.taps[k];
+      const float4 h = *reinterpret_cast<const float4*>(hb + (ly + k) * CE_TW + lx4);
+      m[0] += t * h.x; m[1] += t * h.y; m[2] += t * h.z; m[3] += t * h.w;
+    }
+    const bool whole = vec && x >= ax0 && x + 3 < ax1;
+    const int cy = y - o.top;
+    const bool row_in = cy >= 0 && cy < o.ch;
+    int py0 = 0, py1 = 0;
+    float ply = 0.f;
+    if (row_in) ce_taps(sy, cy, a.hs, py0, py1, ply);
+    unsigned bytes[12];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float* ic = image + c * plane + (long long)y * a.W + x;
+      float v[4];
+      if (whole) {
+        const float4 t = *reinterpret_cast<const float4*>(ic);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = (x + e >= ax0 && x + e < ax1) ? ic[e] : 0.f;
+      }
+      const float* pc = patch + (long long)c * a.hs * a.ws;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float u = ((v[e] + 1.0f) / 2.0f) * 255.0f;
+        u = u < 0.f ? 0.f : (u > 255.f ? 255.f : u);
+        const float iu = (float)(unsigned char)(int)u;
+        const int cx = x + e - o.left;
+        float pred = 0.f;
+        if (row_in && cx >= 0 && cx < o.cw) {
+          int px0, px1;
+          float plx;
+          ce_taps(sx, cx, a.ws, px0, px1, plx);
+          pred = (float)ce_patch_byte(pc, a.ws, py0, py1, px0, px1, ply, plx);
+        }
+        const float r = m[e] * iu + (1.0f - m[e]) * pred;
+        int q = __float2int_rn(r);                                       // nearest even, saturating
+        q = q < 0 ? 0 : (q > 255 ? 255 : q);
+        bytes[e * 3 + c] = (unsigned)q;
+      }
+    }
+    unsigned* w = reinterpret_cast<unsigned*>(ob + ly * CE_OBW + lx4 * 3);
+#pragma unroll
+    for (int q = 0; q < 3; ++q)
+      w[q] = bytes[4 * q] | (bytes[4 * q + 1] << 8) | (bytes[4 * q + 2] << 16) | (bytes[4 * q + 3] << 24);
+  }
+  __syncthreads();
+  if (a.frames) ce_store(ob, x0, y0, ax0, ay0, ax1, ay1, a.out + o.off[0], (long long)a.W * 3, 0, 0);
+  const int cx0 = ax0 > o.left ? ax0 : o.left, cx1 = ax1 < o.left + o.cw ? ax1 : o.left + o.cw;
+  const int cy0 = ay0 > o.top ? ay0 : o.top, cy1 = ay1 < o.top + o.ch ? ay1 : o.top + o.ch;
+  ce_store(ob, x0, y0, cx0, cy0, cx1, cy1, a.out + o.off[1], (long long)o.cw * 3, o.left, o.top);
+}
+
+// tile kind 1: P(patch_gt) on the tile at (x0, y0) of the crop window's own coordinates
+__device__ __forceinline__ void ce_tile_patch(const ce_args& a, const ce_object& o, int b, int x0, int y0, unsigned char* ob) {
+  const float sy = (float)a.hs / (float)o.ch, sx = (float)a.ws / (float)o.cw;
+  const float* patch = a.patch_gt + (long long)b * 3 * a.hs * a.ws;
+  const int lx = threadIdx.x & 63, x = x0 + lx;
+  int px0 = 0, px1 = 0;
+  float plx = 0.f;
+  if (x < o.cw) ce_taps(sx, x, a.ws, px0, px1, plx);
+  for (int ly = threadIdx.x >> 6; ly < CE_TH; ly += 4) {
+    const int y = y0 + ly;
+    if (x >= o.cw || y >= o.ch) continue;
+    int py0, py1;
+    float ply;
+    ce_taps(sy, y, a.hs, py0, py1, ply);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      ob[ly * CE_OBW + lx * 3 + c] = (unsigned char)ce_patch_byte(patch + (long long)c * a.hs * a.ws, a.ws, py0, py1, px0, px1, ply, plx);
+  }
+  __syncthreads();
+  const int x1 = x0 + CE_TW < o.cw ? x0 + CE_TW : o.cw, y1 = y0 + CE_TH < o.ch ? y0 + CE_TH : o.ch;
+  ce_store(ob, x0, y0, x0, y0, x1, y1, a.out + o.off[2], (long long)o.cw * 3, 0, 0);
+}
+
+// taps of OpenCV's 8-bit INTER_LINEAR resize (ldm/data/nuscenes.py:resize_linear_u8): position in fp64, every operation
+// rounded on its own, the fraction rounded to fp32, 11-bit integer weights
+__device__ __forceinline__ void ce_cv_taps(int d, int n_dst, int n_src, int& i0, int& i1, int& w0, int& w1) {
+  const double scale = (double)n_src / (double)n_dst;
+  const double f = __dsub_rn(__dmul_rn(__dadd_rn((double)d, 0.5), scale), 0.5);
+  const double fl = floor(f);
+  i0 = (int)fl;
+  float frac = (float)__dsub_rn(f, fl);
+  if (i0 < 0) { i0 = 0; frac = 0.f; }
+  if (i0 >= n_src - 1) { i0 = n_src - 1; frac = 0.f; }
+  i1 = i0 + 1 < n_src - 1 ? i0 + 1 : n_src - 1;
+  w1 = (int)rintf(frac * 2048.0f);
+  w0 = (int)rintf((1.0f - frac) * 2048.0f);
+}
+
+// pred at frame pixel (y, x): P(patch_pred) inside the crop window, 0 elsewhere -- recomputed, not read from another block's tile
+__device__ __forceinline__ int ce_pred_at(const ce_args& a, const ce_object& o, const float* __restrict__ pc, float sy, float sx,
+                                          int y, int x) {
+  const int cy = y - o.top, cx = x - o.left;
+  if (cy < 0 || cy >= o.ch || cx < 0 || cx >= o.cw) return 0;
+  int py0, py1, px0, px1;
+  float ply, plx;
+  ce_taps(sy, cy, a.hs, py0, py1, ply);
+  ce_taps(sx, cx, a.ws, px0, px1, plx);
+  return ce_patch_byte(pc, a.ws, py0, py1, px0, px1, ply, plx);
+}
+
+// tile kind 2: object_pred = cv2.resize(pred[y1:y2, x1:x2], (224, 224)) on the tile at (x0, y0) of the 224 x 224 picture
+__device__ __forceinline__ void ce_tile_object(const ce_args& a, const ce_object& o, int b, int x0, int y0, const int* box,
+                                               unsigned char* ob) {
+  const int bx1 = box[0], bx2 = box[1], by1 = box[2], by2 = box[3];
+  const int sw = bx2 - bx1, sh = by2 - by1;                              // the slice excludes the last row and column
+  if (sw <= 0 || sh <= 0) return;                                        // (block-uniform: the status word reports it)
+  const float sy = (float)a.hs / (float)o.ch, sx = (float)a.ws / (float)o.cw;
+  const float* patch = a.patch_pred + (long long)b * 3 * a.hs * a.ws;
+  const int lx = threadIdx.x & 63, x = x0 + lx;
+  int xi0 = 0, xi1 = 0, a0 = 0, a1 = 0;
+  if (x < CE_REF) ce_cv_taps(x, CE_REF, sw, xi0, xi1, a0, a1);
+  for (int ly = threadIdx.x >> 6; ly < CE_TH; ly += 4) {
+    const int y = y0 + ly;
+    if (x >= CE_REF || y >= CE_REF) continue;
+    int yi0, yi1, b0, b1;
+    ce_cv_taps(y, CE_REF, sh, yi0, yi1, b0, b1);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float* pc = patch + (long long)c * a.hs * a.ws;
+      const int r0 = ce_pred_at(a, o, pc, sy, sx, by1 + yi0, bx1 + xi0) * a0 + ce_pred_at(a, o, pc, sy, sx, by1 + yi0, bx1 + xi1) * a1;
+      const int r1 = ce_pred_at(a, o, pc, sy, sx, by1 + yi1, bx1 + xi0) * a0 + ce_pred_at(a, o, pc, sy, sx, by1 + yi1, bx1 + xi1) * a1;
+      int v = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
+      v = v < 0 ? 0 : (v > 255 ? 255 : v);
+      ob[ly * CE_OBW + lx * 3 + c] = (unsigned char)v;
+    }
+  }
+  __syncthreads();
+  const int x1 = x0 + CE_TW < CE_REF ? x0 + CE_TW : CE_REF, y1 = y0 + CE_TH < CE_REF ? y0 + CE_TH : CE_REF;
+  ce_store(ob, x0, y0, x0, y0, x1, y1, a.out + o.off[3], (long long)CE_REF * 3, 0, 0);
+}
+
+// tile kind 3: object_ref = un_norm_clip(ref) * 255 on the tile at (x0, y0) of the 224 x 224 picture
+__device__ __forceinline__ void ce_tile_ref(const ce_args& a, const ce_object& o, int b, int x0, int y0, unsigned char* ob) {
+  const float stdv[3] = {(float)0.26862954, (float)0.26130258, (float)0.27577711};
+  const float mean[3] = {(float)0.48145466, (float)0.4578275, (float)0.40821073};
+  const float* ref = a.ref + (long long)b * 3 * CE_REF * CE_REF;
+  const int lx = threadIdx.x & 63, x = x0 + lx;
+  for (int ly = threadIdx.x >> 6; ly < CE_TH; ly += 4) {
+    const int y = y0 + ly;
+    if (x >= CE_REF || y >= CE_REF) continue;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float u = ref[((long long)c * CE_REF + y) * CE_REF + x] * stdv[c];
+      u = u + mean[c];
+      u = u * 255.0f;
+      u = u < 0.f ? 0.f : (u > 255.f ? 255.f : u);
+      ob[ly * CE_OBW + lx * 3 + c] = (unsigned char)(int)u;
+    }
+  }
+  __syncthreads();
+  const int x1 = x0 + CE_TW < CE_REF ? x0 + CE_TW : CE_REF, y1 = y0 + CE_TH < CE_REF ? y0 + CE_TH : CE_REF;
+  ce_store(ob, x0, y0, x0, y0, x1, y1, a.out + o.off[4], (long long)CE_REF * 3, 0, 0);
+}
+
+__global__ __launch_bounds__(256) void camera_export_kernel(const ce_args a, const ce_table t) {
+  __shared__ __attribute__((aligned(16))) float mt[CE_MH * CE_MW];
+  __shared__ __attribute__((aligned(16))) float hb[CE_MH * CE_TW];
+  __shared__ __attribute__((aligned(16))) unsigned char ob[CE_TH * CE_OBW];
+  __shared__ int box[4];
+  const int b = blockIdx.y;
+  const ce_object& o = t.o[b];
+  // the blend tiles lie on the frame's 64 x 32 grid (so that rows of four floats stay 16-byte aligned), the others on their picture's
+  const int bx0 = a.frames ? 0 : o.left / CE_TW, bx1 = a.frames ? (a.W + CE_TW - 1) / CE_TW : (o.left + o.cw - 1) / CE_TW + 1;
+  const int by0 = a.frames ? 0 : o.top / CE_TH, by1 = a.frames ? (a.H + CE_TH - 1) / CE_TH : (o.top + o.ch - 1) / CE_TH + 1;
+  const int nbx = bx1 - bx0, n_blend = nbx * (by1 - by0);
+  const int npx = (o.cw + CE_TW - 1) / CE_TW, n_patch = npx * ((o.ch + CE_TH - 1) / CE_TH);
+  constexpr int NRX = (CE_REF + CE_TW - 1) / CE_TW, N_REF = NRX * ((CE_REF + CE_TH - 1) / CE_TH);
+  const int total = n_blend + n_patch + 2 * N_REF;
+  if (threadIdx.x < 64) {                                                // the object's box: 1 KiB of partial records
+    const int* p = a.box_ws + ((long long)b * CE_BOX_PARTS + threadIdx.x) * 4;
+    int lox = p[0], hix = p[1], loy = p[2], hiy = p[3];
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+      const int c = __shfl_xor(lox, s, 64), d = __shfl_xor(hix, s, 64), e = __shfl_xor(loy, s, 64), f = __shfl_xor(hiy, s, 64);
+      lox = c < lox ? c : lox; hix = d > hix ? d : hix; loy = e < loy ? e : loy; hiy = f > hiy ? f : hiy;
+    }
+    if (threadIdx.x == 0) { box[0] = lox; box[1] = hix; box[2] = loy; box[3] = hiy; }
+  }
+  __syncthreads();
+  for (int i = blockIdx.x; i < total; i += gridDim.x) {
+    if (i < n_blend) {
+      ce_tile_blend(a, o, b, (bx0 + i % nbx) * CE_TW, (by0 + i / nbx) * CE_TH, mt, hb, ob);
+    } else if (i < n_blend + n_patch) {
+      const int k = i - n_blend;
+      ce_tile_patch(a, o, b, (k % npx) * CE_TW, (k / npx) * CE_TH, ob);
+    } else if (i < n_blend + n_patch + N_REF) {
+      const int k = i - n_blend - n_patch;
+      if (k == 0 && threadIdx.x == 0) a.status[b] = (box[1] - box[0] <= 0 || box[3] - box[2] <= 0) ? 1 : 0;
+      ce_tile_object(a, o, b, (k % NRX) * CE_TW, (k / NRX) * CE_TH, box, ob);
+    } else {
+      const int k = i - n_blend - n_patch - N_REF;
+      ce_tile_ref(a, o, b, (k % NRX) * CE_TW, (k / NRX) * CE_TH, ob);
+    }
+    __syncthreads();
+  }
+}
+
 }  // namespace mobi
 
 using namespace mobi;
@@ -594,6 +963,47 @@ extern "C" int mobi_image_grid(const mobi_image_grid_source* sources, int32_t n_
     most = bytes > most ? bytes : most;
   }
   hipLaunchKernelGGL(image_grid_kernel, dim3(egrid_pp((most + 3) / 4), n_sources), dim3(256), 0, ST(stream), t, out);
+  MOBI_CHECK_LAUNCH();
+  return MOBI_OK;
+}
+
+extern "C" int mobi_camera_export(const mobi_camera_export_params* p, void* stream) {
+  if (!p || !p->patch_pred || !p->patch_gt || !p->ref || !p->image || !p->mask || !p->taps || !p->crop || !p->offsets ||
+      !p->box_ws || !p->out) return MOBI_ERR_ARG;
+  if (p->batch <= 0 || p->hs <= 0 || p->ws <= 0 || p->ref_h <= 0 || p->ref_w <= 0 || p->H <= 0 || p->W <= 0 || p->out_bytes <= 0)
+    return MOBI_ERR_ARG;
+  if (p->ref_h != CE_REF || p->ref_w != CE_REF || p->batch > CE_MAX_OBJECTS) return MOBI_ERR_UNSUPPORTED;
+  if ((long long)p->H * p->W > 0x7fffffffLL / 3) return MOBI_ERR_UNSUPPORTED;                  // (32-bit pixel indices)
+  // one picture: inside the buffer, on a 4-byte boundary
+  auto place = [&](long long off, long long bytes) {
+    if (off < 0 || off > p->out_bytes || bytes > p->out_bytes - off) return (int)MOBI_ERR_ARG;
+    return (off & 3) ? (int)MOBI_ERR_ALIGN : (int)MOBI_OK;
+  };
+  if (reinterpret_cast<uintptr_t>(p->out) & 3) return MOBI_ERR_ALIGN;
+  int rc = place(p->status_offset, 4LL * p->batch);
+  if (rc != MOBI_OK) return rc;
+  ce_table t = {};
+  int most = 0;
+  const int n_ref = ((CE_REF + CE_TW - 1) / CE_TW) * ((CE_REF + CE_TH - 1) / CE_TH);
+  for (int b = 0; b < p->batch; ++b) {
+    ce_object& o = t.o[b];
+    o.left = p->crop[b * 4], o.top = p->crop[b * 4 + 1], o.cw = p->crop[b * 4 + 2], o.ch = p->crop[b * 4 + 3];
+    if (o.left < 0 || o.top < 0 || o.cw <= 0 || o.ch <= 0 || o.cw > p->W - o.left || o.ch > p->H - o.top) return MOBI_ERR_ARG;
+    const long long sizes[5] = {p->frames ? 3LL * p->H * p->W : 0, 3LL * o.cw * o.ch, 3LL * o.cw * o.ch, 3LL * CE_REF * CE_REF,
+                                3LL * CE_REF * CE_REF};
+    for (int k = p->frames ? 0 : 1; k < 5; ++k) {
+      o.off[k] = p->offsets[b * 5 + k];
+      if ((rc = place(o.off[k], sizes[k])) != MOBI_OK) return rc;
+    }
+    const int tiles_x = p->frames ? (p->W + CE_TW - 1) / CE_TW : (o.left + o.cw - 1) / CE_TW - o.left / CE_TW + 1;
+    const int tiles_y = p->frames ? (p->H + CE_TH - 1) / CE_TH : (o.top + o.ch - 1) / CE_TH - o.top / CE_TH + 1;
+    const int total = tiles_x * tiles_y + ((o.cw + CE_TW - 1) / CE_TW) * ((o.ch + CE_TH - 1) / CE_TH) + 2 * n_ref;
+    most = total > most ? total : most;
+  }
+  ce_args a = {p->patch_pred, p->patch_gt, p->ref, p->image, p->mask, p->taps, p->box_ws, p->out,
+               reinterpret_cast<int*>(p->out + p->status_offset), p->hs, p->ws, p->H, p->W, p->frames != 0};
+  hipLaunchKernelGGL(camera_box_kernel, dim3(CE_BOX_PARTS, p->batch), dim3(256), 0, ST(stream), p->mask, p->box_ws, p->H, p->W);
+  hipLaunchKernelGGL(camera_export_kernel, dim3(most > 2048 ? 2048 : most, p->batch), dim3(256), 0, ST(stream), a, t);
   MOBI_CHECK_LAUNCH();
   return MOBI_OK;
 }

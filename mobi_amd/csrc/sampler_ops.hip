@@ -279,6 +279,7 @@ extern "C" size_t mobi_struct_size(int id) {
     case 28: return sizeof(mobi_ref_augment_params);
     case 29: return sizeof(mobi_snapshot_record);
     case 30: return sizeof(mobi_image_grid_source);
+    case 31: return sizeof(mobi_camera_export_params);
     default: return 0;
   }
 }

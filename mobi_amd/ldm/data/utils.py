@@ -119,6 +119,35 @@ def paste_camera_patch(*, patch_pred, image, mask, crop, ksize=15, sigma=7.0):
     return ops.blend_frame(blur, image, frame), frame
 
 
+def export_camera_batch(*, patch_pred, patch_gt, ref_image, image, mask, crop, frames=True, ksize=15, sigma=7.0):
+    """The camera results of scripts/inference_test_bench.py:478-527 for the WHOLE batch: `mobi_camera_export`, then ONE copy into
+    pinned host memory.  patch_pred / patch_gt: fp32 [B, 3, hs, ws] in [-1, 1]; ref_image: [B, 3, h, w] CLIP-normalised (resized to
+    224 x 224 first, as un_norm_clip does); image: [B, 3, H, W] in [-1, 1]; mask: [B, H, W] (1 = keep); crop: B x (left, top,
+    crop_W, crop_H).  Returns B dicts of numpy uint8 HWC views in RGB order -- what the reference's files hold, since it hands cv2
+    BGR arrays: frame (only with `frames`), patch_pred (the composited crop), patch_gt, object_pred, object_ref.  ValueError
+    names an object whose mask box is empty once its last row and column are excluded, as the reference slices it."""
+    assert ksize == 15, "mobi_camera_export is built for the reference's 15-tap blur"
+    dev = patch_pred.device
+    f = lambda t: _as_dev(t, dev).float().contiguous()
+    crops = [tuple(int(v) for v in c) for c in (crop.tolist() if isinstance(crop, torch.Tensor) else crop)]
+    ref = _resize(f(ref_image), (224, 224)).contiguous()
+    taps = torch.from_numpy(gaussian_kernel1d(ksize, sigma)).to(dev)
+    out, layout = ops.camera_export(f(patch_pred), f(patch_gt), ref, f(image), f(mask), crops, taps, frames=frames)
+    host = torch.empty(layout["bytes"], dtype=torch.uint8, pin_memory=True)
+    with ops._Timed("camera_export_d2h", 0.0, float(layout["bytes"])):
+        host.copy_(out, non_blocking=True)
+    torch.cuda.current_stream(dev).synchronize()
+    flat = host.numpy()
+    status = flat[layout["status"]:layout["bytes"]].view(np.int32)
+    pictures = [{name: flat[o:o + h * w * 3].reshape(h, w, 3) for name, (o, (h, w, _)) in entry.items()} for entry in layout["objects"]]
+    if status.any():
+        err = ValueError(f"export_camera_batch: the mask box of object(s) {np.nonzero(status)[0].tolist()} is empty "
+                         "(a single row or column of edit pixels, or none)")
+        err.pictures = pictures                                        # the other objects' pictures are complete
+        raise err
+    return pictures
+
+
 # --------------------------------------------------------------------------------------
 # pictures (visualisation only; the drawing primitives are cv2's in the reference)
 # --------------------------------------------------------------------------------------

@@ -1693,6 +1693,61 @@ def image_grid(tensors, max_images, nrow=4, padding=2, *, clamp=True, rescale=Tr
     return {key: flat[o:o + hg * wg * 3].reshape(hg, wg, 3) for key, (o, hg, wg) in zip(keys, shapes)}
 
 
+CAMERA_EXPORT_PICTURES = ("frame", "patch_pred", "patch_gt", "object_pred", "object_ref")
+
+
+def camera_export_layout(crops, H, W, frames=True):
+    """Where `camera_export` puts its pictures: crops = B x (left, top, crop_W, crop_H) Python ints ->
+    dict(objects=[{name: (byte offset, (h, w, 3))} per object, without "frame" unless `frames`], status=byte offset of the int32 [B]
+    status words, bytes=size of the buffer).  Every picture starts on a 4-byte boundary; none overlap (include/mobi_engine.h)."""
+    offset, objects = 0, []
+    for crop in crops:
+        left, top, cw, ch = (int(v) for v in crop)
+        if left < 0 or top < 0 or cw <= 0 or ch <= 0 or left + cw > W or top + ch > H:
+            raise ValueError(f"camera_export: the crop window {(left, top, cw, ch)} leaves its {H} x {W} frame")
+        shapes = {"frame": (int(H), int(W), 3), "patch_pred": (ch, cw, 3), "patch_gt": (ch, cw, 3), "object_pred": (224, 224, 3),
+                  "object_ref": (224, 224, 3)}
+        entry = {}
+        for name in CAMERA_EXPORT_PICTURES:
+            if name == "frame" and not frames:
+                continue
+            h, w, _ = shapes[name]
+            entry[name] = (offset, shapes[name])
+            offset += (h * w * 3 + 3) // 4 * 4
+        objects.append(entry)
+    return {"objects": objects, "status": offset, "bytes": offset + 4 * len(objects)}
+
+
+def camera_export(patch_pred, patch_gt, ref, image, mask, crops, taps, *, frames=True):
+    """The test bench's camera pictures of a batch (include/mobi_engine.h, mobi_camera_export): patch_pred / patch_gt fp32
+    [B, 3, hs, ws], ref fp32 [B, 3, 224, 224], image fp32 [B, 3, H, W], mask fp32 [B, H, W], crops B x (left, top, crop_W, crop_H)
+    on the host, taps fp32 [15] -> (uint8 device buffer, `camera_export_layout`).  A box reduction and one export launch per 32
+    objects, whatever the crops."""
+    lib = _lib.load()
+    for t_ in (patch_pred, patch_gt, ref, image, mask, taps):
+        assert _dev(t_).dtype == torch.float32 and t_.is_contiguous() and t_.device == patch_pred.device
+    b, _, hs, ws = patch_pred.shape
+    _, _, H, W = image.shape
+    assert patch_pred.shape[1] == 3 and patch_gt.shape == patch_pred.shape and ref.dim() == 4 and ref.shape[:2] == (b, 3)
+    assert image.shape[:2] == (b, 3) and tuple(mask.shape) == (b, H, W) and taps.numel() == 15 and len(crops) == b
+    layout = camera_export_layout(crops, H, W, frames)
+    out = torch.empty(layout["bytes"], device=image.device, dtype=torch.uint8)
+    box_ws = torch.empty((b, 64, 4), device=image.device, dtype=torch.int32)
+    step = _lib.CAMERA_EXPORT_MAX_OBJECTS
+    for lo in range(0, b, step):
+        n = min(step, b - lo)
+        crop = (C.c_int32 * (4 * n))(*[int(v) for c_ in crops[lo:lo + n] for v in c_])
+        offs = (C.c_int64 * (5 * n))(*[o.get(name, (0,))[0] for o in layout["objects"][lo:lo + n] for name in CAMERA_EXPORT_PICTURES])
+        p = _lib.CameraExportParams()
+        p.patch_pred, p.patch_gt, p.ref, p.image, p.mask = (_ptr(t_[lo:]) for t_ in (patch_pred, patch_gt, ref, image, mask))
+        p.taps, p.crop, p.offsets = _ptr(taps), C.cast(crop, C.c_void_p), C.cast(offs, C.c_void_p)
+        p.box_ws, p.out, p.out_bytes, p.status_offset = _ptr(box_ws[lo:]), _ptr(out), layout["bytes"], layout["status"] + 4 * lo
+        p.batch, p.hs, p.ws, p.ref_h, p.ref_w, p.H, p.W, p.frames = n, hs, ws, ref.shape[2], ref.shape[3], H, W, int(bool(frames))
+        with _Timed("camera_export", 0.0, float(layout["bytes"]), f"b{n}"):
+            _lib.check(lib.mobi_camera_export(C.byref(p), _stream()), "mobi_camera_export")
+    return out, layout
+
+
 def paste_patch(patch, frame, top, left, crop_h, crop_w):
     """patch: fp32 [3, hs, ws] RGB in [-1, 1]; frame: uint8 [H, W, 3] BGR (written in place)."""
     lib = _lib.load()
