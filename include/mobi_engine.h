@@ -56,7 +56,8 @@ extern "C" {
  *      training splits' data side, mobi_ref_augment (mobi_ref_augment_params 28) and mobi_drop_context (no struct); likewise the checkpoint
  *      snapshot over the pair tables, mobi_snapshot_multi (mobi_snapshot_record 29); likewise the image logger's picture launch,
  *      mobi_image_grid (mobi_image_grid_source 30); likewise the test bench's camera pictures, mobi_camera_export
- *      (mobi_camera_export_params 31) */
+ *      (mobi_camera_export_params 31); likewise the one launch that refreshes every trained weight's 16-bit images,
+ *      mobi_repack_multi (mobi_repack_entry 32) */
 #define MOBI_ABI_VERSION 6
 
 enum { MOBI_OK = 0, MOBI_ERR_ARG = -1, MOBI_ERR_UNSUPPORTED = -2, MOBI_ERR_LAUNCH = -3, MOBI_ERR_ALIGN = -4 };
@@ -70,7 +71,7 @@ const char* mobi_error_string(int code);
  * 8 ddim_step, 9 two_key_adapter, 10 range_paste, 11 lidar_metrics, 12 range_prepare, 13 image_prepare, 14 ff_geglu,
  * 15 row_chain, 16 chain_op, 17 layernorm_bwd, 18 attention_bwd, 19 split_source, 20 dpm_step, 21 lpips_distance,
  * 22 image_normalize, 23 mt_tensor, 24 mt_chunk, 25 grad_stats_record, 26 mt_pair, 27 loss_grad, 28 ref_augment, 29 snapshot_record,
- * 30 image_grid_source, 31 camera_export.
+ * 30 image_grid_source, 31 camera_export, 32 repack_entry.
  * Returns 0 for an unknown id. */
 size_t mobi_struct_size(int id);
 /* Development hook: the library reads its MOBI_* A/B environment variables once, at the first launch
@@ -514,6 +515,28 @@ int mobi_accum_multi(const mobi_mt_pair* pairs, int32_t n_pairs, const mobi_mt_c
 typedef struct mobi_snapshot_record { uint64_t digest; int32_t nonfinite; int32_t reserved; } mobi_snapshot_record;
 int mobi_snapshot_multi(const mobi_mt_pair* pairs, int32_t n_pairs, const mobi_mt_chunk* chunks, int32_t n_chunks,
                         void* workspace, mobi_snapshot_record* out, void* stream);
+
+/* The weight refresh of a training step: one launch writes the 16-bit images of EVERY listed fp32 master weight, instead of a
+ * cast, an allocation and a mobi_tile_weights launch per tensor and image after each optimizer update (ops.pack_linear,
+ * train._packed_t).  `entries` and `tiles` are DEVICE-resident, like the tables above.  tiles[i] = {offset = index of a 64 x 64
+ * tile in row-major order over ceil(n / 64) x ceil(k / 64), tensor}, in any order; one 256-thread block per tile; a tile that does
+ * not lie inside its tensor is skipped, edge tiles are partial.  The only arithmetic is ONE rounding of fp32 to the storage type,
+ * round to nearest even as torch's .to(float16 / bfloat16) (fp16 overflow -> +-inf, subnormals and -0 kept); everything else is
+ * placement.  The tiled images follow mobi_tile_weights' index map (destination chunk ((p steps + s) 16 + r) 4 + slot holds
+ * source chunk slot ^ P[(r >> 2) & 3], P = {0, 2, 3, 1}).  Destinations are 16-byte aligned where the 16-byte store paths apply
+ * (w: k % 8 == 0, w_t: n % 8 == 0); other shapes, and a src off the 16-byte grid, are moved element by element.  A wt / wt_t whose
+ * shape condition does not hold is not written.  No atomics, no workspace.  NULL tables, non-positive counts or a dtype that is
+ * neither MOBI_F16 nor MOBI_BF16: MOBI_ERR_ARG before anything is enqueued.  Addition to ABI 6 (struct id 32). */
+typedef struct mobi_repack_entry {
+  const float* src;        /* fp32 master, dense [n][k] */
+  void* w;                 /* T [n][k]            = round(src)                      or NULL */
+  void* wt;                /* tiled image of w    ([n/16][k/32] 1-KiB blocks)       or NULL; needs n % 16 == 0, k % 32 == 0 */
+  void* w_t;               /* T [k][n]            = round(src) transposed           or NULL */
+  void* wt_t;              /* tiled image of w_t                                    or NULL; needs k % 16 == 0, n % 32 == 0 */
+  int32_t n, k;
+} mobi_repack_entry;
+int mobi_repack_multi(const mobi_repack_entry* entries, int32_t n_entries, const mobi_mt_chunk* tiles, int32_t n_tiles,
+                      int32_t dtype, void* stream);
 
 typedef struct mobi_attention_bwd_params {
   const void* q; int64_t q_img_stride, q_row_stride;       /* T [image][tq][>= heads*dh], strides in elements */

@@ -198,6 +198,10 @@ class SnapshotRecord(C.Structure):
     _fields_ = [("digest", C.c_uint64), ("nonfinite", i32), ("reserved", i32)]
 
 
+class RepackEntry(C.Structure):
+    _fields_ = [("src", vp), ("w", vp), ("wt", vp), ("w_t", vp), ("wt_t", vp), ("n", i32), ("k", i32)]
+
+
 LOSS_L2, LOSS_L1 = 0, 1           # mobi_loss_grad's loss_type
 
 
@@ -233,7 +237,7 @@ STRUCT_IDS = {0: IgemmParams, 1: GroupNormParams, 2: LayerNormParams, 3: Attenti
               17: LayerNormBwdParams, 18: AttentionBwdParams, 19: SplitSource, 20: DpmStepParams,
               21: LpipsDistanceParams, 22: ImageNormalizeParams, 23: MtTensor, 24: MtChunk, 25: GradStatsRecord,
               26: MtPair, 27: LossGradParams, 28: RefAugmentParams, 29: SnapshotRecord, 30: ImageGridSource,
-              31: CameraExportParams}
+              31: CameraExportParams, 32: RepackEntry}
 
 # every symbol include/mobi_engine.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -291,6 +295,7 @@ SYMBOLS = {
     "mobi_ema_multi": (C.c_int, [vp, i32, vp, i32, f32, i32, vp]),
     "mobi_accum_multi": (C.c_int, [vp, i32, vp, i32, f32, i32, vp]),
     "mobi_snapshot_multi": (C.c_int, [vp, i32, vp, i32, vp, vp, vp]),
+    "mobi_repack_multi": (C.c_int, [vp, i32, vp, i32, i32, vp]),
     "mobi_quick_gelu": (C.c_int, [vp, vp, i64, i32, vp]),
     "mobi_timestep_embedding": (C.c_int, [vp, vp, vp, i32, i32, vp]),
     "mobi_conv_small_cin": (C.c_int, [C.POINTER(ConvSmallCinParams), vp]),

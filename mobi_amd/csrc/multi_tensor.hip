@@ -318,6 +318,129 @@ __global__ __launch_bounds__(kMtBlock) void snapshot_multi_kernel(const mobi_mt_
   if (cur >= 0) snapshot_flush(out, cur, s, bad);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Repack: the 16-bit images of every listed fp32 master weight W [n][k] in one launch (mobi_engine.h mobi_repack_multi; what
+// ops.pack_linear / train._packed_t build tensor by tensor after an optimizer update): w = round(W), wt = its 1-KiB request
+// images (tile_weights_kernel's index map), w_t = round(W)^T, wt_t = the images of that.  One rounding (the cast, round to
+// nearest even as torch's .to()), everything else is placement.  One block per 64 x 64 tile of W: 16-byte reads along k,
+// the rounded tile in LDS, then row reads for w / wt and column reads for w_t / wt_t, 16-byte stores.
+// LDS: a row is 32 dwords (64 values) and every 8 rows are followed by 4 dwords of padding, dword (r, d) at
+// 32 r + 4 (r >> 3) + d.
+//   stores  ds_write_b64, 16 lanes = one row = 32 consecutive dwords: conflict-free
+//   rows    ds_read_b128 of (row = idx >> 3, chunk = idx & 7): a wave reads 8 rows of one 8-row group; each 16-lane group of
+//           the instruction holds four half rows, two of even and two of odd rows, one in each 64-byte half: 64 distinct banks
+//           (mod 64)
+//   columns ds_read_b32 of dword kp (two neighbouring k) of rows 8 nc + j, lane = (kp, nc) with nc = lane & 7: a 32-lane half
+//           holds nc = 0..7 and four consecutive kp from a multiple of 4; bank = (32 row + 4 nc + kp) mod 32 = 4 nc + kp - kp0:
+//           32 distinct banks.  (Without the padding the eight nc would meet on four banks.)  One thread turns its 8 dwords
+//           into the two 16-byte chunks w_t[k][8 nc ..] and w_t[k + 1][8 nc ..]: 8 lanes write 128 contiguous bytes.
+// Shapes the 16-byte paths cannot take (k % 8 / n % 8 non-zero, a source off the 16-byte grid) go element by element.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int kRpTile = 64;
+constexpr int kRpLdsDwords = kRpTile * 32 + (kRpTile / 8) * 4;
+
+__device__ __forceinline__ int rp_lds(int r, int d) { return r * 32 + (r >> 3) * 4 + d; }
+
+// chunk (row R, 16-byte chunk kc of that row) of a matrix of `steps` 32-deep steps -> its chunk index in the tiled image
+__device__ __forceinline__ long long rp_tiled_chunk(int R, int kc, int steps) {
+  const int rr = R & 15, perm = (0x1320 >> (4 * ((rr >> 2) & 3))) & 3;          // P[(r >> 2) & 3] of {0, 2, 3, 1}
+  return (((long long)(R >> 4) * steps + (kc >> 2)) * 16 + rr) * 4 + ((kc & 3) ^ perm);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kMtBlock) void repack_multi_kernel(const mobi_repack_entry* __restrict__ entries, int n_entries,
+                                                                const mobi_mt_chunk* __restrict__ tiles) {
+  __shared__ __attribute__((aligned(16))) uint32_t lds[kRpLdsDwords];
+  const int tid = threadIdx.x;
+  const mobi_mt_chunk tl = tiles[blockIdx.x];
+  if (tl.tensor < 0 || tl.tensor >= n_entries) return;
+  const mobi_repack_entry e = entries[tl.tensor];
+  const int n = e.n, k = e.k;
+  if (!e.src || n <= 0 || k <= 0) return;
+  const long long tk = (k + kRpTile - 1) / kRpTile, tn = (n + kRpTile - 1) / kRpTile;
+  if (tl.offset < 0 || tl.offset >= tn * tk) return;                             // (all returns above are block-uniform)
+  const int n0 = (int)(tl.offset / tk) * kRpTile, k0 = (int)(tl.offset % tk) * kRpTile;
+  const float* __restrict__ src = e.src;
+
+  // fp32 tile -> rounded tile in LDS; what lies outside the tensor is written as zero and never stored
+  const bool vld = !(k & 3) && !(reinterpret_cast<uintptr_t>(src) & 15);
+  f32x4 v[4];
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int idx = it * kMtBlock + tid, gr = n0 + (idx >> 4), gc = k0 + 4 * (idx & 15);
+    v[it] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (gr < n && gc < k) {
+      const float* p = src + (long long)gr * k + gc;
+      if (vld) {
+        v[it] = *reinterpret_cast<const f32x4*>(p);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (gc + j < k) v[it][j] = p[j];
+      }
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int idx = it * kMtBlock + tid;
+    const float f[4] = {v[it][0], v[it][1], v[it][2], v[it][3]};
+    *reinterpret_cast<u32x2*>(&lds[rp_lds(idx >> 4, 2 * (idx & 15))]) = pack4<T>(f);
+  }
+  __syncthreads();
+  const uint16_t* lds16 = reinterpret_cast<const uint16_t*>(lds);
+
+  // rows: w and wt
+  uint16_t* __restrict__ w = static_cast<uint16_t*>(e.w);
+  u32x4* __restrict__ wt = !(n & 15) && !(k & 31) ? static_cast<u32x4*>(e.wt) : nullptr;
+  if (!(k & 7)) {
+    if (w || wt) {
+#pragma unroll
+      for (int it = 0; it < 2; ++it) {
+        const int idx = it * kMtBlock + tid, r = idx >> 3, c8 = idx & 7, gr = n0 + r, gc = k0 + 8 * c8;
+        if (gr < n && gc < k) {
+          const u32x4 q = *reinterpret_cast<const u32x4*>(&lds[rp_lds(r, 4 * c8)]);
+          if (w) st16(w + (long long)gr * k + gc, q);
+          if (wt) wt[rp_tiled_chunk(gr, gc >> 3, k >> 5)] = q;
+        }
+      }
+    }
+  } else if (w) {
+    for (int i = tid; i < kRpTile * kRpTile; i += kMtBlock) {
+      const int r = i >> 6, c = i & 63;
+      if (n0 + r < n && k0 + c < k) w[(long long)(n0 + r) * k + k0 + c] = lds16[2 * rp_lds(r, 0) + c];
+    }
+  }
+
+  // columns: w_t and wt_t (the matrix [k][n])
+  uint16_t* __restrict__ w_t = static_cast<uint16_t*>(e.w_t);
+  u32x4* __restrict__ wt_t = !(k & 15) && !(n & 31) ? static_cast<u32x4*>(e.wt_t) : nullptr;
+  if (!(n & 7)) {
+    const int nc = tid & 7, kp = tid >> 3, gn = n0 + 8 * nc, gk = k0 + 2 * kp;
+    if ((w_t || wt_t) && gn < n && gk < k) {
+      uint32_t d[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) d[j] = lds[rp_lds(8 * nc + j, kp)];
+      u32x4 lo, hi;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        lo[j] = (d[2 * j] & 0xffffu) | (d[2 * j + 1] << 16);
+        hi[j] = (d[2 * j] >> 16) | (d[2 * j + 1] & 0xffff0000u);
+      }
+      if (w_t) st16(w_t + (long long)gk * n + gn, lo);
+      if (wt_t) wt_t[rp_tiled_chunk(gk, gn >> 3, n >> 5)] = lo;
+      if (gk + 1 < k) {
+        if (w_t) st16(w_t + (long long)(gk + 1) * n + gn, hi);
+        if (wt_t) wt_t[rp_tiled_chunk(gk + 1, gn >> 3, n >> 5)] = hi;
+      }
+    }
+  } else if (w_t) {
+    for (int i = tid; i < kRpTile * kRpTile; i += kMtBlock) {
+      const int c = i >> 6, r = i & 63;
+      if (n0 + r < n && k0 + c < k) w_t[(long long)(k0 + c) * n + n0 + r] = lds16[2 * rp_lds(r, 0) + c];
+    }
+  }
+}
+
 static int mt_grid(int n_chunks) {
   static int cus = 0;
   if (!cus) {
@@ -400,6 +523,20 @@ extern "C" int mobi_snapshot_multi(const mobi_mt_pair* pairs, int32_t n_pairs, c
   if (reinterpret_cast<uintptr_t>(out) & 7) return MOBI_ERR_ALIGN;
   if (hipMemsetAsync(out, 0, (size_t)n_pairs * sizeof(mobi_snapshot_record), ST(stream)) != hipSuccess) return MOBI_ERR_LAUNCH;
   hipLaunchKernelGGL(snapshot_multi_kernel, dim3(mt_grid(n_chunks)), dim3(kMtBlock), 0, ST(stream), pairs, n_pairs, chunks, n_chunks, out);
+  MOBI_CHECK_LAUNCH();
+  return MOBI_OK;
+}
+
+extern "C" int mobi_repack_multi(const mobi_repack_entry* entries, int32_t n_entries, const mobi_mt_chunk* tiles, int32_t n_tiles,
+                                 int32_t dtype, void* stream) {
+  if (!entries || !tiles || n_entries <= 0 || n_tiles <= 0) return MOBI_ERR_ARG;
+  if (dtype == MOBI_F16) {
+    hipLaunchKernelGGL(repack_multi_kernel<f16_t>, dim3((unsigned)n_tiles), dim3(kMtBlock), 0, ST(stream), entries, n_entries, tiles);
+  } else if (dtype == MOBI_BF16) {
+    hipLaunchKernelGGL(repack_multi_kernel<bf16_t>, dim3((unsigned)n_tiles), dim3(kMtBlock), 0, ST(stream), entries, n_entries, tiles);
+  } else {
+    return MOBI_ERR_ARG;
+  }
   MOBI_CHECK_LAUNCH();
   return MOBI_OK;
 }

@@ -280,6 +280,7 @@ extern "C" size_t mobi_struct_size(int id) {
     case 29: return sizeof(mobi_snapshot_record);
     case 30: return sizeof(mobi_image_grid_source);
     case 31: return sizeof(mobi_camera_export_params);
+    case 32: return sizeof(mobi_repack_entry);
     default: return 0;
   }
 }

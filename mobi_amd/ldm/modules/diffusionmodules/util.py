@@ -126,9 +126,18 @@ class _Holder(nn.Module):
         WEIGHTS_EPOCH[0] += 1
         return super()._load_from_state_dict(*args, **kwargs)
 
-    def _cached(self, tag, build):
+    def _cache_key(self, tag):
         ps = list(self.parameters(recurse=False))
-        key = (tag, engine_dtype(), ps[0].device, tuple(p._version for p in ps), tuple(p.data_ptr() for p in ps))
+        return (tag, engine_dtype(), ps[0].device, tuple(p._version for p in ps), tuple(p.data_ptr() for p in ps))
+
+    def _install(self, tag, value):
+        """`value` becomes the cached copy under `tag` for the parameters as they are NOW (somebody else built it: the one launch
+        of `train.WeightRefresher`): the next `_cached(tag, ...)` is a hit until a version, an address or the engine dtype moves."""
+        self.__dict__.setdefault("_pack_cache", {})[tag] = (self._cache_key(tag), value)
+        return value
+
+    def _cached(self, tag, build):
+        key = self._cache_key(tag)
         cache = self.__dict__.setdefault("_pack_cache", {})
         hit = cache.get(tag)
         if hit is None or hit[0] != key:

@@ -10,7 +10,7 @@ import torch
 def get_obj_from_str(string, reload=False):
     """`target:` strings written for the reference (`ldm.…`) resolve to this package."""
     module, cls = string.rsplit(".", 1)
-    if module == "ldm" or module.startswith("ldm."):
+    if module == "ldm" or module.startswith("ldm.") or module == "main":       # (`data.target: main.DataModuleFromConfig`)
         module = "mobi_amd." + module
     mod = importlib.import_module(module)
     if reload:
@@ -57,9 +57,29 @@ _INTERP = re.compile(r"\$\{([^}]+)\}")
 def load_config(path, overrides=None):
     """YAML + `${key.sub}` interpolation + dot-list overrides (`a.b=1`), the subset of
     OmegaConf the reference's configs and harness use (inference_test_bench.py:339-341)."""
+    return load_configs([path], overrides)[0]
+
+
+def merge_config(into, other):
+    """OmegaConf.merge's rule for plain trees, in place on `into`: dicts merge key by key, anything else is replaced."""
+    for k, v in other.items():
+        if isinstance(v, dict) and isinstance(into.get(k), dict):
+            merge_config(into[k], v)
+        else:
+            into[k] = v
+    return into
+
+
+def load_configs(paths, overrides=None):
+    """Several YAML files merged left to right (`merge_config`), then the dot-list overrides -> (resolved, raw): `raw` is the
+    merged tree BEFORE `${}` resolution -- what the training command saves, so that a resumed run with another override resolves
+    anew (main.py:503-505 of the reference) -- and `resolved` what `load_config` returns."""
+    import copy
     import yaml
-    with open(path) as f:
-        cfg = yaml.safe_load(f)
+    cfg = {}
+    for path in paths:
+        with open(path) as f:
+            merge_config(cfg, yaml.safe_load(f) or {})
     for item in overrides or []:
         key, val = item.split("=", 1)
         node = cfg
@@ -67,7 +87,11 @@ def load_config(path, overrides=None):
         for p in parts[:-1]:
             node = node.setdefault(p, {})
         node[parts[-1]] = yaml.safe_load(val)
+    return resolve_config(cfg), copy.deepcopy(cfg)
 
+
+def resolve_config(cfg):
+    """`cfg` with every `${key.sub}` replaced by the value it names (a new tree)."""
     def lookup(key):
         node = cfg
         for p in key.split("."):

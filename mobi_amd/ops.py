@@ -773,6 +773,83 @@ def read_snapshot_records(rec):
     return [(int(d) & 0xffffffffffffffff, bool(int(f) & 0xffffffff)) for d, f in host]
 
 
+REPACK_TILE = 64     # mobi_repack_multi's tile edge
+
+
+def repack_tile_map(shapes):
+    """The tile map of a list of [n, k] shapes, in `multi_tensor_chunk_map`'s record format: entry i cut into
+    ceil(n / 64) x ceil(k / 64) tiles, offset = the tile's row-major index, in order."""
+    t = REPACK_TILE
+    return multi_tensor_chunk_map([((n + t - 1) // t) * ((k + t - 1) // t) for n, k in shapes], chunk=1)
+
+
+class RepackTable:
+    """The device-resident tables of `repack_multi` and the persistent 16-bit images it writes.  items: [(src, want_forward,
+    want_transposed)], src a dense fp32 [n, k] master on one device; want_forward: `w` = round(src) and its tiled image `wt`
+    ("cast": `w` alone, what `Linear.skinny()` reads); want_transposed: `w_t` = round(src)^T and its tiled image `wt_t`.  A tiled
+    image exists exactly where `tile_weights` would return one (wt: n % 16 == 0 and k % 32 == 0; wt_t: k % 16 == 0 and
+    n % 32 == 0), the entry holds NULL otherwise.  All images live in ONE flat allocation (`buffer`), each on a 16-byte boundary
+    with `guard` elements (rounded up to 8) in front of the first, between neighbours and behind the last; `images[i]` is
+    {"w", "wt", "w_t", "wt_t"} -> the image's view of the buffer or None, `spans` the (start, stop) element ranges.  Entries
+    and the tile map (`repack_tile_map`'s, or `tile_map`: the caller's own in its format) are uploaded once; `ptrs` (the
+    sources' addresses) is what a caller compares to notice that a parameter moved."""
+
+    def __init__(self, items, dtype, guard=0, tile_map=None):
+        import numpy as np
+        _dt(dtype)
+        items = list(items)
+        if not items:
+            raise ValueError("RepackTable: no tensors")
+        self.device, self.dtype, self.count = items[0][0].device, dtype, len(items)
+        for src, _, _ in items:
+            if src.dtype != torch.float32:
+                raise ValueError(f"RepackTable: a master of type {src.dtype} where fp32 is read")
+            if src.dim() != 2 or not src.is_contiguous() or src.numel() == 0:
+                raise ValueError(f"RepackTable: a master must be a dense, non-empty [n, k] tensor, got shape {tuple(src.shape)} "
+                                 f"strides {tuple(src.stride())}")
+            if not src.is_cuda or src.device != self.device:
+                raise ValueError(f"RepackTable: a master on {src.device} in a table on {self.device}")
+        self.shapes = [tuple(src.shape) for src, _, _ in items]
+        guard = (int(guard) + 7) // 8 * 8
+        at, plan = guard, []
+        for (n, k), (_, fwd, tr) in zip(self.shapes, items):
+            want = {"w": bool(fwd), "wt": bool(fwd) and fwd != "cast" and n % 16 == 0 and k % 32 == 0,
+                    "w_t": bool(tr), "wt_t": bool(tr) and k % 16 == 0 and n % 32 == 0}
+            where = {}
+            for name, on in want.items():
+                if on:
+                    where[name] = at
+                    at += (n * k + 7) // 8 * 8 + guard
+            plan.append(where)
+        self.buffer = torch.zeros(max(at, 8), dtype=dtype, device=self.device)
+        assert self.buffer.data_ptr() % 16 == 0
+        view = {"w": lambda n, k: (n, k), "wt": lambda n, k: (n // 16, k // 32, 16, 4, 8),
+                "w_t": lambda n, k: (k, n), "wt_t": lambda n, k: (k // 16, n // 32, 16, 4, 8)}
+        self.images, self.spans = [], []
+        entries = np.zeros(self.count, dtype=np.dtype([("src", "<u8"), ("w", "<u8"), ("wt", "<u8"), ("w_t", "<u8"), ("wt_t", "<u8"),
+                                                       ("n", "<i4"), ("k", "<i4")]))
+        assert entries.dtype.itemsize == C.sizeof(_lib.RepackEntry)
+        base = self.buffer.data_ptr()
+        for i, ((n, k), where) in enumerate(zip(self.shapes, plan)):
+            self.images.append({name: self.buffer[where[name]:where[name] + n * k].view(view[name](n, k)) if name in where else None
+                                for name in view})
+            self.spans += [(off, off + n * k) for off in where.values()]
+            entries[i] = (items[i][0].data_ptr(), *[base + 2 * where[name] if name in where else 0 for name in view], n, k)
+        self._keep = [src for src, _, _ in items]
+        self.ptrs = tuple(src.data_ptr() for src in self._keep)
+        tmap = repack_tile_map(self.shapes) if tile_map is None else tile_map
+        self.n_tiles = len(tmap)
+        self.entries = torch.from_numpy(entries.view(np.uint8)).to(self.device)        # (blocking copies, once)
+        self.tiles = torch.from_numpy(tmap.view(np.uint8)).to(self.device)
+
+
+def repack_multi(table):
+    """Every image of `table` (a RepackTable) from its fp32 master, one launch on the current stream: one rounding to the
+    table's storage type (as torch's `.to()`), the rest is placement (`mobi_repack_multi`)."""
+    _lib.check(_lib.load().mobi_repack_multi(_ptr(table.entries), table.count, _ptr(table.tiles), table.n_tiles, _dt(table.dtype),
+                                             _stream()), "mobi_repack_multi")
+
+
 def geglu_fwd(pre):
     """pre: T [..., 2 inner] = [value | gate] dense -> value * gelu_erf(gate): T [..., inner]."""
     lib = _lib.load()

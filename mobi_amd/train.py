@@ -48,6 +48,68 @@ def _packed_t(lin):
     return c["val"]
 
 
+# `block_backward` sends the data gradient of the bbox adapter's to_k / to_v (a handful of context rows) through fp32 chains
+# on the master weight: their `_packed_t` is never read
+_NO_PACKED_T = ("cond_adapter_attn.to_k", "cond_adapter_attn.to_v")
+
+
+class WeightRefresher:
+    """The 16-bit copies of every trained Linear weight, rebuilt by ONE launch after an optimizer update (`mobi_repack_multi`)
+    instead of lazily, tensor by tensor, by the next forward / backward (`ops.pack_linear`, `_packed_t`: a cast, an allocation
+    and a `mobi_tile_weights` launch each, twice per layer).  names: the parameter names an optimizer steps, relative to `model`.
+    Of those, every `Linear` weight is listed with the copies the training step reads: inside a `BBoxEmbedder` the cast alone
+    (`Linear.skinny()`), elsewhere `Linear.packed()` (w, wt, the fp32 bias alias) and `_packed_t` (the transposed pair; not for
+    `_NO_PACKED_T`, whose data gradient never reads one).
+    `refresh()` launches on the current stream and then re-keys the layers' caches (`_Holder._install`, the `_packed_t` dict) on
+    the parameters' current versions: the next `packed()` / `_packed_t()` is a hit that returns `ops.Packed` objects over the
+    table's persistent buffers.  The table is rebuilt when the engine dtype or a parameter's address has moved.  A cache
+    something else invalidates later (an `ema_scope` swap) is rebuilt lazily by the old path and re-installed at the next
+    `refresh()`; the sampling path's folded tables are not touched."""
+
+    def __init__(self, model, names):
+        from .ldm.modules.diffusionmodules.util import Linear
+        from .ldm.modules.encoders.modules import BBoxEmbedder
+        skinny = {id(m) for e in model.modules() if isinstance(e, BBoxEmbedder) for m in e.modules()}
+        self.layers = []                              # (Linear, "mfma" | "forward" | "skinny")
+        for name in names:
+            prefix, _, leaf = name.rpartition(".")
+            if leaf != "weight" or not prefix:
+                continue
+            mod = model.get_submodule(prefix)
+            if isinstance(mod, Linear):
+                kind = "skinny" if id(mod) in skinny else "forward" if prefix.endswith(_NO_PACKED_T) else "mfma"
+                self.layers.append((mod, kind))
+        self.table = self._key = None
+        self.launches = 0
+
+    def _now(self):
+        return (engine_dtype(),) + tuple(m.weight.data_ptr() for m, _ in self.layers)
+
+    def refresh(self):
+        if not self.layers:
+            return
+        key = self._now()
+        if self.table is None or key != self._key:
+            want = {"mfma": (True, True), "forward": (True, False), "skinny": ("cast", False)}
+            self.table = ops.RepackTable([(m.weight.data, *want[kind]) for m, kind in self.layers], engine_dtype())
+            self._key = key
+        ops.repack_multi(self.table)
+        self.launches += 1
+        dt = engine_dtype()
+        for (m, kind), im in zip(self.layers, self.table.images):
+            w = m.weight
+            b = None if m.bias is None else m.bias.detach().float().contiguous()
+            if kind == "skinny":
+                m._install("skinny", (im["w"], b))
+                continue
+            n, k = w.shape
+            m._install("mfma", Packed(im["w"], b, 1, 1, k, n, n, wt=im["wt"]))
+            if kind == "forward":
+                continue
+            c = m.__dict__.setdefault("_packed_t", {})
+            c["key"], c["val"] = (w._version, w.data_ptr(), dt), Packed(im["w_t"], None, 1, 1, n, k, k, wt=im["wt_t"])
+
+
 def _rows(t):
     return t.reshape(-1, t.shape[-1])
 
@@ -540,8 +602,9 @@ class AdamW:
         self.state, self.steps = {}, 0
         self._multi = _TableCache()                   # step_scaled's tables, per set of names that had a gradient (built lazily)
 
-    def step(self, grads):
-        """grads: {name: fp32 tensor}; names without an entry are left alone."""
+    def step(self, grads, refresh=None):
+        """grads: {name: fp32 tensor}; names without an entry are left alone.  refresh: a `WeightRefresher`, called after the
+        update (None: the 16-bit copies are rebuilt lazily, as ever)."""
         self.steps += 1
         stepped = {name: p for name, p in self.params.items() if name in grads}
         for name, p in stepped.items():
@@ -549,6 +612,8 @@ class AdamW:
             ops.adamw_step(p.data, grads[name].reshape(p.shape).contiguous(), st[0], st[1], self.steps, self.lr, self.betas, self.eps,
                            self.weight_decay)
         weights_changed(stepped.values())
+        if refresh is not None:
+            refresh.refresh()
         return self
 
     def state_dict(self):
@@ -608,14 +673,15 @@ class AdamW:
         self.lr, self.betas = float(group["lr"]), tuple(float(b) for b in group["betas"])
         self.eps, self.weight_decay = float(group["eps"]), float(group["weight_decay"])
 
-    def step_scaled(self, grads, scaler=None, max_norm=None):
+    def step_scaled(self, grads, scaler=None, max_norm=None, refresh=None):
         """`step()` for gradients that are still multiplied by `scaler.scale` (`training_step(..., scaler=s)`), with overflow
         skipping and gradient-norm clipping, in two launches whatever the number of tensors: `mobi_grad_stats` (fp64 sum of squares
         + non-finite flag over every gradient), ONE read-back of its 16-byte record -- the single host sync of a step: it keeps
         `steps`, the bias corrections and the scale on the host, where `step()` keeps them -- then `mobi_adamw_multi` on
         g * clip_coef / scale.  norm = sqrt(sumsq) / scale (host fp64); clip_coef = min(1, max_norm / (norm + 1e-6)) as
         torch.nn.utils.clip_grad_norm_.  A non-finite gradient launches nothing more: `steps`, every parameter and both moments
-        stay as they are and the scaler backs off.  Names without an entry in `grads` are left alone.  -> StepResult."""
+        stay as they are and the scaler backs off.  Names without an entry in `grads` are left alone.  refresh: a `WeightRefresher`,
+        called after an update that took place (a skipped step launches nothing).  -> StepResult."""
         names = tuple(n for n in self.params if n in grads)
         scale = 1.0 if scaler is None else scaler.scale
         if not names:
@@ -638,6 +704,8 @@ class AdamW:
         self.steps += 1
         ops.adamw_multi(mt, clip / scale, self.steps, self.lr, self.betas, self.eps, self.weight_decay)
         weights_changed(self.params[n] for n in names)
+        if refresh is not None:
+            refresh.refresh()
         if scaler is not None:
             scaler.update(False)
         return StepResult(False, norm, clip, scale)
@@ -712,8 +780,8 @@ class GradAccumulator:
             raise ValueError(f"a GradAccumulator has no state between windows, got keys {sorted(sd)[:4]}")
         self._clear()
 
-    def step(self, scaler=None, max_norm=None):
-        """The optimizer step of the window: `optimizer.step_scaled` on the accumulators of every tensor some rank saw (a tensor
+    def step(self, scaler=None, max_norm=None, refresh=None):
+        """The optimizer step of the window (refresh: handed on to `step_scaled`): `optimizer.step_scaled` on the accumulators of every tensor some rank saw (a tensor
         nobody saw is left out and so left alone -- no weight decay, no decay of its moments), after the one collective of the
         window where there is more than one process.  The window is cleared whether or not the step was skipped.  -> StepResult."""
         from . import dist as mdist
@@ -724,7 +792,7 @@ class GradAccumulator:
             raise ValueError(f"the window's gradients carry the loss scale {self._scale!r}, the step would divide by {want!r}")
         try:
             present = mdist.allreduce_accumulated(self.buckets, self.layout, self._seen)
-            return self.optimizer.step_scaled({k: self.views[k] for k in present}, scaler=scaler, max_norm=max_norm)
+            return self.optimizer.step_scaled({k: self.views[k] for k in present}, scaler=scaler, max_norm=max_norm, refresh=refresh)
         finally:
             self._clear()
 
@@ -908,10 +976,15 @@ class Trainer:
     `image_logger` (an `ImageLogger`) is called after every optimizer step (`on_train_batch_end(self, model, batch, i)`, once
     `global_step` has moved; in an accumulation window after the window's step only) and after every `validation_step`; the rows it
     returns go to `image_history`.  `log_dir`: every row of `history`, `val_history` and `image_history` is also appended to
-    `log_dir/metrics.jsonl` as it is made.  `current_epoch` is the epoch `fit` is in.  With neither, nothing changes."""
+    `log_dir/metrics.jsonl` as it is made.  `current_epoch` is the epoch `fit` is in.  With neither, nothing changes.
+
+    `refresh_weights`: every optimizer step ends with one `WeightRefresher.refresh()` over the optimizer's tensors (the same
+    numbers; off by default).  `request_save()` asks for a `last.ckpt` after the optimizer step in progress (it only sets a flag:
+    safe to call from a signal handler)."""
 
     def __init__(self, model, max_epochs, accumulate_grad_batches=1, max_norm=None, scaler=None, ckpt_dir=None, every_n_steps=None,
-                 save_top_k=3, seed=0, log_every=50, max_steps=None, image_logger=None, log_dir=None):
+                 save_top_k=3, seed=0, log_every=50, max_steps=None, image_logger=None, log_dir=None, refresh_weights=False):
+        self.refresh_weights, self.refresher, self._save_requested = bool(refresh_weights), None, False
         self.image_logger, self.log_dir, self.image_history, self.current_epoch = image_logger, log_dir, [], 0
         self.model, self.max_epochs, self.accumulate = model, int(max_epochs), int(accumulate_grad_batches)
         self.max_norm, self.scaler, self.ckpt_dir, self.every_n_steps = max_norm, scaler, ckpt_dir, every_n_steps
@@ -957,6 +1030,9 @@ class Trainer:
         self._pending = []
 
     # -- checkpoints
+    def request_save(self):
+        self._save_requested = True
+
     def _save(self, name, epoch, batch_in_epoch):
         import os
         from . import dist as mdist
@@ -1028,6 +1104,8 @@ class Trainer:
         made = model.configure_optimizers()
         self.optimizer, self.scheduler = (made[0][0], made[1][0]["scheduler"]) if isinstance(made, tuple) else (made, None)
         self.accumulator = GradAccumulator(self.optimizer, k) if k > 1 else None
+        self.refresher = WeightRefresher(model, list(self.optimizer.params)) if self.refresh_weights else None
+        refresh = {} if self.refresher is None else {"refresh": self.refresher}      # (off: the calls are what they always were)
         self.checkpointer = checkpoint.Checkpointer(model, self.optimizer, self.scheduler, self.scaler, self.accumulator)
         if self.ckpt_dir is not None:
             os.makedirs(self.ckpt_dir, exist_ok=True)
@@ -1055,9 +1133,9 @@ class Trainer:
                     if (i + 1) % k:
                         self._pending.pop()            # (a row of the log is an optimizer step: the window's last micro-batch)
                         continue
-                    self.accumulator.step(scaler=self.scaler, max_norm=self.max_norm)
+                    self.accumulator.step(scaler=self.scaler, max_norm=self.max_norm, **refresh)
                 else:
-                    self.optimizer.step_scaled(model.adapter_grads, scaler=self.scaler, max_norm=self.max_norm)
+                    self.optimizer.step_scaled(model.adapter_grads, scaler=self.scaler, max_norm=self.max_norm, **refresh)
                 model.on_train_batch_end()
                 if self.scheduler is not None:
                     self.scheduler.step()
@@ -1065,7 +1143,9 @@ class Trainer:
                 self._log_images("on_train_batch_end", batch, i)       # (in a window: after its optimizer step only)
                 if len(self._pending) >= self.log_every:
                     self._flush_log()
-                if self.every_n_steps and self.ckpt_dir is not None and self.global_step % self.every_n_steps == 0:
+                due = bool(self.every_n_steps) and self.global_step % self.every_n_steps == 0
+                if (due or self._save_requested) and self.ckpt_dir is not None:
+                    self._save_requested = False
                     self._save("last.ckpt", epoch, i + 1)
             if done():
                 break

@@ -2,7 +2,7 @@
 """Time one training step of the adapter parameters (mobi_amd/train.py: forward with a tape + the backward pass through the
 whole UNet + AdamW on the 432 adapter tensors) -- informational: the backward kernels are a first slice, not tuned.
 
-    python tools/train_bench.py [--mc 320] [--side 32] [--n 4] [--dtype bf16] [--iters 3] [--scaler] [--ema] [--accumulate K]
+    python tools/train_bench.py [--mc 320] [--side 32] [--n 4] [--dtype bf16] [--iters 3] [--scaler] [--ema] [--accumulate K] [--refresh]
 
 --scaler: the gradients stay multiplied by a `train.GradScaler`'s scale and `AdamW.step_scaled` (two multi-tensor launches + one
 read-back) replaces the per-tensor unscale and update launches; `--max-norm` adds gradient-norm clipping to it.
@@ -10,7 +10,9 @@ read-back) replaces the per-tensor unscale and update launches; `--max-norm` add
 keeps) and their update inside the timed step, after the optimizer's (what `on_train_batch_end` calls: one `mobi_ema_multi` launch).
 --accumulate K: a timed iteration is K forward / backward passes, each added to a `train.GradAccumulator` (one `mobi_accum_multi`
 launch), plus ONE optimizer step on the accumulated mean (`GradAccumulator.step` -> `AdamW.step_scaled`); the time printed is per
-optimizer step."""
+optimizer step.
+--refresh: every optimizer step ends with one `train.WeightRefresher.refresh()` (`mobi_repack_multi`: the 16-bit copies of the
+trained Linear weights in one launch) instead of the lazy per-tensor re-pack inside the next forward / backward."""
 import argparse
 import math
 import os
@@ -37,6 +39,7 @@ def main():
     ap.add_argument("--max-norm", type=float, default=None)
     ap.add_argument("--ema", action="store_true")
     ap.add_argument("--accumulate", type=int, default=0)
+    ap.add_argument("--refresh", action="store_true")
     a = ap.parse_args()
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float16
     mobi_amd.set_engine_dtype(dt)
@@ -53,6 +56,7 @@ def main():
     noise = W.synth_input("tb.n", (a.n, 4, a.side, a.side)).cuda()
     t = torch.full((a.n,), 500, dtype=torch.long, device="cuda")
     opt = train.AdamW({k: p for k, p in net.named_parameters() if any(m in k for m in train.TRAINABLE_MARKERS)}, lr=1e-5)
+    refresh = train.WeightRefresher(net, list(opt.params)) if a.refresh else None
     ema = None
     if a.ema:
         from mobi_amd.ldm.modules.ema import LitEma
@@ -76,7 +80,7 @@ def main():
                     loss, grads = train.loss_and_gradients(net, x, t, ctx, noise, loss_scale=static)
                 grads.pop("__dcontext__", None)
                 acc.add(grads, scale=1.0 if scaler is None else scaler.scale)
-            acc.step(scaler=scaler, max_norm=a.max_norm)
+            acc.step(scaler=scaler, max_norm=a.max_norm, refresh=refresh)
             if ema is not None:
                 ema(net)
             ops.set_profiler(None)
@@ -84,14 +88,14 @@ def main():
         if scaler is not None:
             loss, grads = train.loss_and_gradients(net, x, t, ctx, noise, loss_scale=scaler.scale, unscale=False)
             grads.pop("__dcontext__", None)
-            opt.step_scaled(grads, scaler=scaler, max_norm=a.max_norm)
+            opt.step_scaled(grads, scaler=scaler, max_norm=a.max_norm, refresh=refresh)
             if ema is not None:
                 ema(net)
             ops.set_profiler(None)
             return loss
         loss, grads = train.loss_and_gradients(net, x, t, ctx, noise, loss_scale=static)
         grads.pop("__dcontext__", None)
-        opt.step(grads)
+        opt.step(grads, refresh=refresh)
         if ema is not None:
             ema(net)
         ops.set_profiler(None)
@@ -115,6 +119,8 @@ def main():
     if acc is not None:
         print(f"--accumulate: {a.accumulate} micro-batches of {a.n} per optimizer step, accumulators {sum(b.numel() for b in acc.buckets) * 4 / 2**30:.2f} GiB "
               f"in {len(acc.buckets)} buckets; the time below is per optimizer step")
+    if refresh is not None:
+        print(f"--refresh: {len(refresh.layers)} layers, {refresh.launches} launches of mobi_repack_multi")
     if scaler is not None:
         print(f"--scaler: loss scale {scaler.scale:g}, max_norm {a.max_norm}")
     print(f"training step, UNet model_channels {a.mc}, latent {a.side}x{a.side}, UNet batch {a.n}, {a.dtype}: {dt_s * 1e3:.1f} ms "
