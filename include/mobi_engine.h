@@ -57,7 +57,8 @@ extern "C" {
  *      snapshot over the pair tables, mobi_snapshot_multi (mobi_snapshot_record 29); likewise the image logger's picture launch,
  *      mobi_image_grid (mobi_image_grid_source 30); likewise the test bench's camera pictures, mobi_camera_export
  *      (mobi_camera_export_params 31); likewise the one launch that refreshes every trained weight's 16-bit images,
- *      mobi_repack_multi (mobi_repack_entry 32) */
+ *      mobi_repack_multi (mobi_repack_entry 32); likewise the test bench's lidar-on-camera overlays, mobi_lidar_overlay +
+ *      mobi_lidar_overlay_workspace_bytes (mobi_lidar_overlay_params 33, mobi_lidar_overlay_picture 34) */
 #define MOBI_ABI_VERSION 6
 
 enum { MOBI_OK = 0, MOBI_ERR_ARG = -1, MOBI_ERR_UNSUPPORTED = -2, MOBI_ERR_LAUNCH = -3, MOBI_ERR_ALIGN = -4 };
@@ -71,7 +72,7 @@ const char* mobi_error_string(int code);
  * 8 ddim_step, 9 two_key_adapter, 10 range_paste, 11 lidar_metrics, 12 range_prepare, 13 image_prepare, 14 ff_geglu,
  * 15 row_chain, 16 chain_op, 17 layernorm_bwd, 18 attention_bwd, 19 split_source, 20 dpm_step, 21 lpips_distance,
  * 22 image_normalize, 23 mt_tensor, 24 mt_chunk, 25 grad_stats_record, 26 mt_pair, 27 loss_grad, 28 ref_augment, 29 snapshot_record,
- * 30 image_grid_source, 31 camera_export, 32 repack_entry.
+ * 30 image_grid_source, 31 camera_export, 32 repack_entry, 33 lidar_overlay, 34 lidar_overlay_picture.
  * Returns 0 for an unknown id. */
 size_t mobi_struct_size(int id);
 /* Development hook: the library reads its MOBI_* A/B environment variables once, at the first launch
@@ -968,6 +969,53 @@ typedef struct mobi_camera_export_params {
   int32_t batch, hs, ws, ref_h, ref_w, H, W, frames;
 } mobi_camera_export_params;
 int mobi_camera_export(const mobi_camera_export_params* p, void* stream);
+
+/* Lidar-on-camera overlays of a whole sampled batch (scripts/inference_test_bench.py, overlay_lidar_on_image and its two calls
+ * per object): a sweep's points projected into a frame and drawn over it, coloured by depth; every picture [H][W][3] uint8 RGB
+ * in ONE buffer.  One clear of the workspace and two launches per 32 pictures, whatever the sweeps hold.  For one picture, all in
+ * fp32 with every operation rounded on its own (no contraction), i the row-major index of a sweep pixel:
+ *   point        d = (depth + 1) / 2 * 54; a point iff 1.4 < d < 54; x = cos(yaw) cos(pitch) d, y = -sin(yaw) cos(pitch) d,
+ *                z = sin(pitch) d (LidarConverter.range2pcd, as mobi_range_paste)
+ *   projection   q = M (x, y, z, 1), each row summed left to right; kept iff q.z > 0 and, with zc = clip(q.z, 1e-5, 1e5),
+ *                u = q.x / zc, v = q.y / zc, 0 <= u < W and 0 <= v < H
+ *   colour       t = (zc - zmin) / (zmax - zmin) over the picture's kept points (0 when zmax == zmin);
+ *                lut[min(int(t * 256), 255)]
+ *   marker       the pixels (floor(u) + dx, floor(v) + dy) with dx^2 + dy^2 <= (point_size / 2)^2 (1, 9 or 21 pixels for
+ *                point_size 1, 3, 5), clipped to the frame; where markers overlap the point with the higher i wins
+ *   frame        under the markers: a MOBI_OVERLAY_FRAME_F32_PLANAR source [3][H][W] in [-1, 1] converted per channel as
+ *                (x + 1) / 2 * 255, clamped to [0, 255], truncated; a MOBI_OVERLAY_FRAME_U8_HWC source [H][W][3] as it is
+ * A picture without a kept point is its frame.  The up to three bytes between a picture's end and the next multiple of 4 are
+ * written 0 (where they lie inside the buffer).  records u32 [n_pictures][4] at out + records_offset: zmin and zmax as fp32
+ * bits (0 without a kept point), the number of kept points, 0.  The result does not depend on the order threads run in.
+ * `pictures` is a HOST array: it is checked here and travels to the device inside the launches' own argument blocks.
+ * 1 <= n_pictures <= 64 (more: MOBI_ERR_UNSUPPORTED; a caller splits); point_size outside {1, 3, 5}: MOBI_ERR_UNSUPPORTED;
+ * a null pointer, an unknown frame_kind, a negative frame_offset, a picture or the records outside [out, out + out_bytes), two
+ * pictures, or a picture and the records, that share a byte (a picture counted up to the next multiple of 4 behind it), a frame
+ * source that shares a byte with [out, out + out_bytes), or workspace_bytes < mobi_lidar_overlay_workspace_bytes(n_pictures, H, W):
+ * MOBI_ERR_ARG; out, an out_offset, records_offset,
+ * frame + frame_offset or a sweep pointer that is not a multiple of 4, or a workspace that is not a multiple of 16:
+ * MOBI_ERR_ALIGN; all before the clear.  A frame source may lie in another call's output (mobi_camera_export's frame picture,
+ * read in place), never in `out` itself.  Matplotlib's resampled figure is not reproduced: the overlay is drawn at the
+ * frame's own resolution; parity with matplotlib unpinned.  Addition to ABI 6 (struct ids 33, 34). */
+enum { MOBI_OVERLAY_FRAME_F32_PLANAR = 0, MOBI_OVERLAY_FRAME_U8_HWC = 1 };
+typedef struct mobi_lidar_overlay_picture {
+  const float* depth; const float* pitch; const float* yaw; /* DEVICE [h0][w0]: the depth code in [-1, 1], radians */
+  const void* frame;                                        /* DEVICE */
+  int64_t frame_offset;                                     /* bytes from `frame` to the frame's first pixel */
+  int64_t out_offset;                                       /* bytes; the picture is [H][W][3] uint8 */
+  float matrix[12];                                         /* rows 0 .. 2 of the 4 x 4 lidar2image */
+  int32_t frame_kind, reserved;
+} mobi_lidar_overlay_picture;
+typedef struct mobi_lidar_overlay_params {
+  const mobi_lidar_overlay_picture* pictures;               /* HOST [n_pictures] */
+  const uint8_t* lut;                                       /* DEVICE [256][3] RGB */
+  uint8_t* out;                                             /* DEVICE */
+  void* workspace;                                          /* DEVICE; cleared here */
+  int64_t out_bytes, records_offset, workspace_bytes;
+  int32_t n_pictures, h0, w0, H, W, point_size;
+} mobi_lidar_overlay_params;
+size_t mobi_lidar_overlay_workspace_bytes(int32_t n_pictures, int32_t H, int32_t W);
+int mobi_lidar_overlay(const mobi_lidar_overlay_params* p, void* stream);
 
 /* ddim.py:145-148 with q_sample (ddpm.py:284-287):
  *   img = (sa[t]*x0 + s1ma[t]*noise) * mask + (1 - mask) * img

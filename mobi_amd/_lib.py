@@ -230,6 +230,20 @@ class CameraExportParams(C.Structure):
                 ("hs", i32), ("ws", i32), ("ref_h", i32), ("ref_w", i32), ("H", i32), ("W", i32), ("frames", i32)]
 
 
+LIDAR_OVERLAY_MAX_PICTURES = 64   # per mobi_lidar_overlay call
+OVERLAY_FRAME_F32_PLANAR, OVERLAY_FRAME_U8_HWC = 0, 1
+
+
+class LidarOverlayPicture(C.Structure):
+    _fields_ = [("depth", vp), ("pitch", vp), ("yaw", vp), ("frame", vp), ("frame_offset", i64), ("out_offset", i64),
+                ("matrix", C.c_float * 12), ("frame_kind", i32), ("reserved", i32)]
+
+
+class LidarOverlayParams(C.Structure):
+    _fields_ = [("pictures", vp), ("lut", vp), ("out", vp), ("workspace", vp), ("out_bytes", i64), ("records_offset", i64),
+                ("workspace_bytes", i64), ("n_pictures", i32), ("h0", i32), ("w0", i32), ("H", i32), ("W", i32), ("point_size", i32)]
+
+
 STRUCT_IDS = {0: IgemmParams, 1: GroupNormParams, 2: LayerNormParams, 3: AttentionParams, 4: CtxAttentionParams,
               5: SkinnyLinearParams, 6: ConvSmallCinParams, 7: ConvSmallCoutParams, 8: DdimStepParams, 9: TwoKeyAdapterParams,
               10: RangePasteParams, 11: LidarMetricsParams, 12: RangePrepareParams, 13: ImagePrepareParams,
@@ -237,7 +251,7 @@ STRUCT_IDS = {0: IgemmParams, 1: GroupNormParams, 2: LayerNormParams, 3: Attenti
               17: LayerNormBwdParams, 18: AttentionBwdParams, 19: SplitSource, 20: DpmStepParams,
               21: LpipsDistanceParams, 22: ImageNormalizeParams, 23: MtTensor, 24: MtChunk, 25: GradStatsRecord,
               26: MtPair, 27: LossGradParams, 28: RefAugmentParams, 29: SnapshotRecord, 30: ImageGridSource,
-              31: CameraExportParams, 32: RepackEntry}
+              31: CameraExportParams, 32: RepackEntry, 33: LidarOverlayParams, 34: LidarOverlayPicture}
 
 # every symbol include/mobi_engine.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -318,6 +332,8 @@ SYMBOLS = {
     "mobi_drop_context": (C.c_int, [vp, vp, vp, vp, i32, i32, i64, vp]),
     "mobi_image_grid": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, vp, i64, vp]),
     "mobi_camera_export": (C.c_int, [C.POINTER(CameraExportParams), vp]),
+    "mobi_lidar_overlay_workspace_bytes": (C.c_size_t, [i32, i32, i32]),
+    "mobi_lidar_overlay": (C.c_int, [C.POINTER(LidarOverlayParams), vp]),
     "mobi_paste_patch": (C.c_int, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
     "mobi_gaussian_blur": (C.c_int, [vp, vp, vp, i32, i32, vp, i32, vp]),
     "mobi_blend_frame": (C.c_int, [vp, vp, vp, vp, i32, i32, vp]),

@@ -911,6 +911,183 @@ __global__ __launch_bounds__(256) void camera_export_kernel(const ce_args a, con
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Lidar-on-camera overlays of a batch (include/mobi_engine.h, mobi_lidar_overlay): a sweep's points projected into a frame and
+// drawn over it as round markers coloured by depth, every picture HWC uint8 in one buffer.  Two launches over a cleared
+// workspace of one u32 key per frame pixel: the splat launch projects every sweep pixel, folds the picture's depth range into
+// its record and leaves `sweep index + 1` under its marker with atomicMax (the higher index wins, as matplotlib paints in array
+// order, whatever the thread order); the resolve launch walks the frame four pixels a lane, converts or copies the frame's
+// pixel where the key is 0 and otherwise projects that point again (the same expressions: the same bits) for its colour.
+// blockIdx.y = the picture; its table entry travels in the launch's argument block.  No FMA contraction in this file.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int LO_MAX_PICTURES = 64, LO_LAUNCH = 32;          // per call; per launch (what fits the argument block)
+constexpr int LO_REC = 4;                                    // u32 per record: ~min bits, max bits, kept count, 0
+struct lo_picture {
+  const float* depth; const float* pitch; const float* yaw;
+  const unsigned char* frame;                                // the frame source with its byte offset added
+  long long out_off;
+  float m[12];
+  int kind, pad;
+};
+struct lo_table { lo_picture p[LO_LAUNCH]; };
+struct lo_args {
+  unsigned* keys; unsigned* rec;                             // of this launch's first picture
+  const unsigned char* lut; unsigned char* out;
+  long long out_bytes, rec_off, key_stride;                  // rec_off: this launch's first record in `out`
+  int h0, w0, H, W, point_size;
+};
+
+// sweep pixel i of picture s -> kept?, the clipped camera depth and the marker's centre pixel
+__device__ __forceinline__ bool lo_project(const lo_picture& s, int i, int H, int W, float& zc, int& px, int& py) {
+  float d = (s.depth[i] + 1.0f) / 2.0f;
+  d = d * 54.0f;
+  if (!(d > 1.4f && d < 54.0f)) return false;                // LidarConverter.range2pcd's validity window
+  const float yaw = s.yaw[i], pitch = s.pitch[i];
+  const float cp = cosf(pitch);
+  const float x = cosf(yaw) * cp * d;
+  const float y = -sinf(yaw) * cp * d;
+  const float z = sinf(pitch) * d;
+  const float qx = s.m[0] * x + s.m[1] * y + s.m[2] * z + s.m[3];
+  const float qy = s.m[4] * x + s.m[5] * y + s.m[6] * z + s.m[7];
+  const float qz = s.m[8] * x + s.m[9] * y + s.m[10] * z + s.m[11];
+  if (!(qz > 0.0f)) return false;
+  zc = qz < 1e-5f ? 1e-5f : (qz > 1e5f ? 1e5f : qz);
+  const float u = qx / zc, v = qy / zc;
+  if (!(u >= 0.0f && u < (float)W && v >= 0.0f && v < (float)H)) return false;
+  px = (int)u, py = (int)v;
+  return true;
+}
+
+__global__ __launch_bounds__(256) void lidar_overlay_splat_kernel(const lo_args a, const lo_table t) {
+  const int p = blockIdx.y;
+  const lo_picture& s = t.p[p];
+  const int n = a.h0 * a.w0, i = blockIdx.x * 256 + threadIdx.x;
+  float zc = 0.f;
+  int px = 0, py = 0;
+  const bool kept = i < n && lo_project(s, i, a.H, a.W, zc, px, py);
+  if (kept) {
+    unsigned* keys = a.keys + (long long)p * a.key_stride;
+    const int r = a.point_size >> 1, d2 = a.point_size * a.point_size;           // dx^2 + dy^2 <= (point_size / 2)^2
+    for (int dy = -r; dy <= r; ++dy) {
+      const int y = py + dy;
+      if (y < 0 || y >= a.H) continue;
+      for (int dx = -r; dx <= r; ++dx) {
+        const int x = px + dx;
+        if (4 * (dx * dx + dy * dy) > d2 || x < 0 || x >= a.W) continue;
+        atomicMax(keys + (long long)y * a.W + x, (unsigned)i + 1u);
+      }
+    }
+  }
+  // zc > 0: its bits order as unsigned integers; the minimum is kept as the maximum of the complement, so that 0 means "none"
+  unsigned lo = kept ? ~__float_as_uint(zc) : 0u, hi = kept ? __float_as_uint(zc) : 0u, cnt = kept ? 1u : 0u;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned l2 = __shfl_xor(lo, o, 64), h2 = __shfl_xor(hi, o, 64);
+    lo = l2 > lo ? l2 : lo, hi = h2 > hi ? h2 : hi, cnt += __shfl_xor(cnt, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0 && cnt) {
+    unsigned* rec = a.rec + p * LO_REC;
+    atomicMax(rec, lo);
+    atomicMax(rec + 1, hi);
+    atomicAdd(rec + 2, cnt);
+  }
+}
+
+// one frame pixel as 0x00BBGGRR: the marker's colour under a key, else the frame's own pixel `under`
+__device__ __forceinline__ unsigned lo_pixel(const lo_args& a, const lo_picture& s, unsigned key, float zmin, float zmax, unsigned under) {
+  if (key == 0u || key > (unsigned)(a.h0 * a.w0)) return under;
+  float zc = 0.f;
+  int px, py;
+  if (!lo_project(s, (int)(key - 1u), a.H, a.W, zc, px, py)) return under;       // (cannot be: the splat launch kept it)
+  float tt = 0.f;
+  if (zmax != zmin) tt = (zc - zmin) / (zmax - zmin);
+  int li = (int)(tt * 256.0f);
+  li = li < 0 ? 0 : (li > 255 ? 255 : li);
+  const unsigned char* c = a.lut + li * 3;
+  return (unsigned)c[0] | ((unsigned)c[1] << 8) | ((unsigned)c[2] << 16);
+}
+
+__device__ __forceinline__ unsigned lo_byte(float x) {        // ((x + 1) / 2 * 255) clamped to [0, 255], truncated
+  float u = ((x + 1.0f) / 2.0f) * 255.0f;
+  u = u < 0.f ? 0.f : (u > 255.f ? 255.f : u);
+  return (unsigned)(int)u;
+}
+
+__global__ __launch_bounds__(256) void lidar_overlay_resolve_kernel(const lo_args a, const lo_table t) {
+  const int p = blockIdx.y;
+  const lo_picture& s = t.p[p];
+  const long long N = (long long)a.H * a.W, groups = (N + 3) >> 2;
+  const unsigned* rec = a.rec + p * LO_REC;
+  const unsigned count = rec[2];
+  const float zmin = count ? __uint_as_float(~rec[0]) : 0.f, zmax = count ? __uint_as_float(rec[1]) : 0.f;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {                 // the record, behind the pictures
+    const long long ro = a.rec_off + (long long)p * LO_REC * 4;
+    if (ro >= 0 && ro + LO_REC * 4 <= a.out_bytes) {
+      unsigned* o = reinterpret_cast<unsigned*>(a.out + ro);
+      o[0] = __float_as_uint(zmin), o[1] = __float_as_uint(zmax), o[2] = count, o[3] = 0u;
+    }
+  }
+  const unsigned* keys = a.keys + (long long)p * a.key_stride;
+  const float* f32 = reinterpret_cast<const float*>(s.frame);
+  const bool vec = (N & 3) == 0 && (reinterpret_cast<uintptr_t>(s.frame) & 15) == 0;
+  for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < groups; j += (long long)gridDim.x * 256) {
+    const long long q0 = j * 4, ob = s.out_off + q0 * 3;
+    const int m = N - q0 < 4 ? (int)(N - q0) : 4;            // pixels of this group
+    const uint4 k4 = *reinterpret_cast<const uint4*>(keys + q0);                 // (key rows are padded to whole groups)
+    const unsigned key[4] = {k4.x, k4.y, k4.z, k4.w};
+    unsigned under[4] = {0u, 0u, 0u, 0u};
+    if (s.kind == 1) {                                       // uint8 HWC: 12 bytes of 4 pixels
+      if (m == 4) {
+        const unsigned* w = reinterpret_cast<const unsigned*>(s.frame + q0 * 3);
+        const unsigned w0 = w[0], w1 = w[1], w2 = w[2];
+        under[0] = w0 & 0xffffffu, under[1] = (w0 >> 24) | ((w1 & 0xffffu) << 8);
+        under[2] = (w1 >> 16) | ((w2 & 0xffu) << 16), under[3] = w2 >> 8;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {                        // (the picture's last, short group)
+          if (e >= m) continue;
+          const unsigned char* c = s.frame + (q0 + e) * 3;
+          under[e] = (unsigned)c[0] | ((unsigned)c[1] << 8) | ((unsigned)c[2] << 16);
+        }
+      }
+    } else {                                                 // fp32 planar in [-1, 1]
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float* pc = f32 + c * N + q0;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (vec) {
+          const float4 f = *reinterpret_cast<const float4*>(pc);
+          v[0] = f.x, v[1] = f.y, v[2] = f.z, v[3] = f.w;
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = e < m ? pc[e] : 0.f;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) under[e] |= lo_byte(v[e]) << (8 * c);
+      }
+    }
+    unsigned px[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) px[e] = lo_pixel(a, s, e < m ? key[e] : 0u, zmin, zmax, under[e]);
+    if (ob < 0 || ob + m * 3 > a.out_bytes) continue;        // (the host placed every picture inside the buffer)
+    if (m == 4) {
+      unsigned* w = reinterpret_cast<unsigned*>(a.out + ob);                     // out, out_off and 12 j: 4-byte aligned
+      w[0] = px[0] | (px[1] << 24);
+      w[1] = (px[1] >> 8) | (px[2] << 16);
+      w[2] = (px[2] >> 16) | (px[3] << 8);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 3; ++e)
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          if (e < m) a.out[ob + e * 3 + c] = (unsigned char)(px[e] >> (8 * c));
+      // the bytes up to the next 4-byte boundary are nobody else's (every offset is a multiple of 4): 0, so that a buffer is
+      // defined to its last byte
+      for (long long b = ob + m * 3; (b & 3) && b < a.out_bytes; ++b) a.out[b] = 0;
+    }
+  }
+}
+
 }  // namespace mobi
 
 using namespace mobi;
@@ -1004,6 +1181,72 @@ extern "C" int mobi_camera_export(const mobi_camera_export_params* p, void* stre
                reinterpret_cast<int*>(p->out + p->status_offset), p->hs, p->ws, p->H, p->W, p->frames != 0};
   hipLaunchKernelGGL(camera_box_kernel, dim3(CE_BOX_PARTS, p->batch), dim3(256), 0, ST(stream), p->mask, p->box_ws, p->H, p->W);
   hipLaunchKernelGGL(camera_export_kernel, dim3(most > 2048 ? 2048 : most, p->batch), dim3(256), 0, ST(stream), a, t);
+  MOBI_CHECK_LAUNCH();
+  return MOBI_OK;
+}
+
+static inline long long lo_key_stride(long long H, long long W) { return (H * W + 3) & ~3LL; }
+
+extern "C" size_t mobi_lidar_overlay_workspace_bytes(int32_t n_pictures, int32_t H, int32_t W) {
+  if (n_pictures <= 0 || H <= 0 || W <= 0) return 0;
+  return (size_t)n_pictures * ((size_t)lo_key_stride(H, W) * 4 + LO_REC * 4);
+}
+
+extern "C" int mobi_lidar_overlay(const mobi_lidar_overlay_params* p, void* stream) {
+  if (!p || !p->pictures || !p->lut || !p->out || !p->workspace) return MOBI_ERR_ARG;
+  if (p->n_pictures <= 0 || p->h0 <= 0 || p->w0 <= 0 || p->H <= 0 || p->W <= 0 || p->out_bytes <= 0) return MOBI_ERR_ARG;
+  if (p->n_pictures > LO_MAX_PICTURES) return MOBI_ERR_UNSUPPORTED;
+  if (p->point_size != 1 && p->point_size != 3 && p->point_size != 5) return MOBI_ERR_UNSUPPORTED;
+  if ((long long)p->H * p->W > 0x7fffffffLL / 3 || (long long)p->h0 * p->w0 > 0x7ffffff0LL) return MOBI_ERR_UNSUPPORTED;   // (32-bit indices)
+  if (p->workspace_bytes < 0 || (size_t)p->workspace_bytes < mobi_lidar_overlay_workspace_bytes(p->n_pictures, p->H, p->W))
+    return MOBI_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(p->out) & 3) || (reinterpret_cast<uintptr_t>(p->workspace) & 15)) return MOBI_ERR_ALIGN;
+  auto place = [&](long long off, long long bytes) {         // inside the buffer, on a 4-byte boundary
+    if (off < 0 || off > p->out_bytes || bytes > p->out_bytes - off) return (int)MOBI_ERR_ARG;
+    return (off & 3) ? (int)MOBI_ERR_ALIGN : (int)MOBI_OK;
+  };
+  int rc = place(p->records_offset, 4LL * LO_REC * p->n_pictures);
+  if (rc != MOBI_OK) return rc;
+  const long long N = (long long)p->H * p->W, stride = lo_key_stride(p->H, p->W);
+  lo_table t[LO_MAX_PICTURES / LO_LAUNCH] = {};
+  for (int i = 0; i < p->n_pictures; ++i) {
+    const mobi_lidar_overlay_picture& s = p->pictures[i];
+    if (!s.depth || !s.pitch || !s.yaw || !s.frame || s.frame_offset < 0) return MOBI_ERR_ARG;
+    if (s.frame_kind != MOBI_OVERLAY_FRAME_F32_PLANAR && s.frame_kind != MOBI_OVERLAY_FRAME_U8_HWC) return MOBI_ERR_ARG;
+    if ((rc = place(s.out_offset, 3 * N)) != MOBI_OK) return rc;
+    const uintptr_t frame = reinterpret_cast<uintptr_t>(s.frame) + (uintptr_t)s.frame_offset;
+    // a picture owns its bytes up to the next multiple of 4 (the resolve launch zeroes them): it may share none of them with the
+    // records or with an earlier picture, and no frame source may lie in the buffer the pictures are written to
+    const long long end = (s.out_offset + 3 * N + 3) & ~3LL;
+    if (s.out_offset < p->records_offset + 4LL * LO_REC * p->n_pictures && p->records_offset < end) return MOBI_ERR_ARG;
+    for (int j = 0; j < i; ++j) {
+      const long long oj = p->pictures[j].out_offset;
+      if (s.out_offset < ((oj + 3 * N + 3) & ~3LL) && oj < end) return MOBI_ERR_ARG;
+    }
+    const uintptr_t frame_bytes = (uintptr_t)(s.frame_kind == MOBI_OVERLAY_FRAME_U8_HWC ? 3 * N : 12 * N);
+    const uintptr_t out0 = reinterpret_cast<uintptr_t>(p->out);
+    if (frame < out0 + (uintptr_t)p->out_bytes && out0 < frame + frame_bytes) return MOBI_ERR_ARG;
+    if ((frame & 3) || ((reinterpret_cast<uintptr_t>(s.depth) | reinterpret_cast<uintptr_t>(s.pitch) | reinterpret_cast<uintptr_t>(s.yaw)) & 3))
+      return MOBI_ERR_ALIGN;
+    lo_picture& o = t[i / LO_LAUNCH].p[i % LO_LAUNCH];
+    o.depth = s.depth, o.pitch = s.pitch, o.yaw = s.yaw, o.frame = reinterpret_cast<const unsigned char*>(frame);
+    o.out_off = s.out_offset, o.kind = s.frame_kind;
+    for (int k = 0; k < 12; ++k) o.m[k] = s.matrix[k];
+  }
+  unsigned* keys = reinterpret_cast<unsigned*>(p->workspace);
+  unsigned* rec = keys + (long long)p->n_pictures * stride;
+  if (hipMemsetAsync(p->workspace, 0, mobi_lidar_overlay_workspace_bytes(p->n_pictures, p->H, p->W), ST(stream)) != hipSuccess)
+    return MOBI_ERR_LAUNCH;
+  const int sweep_blocks = (int)(((long long)p->h0 * p->w0 + 255) / 256);
+  const long long groups = (N + 3) / 4;
+  const int frame_blocks = (int)((groups + 255) / 256 > 4096 ? 4096 : (groups + 255) / 256);
+  for (int lo = 0; lo < p->n_pictures; lo += LO_LAUNCH) {
+    const int n = p->n_pictures - lo < LO_LAUNCH ? p->n_pictures - lo : LO_LAUNCH;
+    const lo_args a = {keys + (long long)lo * stride, rec + lo * LO_REC, p->lut, p->out, p->out_bytes,
+                       p->records_offset + 4LL * LO_REC * lo, stride, p->h0, p->w0, p->H, p->W, p->point_size};
+    hipLaunchKernelGGL(lidar_overlay_splat_kernel, dim3(sweep_blocks, n), dim3(256), 0, ST(stream), a, t[lo / LO_LAUNCH]);
+    hipLaunchKernelGGL(lidar_overlay_resolve_kernel, dim3(frame_blocks, n), dim3(256), 0, ST(stream), a, t[lo / LO_LAUNCH]);
+  }
   MOBI_CHECK_LAUNCH();
   return MOBI_OK;
 }

@@ -281,6 +281,8 @@ extern "C" size_t mobi_struct_size(int id) {
     case 30: return sizeof(mobi_image_grid_source);
     case 31: return sizeof(mobi_camera_export_params);
     case 32: return sizeof(mobi_repack_entry);
+    case 33: return sizeof(mobi_lidar_overlay_params);
+    case 34: return sizeof(mobi_lidar_overlay_picture);
     default: return 0;
   }
 }

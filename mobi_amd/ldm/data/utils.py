@@ -119,13 +119,15 @@ def paste_camera_patch(*, patch_pred, image, mask, crop, ksize=15, sigma=7.0):
     return ops.blend_frame(blur, image, frame), frame
 
 
-def export_camera_batch(*, patch_pred, patch_gt, ref_image, image, mask, crop, frames=True, ksize=15, sigma=7.0):
+def export_camera_batch(*, patch_pred, patch_gt, ref_image, image, mask, crop, frames=True, ksize=15, sigma=7.0, return_device=False):
     """The camera results of scripts/inference_test_bench.py:478-527 for the WHOLE batch: `mobi_camera_export`, then ONE copy into
     pinned host memory.  patch_pred / patch_gt: fp32 [B, 3, hs, ws] in [-1, 1]; ref_image: [B, 3, h, w] CLIP-normalised (resized to
     224 x 224 first, as un_norm_clip does); image: [B, 3, H, W] in [-1, 1]; mask: [B, H, W] (1 = keep); crop: B x (left, top,
     crop_W, crop_H).  Returns B dicts of numpy uint8 HWC views in RGB order -- what the reference's files hold, since it hands cv2
     BGR arrays: frame (only with `frames`), patch_pred (the composited crop), patch_gt, object_pred, object_ref.  ValueError
-    names an object whose mask box is empty once its last row and column are excluded, as the reference slices it."""
+    names an object whose mask box is empty once its last row and column are excluded, as the reference slices it.
+    return_device: (pictures, the uint8 device buffer, its `ops.camera_export_layout`) -- for `overlay_lidar_batch`, which reads the
+    recomposed frames in place."""
     assert ksize == 15, "mobi_camera_export is built for the reference's 15-tap blur"
     dev = patch_pred.device
     f = lambda t: _as_dev(t, dev).float().contiguous()
@@ -145,7 +147,127 @@ def export_camera_batch(*, patch_pred, patch_gt, ref_image, image, mask, crop, f
                          "(a single row or column of edit pixels, or none)")
         err.pictures = pictures                                        # the other objects' pictures are complete
         raise err
-    return pictures
+    return (pictures, out, layout) if return_device else pictures
+
+
+# --------------------------------------------------------------------------------------
+# lidar-on-camera overlays (reference: scripts/inference_test_bench.py, overlay_lidar_on_image and its two calls per object;
+# restated from its behaviour at the frame's own resolution -- matplotlib's resampled figure is not reproduced)
+# --------------------------------------------------------------------------------------
+_TURBO = {}
+
+
+def turbo_lut():
+    """matplotlib's 256-entry `turbo` as uint8 [256, 3] RGB (fetched lazily: matplotlib is only needed where overlays are made)."""
+    if "host" not in _TURBO:
+        import matplotlib
+        _TURBO["host"] = np.ascontiguousarray(matplotlib.colormaps["turbo"](np.arange(256), bytes=True)[:, :3]).astype(np.uint8)
+    return _TURBO["host"]
+
+
+def _turbo_on(device):
+    key = str(device)
+    if key not in _TURBO:
+        _TURBO[key] = torch.from_numpy(turbo_lut()).to(device)         # uploaded once per device
+    return _TURBO[key]
+
+
+def marker_offsets(point_size):
+    """(dx, dy) of a marker's pixels: dx^2 + dy^2 <= (point_size / 2)^2 -- 1, 9 and 21 pixels for point_size 1, 3, 5."""
+    if point_size not in (1, 3, 5):
+        raise ValueError(f"point_size {point_size}: 1, 3 or 5")
+    r = point_size // 2
+    return [(dx, dy) for dy in range(-r, r + 1) for dx in range(-r, r + 1) if 4 * (dx * dx + dy * dy) <= point_size * point_size]
+
+
+def frame_u8(image):
+    """A frame as the overlay shows it: uint8 [H, W, 3] as it is; fp32 [3, H, W] in [-1, 1] -> ((x + 1) / 2 * 255) clamped to
+    [0, 255] and truncated, HWC."""
+    image = np.asarray(image)
+    if image.dtype == np.uint8:
+        assert image.ndim == 3 and image.shape[2] == 3
+        return image.copy()
+    assert image.ndim == 3 and image.shape[0] == 3
+    x = image.astype(np.float32)
+    return ((x + np.float32(1)) / np.float32(2) * np.float32(255)).clip(0, 255).astype(np.uint8).transpose(1, 2, 0).copy()
+
+
+def overlay_lidar_on_image(points, lidar2image, image, point_size=3, lut=None, return_record=False):
+    """The overlay of ONE picture in numpy, the documented meaning of `mobi_lidar_overlay` (include/mobi_engine.h) and the slow
+    path: points [N, 3] in the order range2pcd leaves them (row-major over the sweep), lidar2image 4 x 4, image uint8 [H, W, 3] or
+    fp32 [3, H, W] in [-1, 1] -> uint8 [H, W, 3].  fp32 throughout, every operation rounded on its own: q = M (x, y, z, 1) summed left
+    to right; kept iff q.z > 0 and, with zc = clip(q.z, 1e-5, 1e5), 0 <= q.x / zc < W and 0 <= q.y / zc < H; colour
+    lut[min(int((zc - zmin) / (zmax - zmin) * 256), 255)] over the kept points (index 0 when zmax == zmin); marker = `marker_offsets`
+    around (floor(u), floor(v)), clipped; the later point wins where markers overlap.  return_record: also (zmin, zmax, kept)."""
+    lut = turbo_lut() if lut is None else np.asarray(lut, dtype=np.uint8)
+    pic = frame_u8(image)
+    H, W = pic.shape[:2]
+    pts = np.asarray(points, dtype=np.float32).reshape(-1, 3)
+    m = np.asarray(lidar2image, dtype=np.float64).reshape(-1, 4)[:3].astype(np.float32)
+    x, y, z = pts[:, 0], pts[:, 1], pts[:, 2]
+    q = [m[r, 0] * x + m[r, 1] * y + m[r, 2] * z + m[r, 3] for r in range(3)]
+    zc = np.clip(q[2], np.float32(1e-5), np.float32(1e5))
+    u, v = q[0] / zc, q[1] / zc
+    keep = (q[2] > 0) & (u >= 0) & (u < np.float32(W)) & (v >= 0) & (v < np.float32(H))
+    record = (np.float32(0), np.float32(0), 0)
+    if keep.any():
+        index = np.nonzero(keep)[0]
+        zc, px, py = zc[keep], u[keep].astype(np.int64), v[keep].astype(np.int64)
+        zmin, zmax = zc.min(), zc.max()
+        record = (zmin, zmax, int(keep.sum()))
+        t = (zc - zmin) / (zmax - zmin) if zmax != zmin else np.zeros_like(zc)
+        colour = lut[np.minimum((t * np.float32(256)).astype(np.int64), 255)]
+        key = np.zeros((H, W), dtype=np.int64)                          # position among the kept points + 1 of the winner
+        order = np.arange(1, len(index) + 1)
+        for dx, dy in marker_offsets(point_size):
+            xx, yy = px + dx, py + dy
+            ok = (xx >= 0) & (xx < W) & (yy >= 0) & (yy < H)
+            np.maximum.at(key, (yy[ok], xx[ok]), order[ok])
+        drawn = key > 0
+        pic[drawn] = colour[key[drawn] - 1]
+    return (pic, record) if return_record else pic
+
+
+def overlay_lidar_batch(*, depth, pitch, yaw, lidar2image, frames_f32=None, frames_u8=None, size=None, point_size=3):
+    """The lidar-on-camera overlays of a WHOLE batch: `mobi_lidar_overlay`, then ONE copy into pinned host memory.  One picture per
+    sweep: depth (the code in [-1, 1]) / pitch / yaw [P, H0, W0] and lidar2image [P, 4, 4] (host or device).  Picture i is drawn on
+    frames_u8 = (uint8 device buffer, offsets)'s [H, W, 3] frame at byte offsets[i] where that is not None -- `export_camera_batch(
+    ..., return_device=True)`'s buffer, read in place -- and else on frames_f32[i], fp32 [3, H, W] in [-1, 1].  size = (H, W) is
+    needed only when no fp32 frame tells it.  Returns (P numpy uint8 HWC views into one pinned buffer, dict(zmin fp32 [P],
+    zmax fp32 [P], count int32 [P]) over each picture's kept points).  Any P: 64 pictures per engine call."""
+    dev = depth.device
+    f = lambda t: _as_dev(t, dev).float().contiguous()
+    depth, pitch, yaw = f(depth), f(pitch), f(yaw)
+    P = depth.shape[0]
+    assert depth.dim() == 3 and pitch.shape == depth.shape and yaw.shape == depth.shape and len(lidar2image) == P
+    buf, offsets = frames_u8 if frames_u8 is not None else (None, [None] * P)
+    planar = list(frames_f32) if frames_f32 is not None else [None] * P
+    assert len(offsets) == P and len(planar) == P
+    frames = []
+    for i in range(P):
+        if offsets[i] is not None:
+            frames.append((buf, int(offsets[i])))
+        elif planar[i] is not None:
+            frames.append(f(planar[i]))
+            if size is not None and tuple(frames[-1].shape[-2:]) != tuple(int(v) for v in size):
+                raise ValueError(f"overlay_lidar_batch: picture {i}'s frame is {tuple(frames[-1].shape[-2:])}, not {tuple(size)}")
+            size = tuple(frames[-1].shape[-2:])
+        else:
+            raise ValueError(f"overlay_lidar_batch: picture {i} has no frame")
+    if size is None:
+        raise ValueError("overlay_lidar_batch: size=(H, W) is needed when every frame is uint8")
+    H, W = (int(v) for v in size)
+    matrices = lidar2image.detach().cpu() if isinstance(lidar2image, torch.Tensor) else lidar2image
+    out, layout = ops.lidar_overlay([(depth[i], pitch[i], yaw[i]) for i in range(P)], matrices, frames, _turbo_on(dev), H=H, W=W,
+                                    point_size=point_size)
+    host = torch.empty(layout["bytes"], dtype=torch.uint8, pin_memory=True)
+    with ops._Timed("lidar_overlay_d2h", 0.0, float(layout["bytes"])):
+        host.copy_(out, non_blocking=True)
+    torch.cuda.current_stream(dev).synchronize()
+    flat = host.numpy()
+    rec = flat[layout["records"]:layout["bytes"]].view(np.uint32).reshape(P, 4)
+    records = {"zmin": rec[:, 0].copy().view(np.float32), "zmax": rec[:, 1].copy().view(np.float32), "count": rec[:, 2].astype(np.int32)}
+    return [flat[o:o + H * W * 3].reshape(H, W, 3) for o, _ in layout["pictures"]], records
 
 
 # --------------------------------------------------------------------------------------

@@ -1825,6 +1825,64 @@ def camera_export(patch_pred, patch_gt, ref, image, mask, crops, taps, *, frames
     return out, layout
 
 
+def lidar_overlay_layout(P, H, W):
+    """Where `lidar_overlay` puts its P pictures: dict(pictures=[(byte offset, (H, W, 3))], records=byte offset of the uint32
+    [P, 4] records (zmin bits, zmax bits, kept count, 0), bytes=size of the buffer).  Every picture starts on a 4-byte boundary, none
+    overlap, the records lie behind the pictures (include/mobi_engine.h)."""
+    P, H, W = int(P), int(H), int(W)
+    if P <= 0 or H <= 0 or W <= 0:
+        raise ValueError(f"lidar_overlay: {P} pictures of {H} x {W}")
+    step = (H * W * 3 + 3) // 4 * 4
+    return {"pictures": [(i * step, (H, W, 3)) for i in range(P)], "records": P * step, "bytes": P * step + 16 * P}
+
+
+def lidar_overlay(sweeps, matrices, frames, lut, *, H, W, point_size=3):
+    """The lidar-on-camera overlays of a batch (include/mobi_engine.h, mobi_lidar_overlay).  Per picture: sweeps[i] = (depth,
+    pitch, yaw), fp32 [H0, W0] device tensors (views are fine: nothing is copied); matrices[i] = lidar2image, 4 x 4 (or its first
+    three rows) on the host; frames[i] = an fp32 [3, H, W] device tensor in [-1, 1], or (uint8 device buffer, byte offset of an
+    [H, W, 3] frame in it) -- another call's output read in place.  lut: uint8 [256, 3] on the device.  -> (uint8 device buffer,
+    `lidar_overlay_layout`).  One clear and two launches per 32 pictures, one call per 64."""
+    lib = _lib.load()
+    P = len(sweeps)
+    assert len(frames) == P and len(matrices) == P and P > 0
+    dev = _dev(lut).device
+    assert lut.dtype == torch.uint8 and tuple(lut.shape) == (256, 3) and lut.is_contiguous()
+    h0, w0 = sweeps[0][0].shape
+    layout = lidar_overlay_layout(P, H, W)
+    out = torch.empty(layout["bytes"], device=dev, dtype=torch.uint8)
+    step = _lib.LIDAR_OVERLAY_MAX_PICTURES
+    ws_bytes = int(lib.mobi_lidar_overlay_workspace_bytes(min(P, step), H, W))
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    pics = (_lib.LidarOverlayPicture * P)()
+    for i, (pic, sweep, matrix, frame) in enumerate(zip(pics, sweeps, matrices, frames)):
+        for t_ in sweep:
+            assert _dev(t_).dtype == torch.float32 and t_.is_contiguous() and tuple(t_.shape) == (h0, w0) and t_.device == dev
+        pic.depth, pic.pitch, pic.yaw = (_ptr(t_) for t_ in sweep)
+        m = torch.as_tensor(matrix).detach().cpu().reshape(-1, 4)[:3].to(torch.float32)
+        assert tuple(m.shape) == (3, 4)
+        pic.matrix[:] = m.reshape(-1).tolist()
+        if isinstance(frame, torch.Tensor):
+            assert frame.dtype == torch.float32 and tuple(frame.shape) == (3, H, W) and frame.is_contiguous() and frame.device == dev
+            pic.frame, pic.frame_offset, pic.frame_kind = _ptr(frame), 0, _lib.OVERLAY_FRAME_F32_PLANAR
+        else:
+            buf, offset = frame
+            assert buf.dtype == torch.uint8 and buf.is_contiguous() and buf.device == dev
+            if offset < 0 or offset + H * W * 3 > buf.numel():
+                raise ValueError(f"lidar_overlay: picture {i}'s frame leaves its buffer")
+            pic.frame, pic.frame_offset, pic.frame_kind = _ptr(buf), int(offset), _lib.OVERLAY_FRAME_U8_HWC
+        pic.out_offset = layout["pictures"][i][0]
+    for lo in range(0, P, step):
+        n = min(step, P - lo)
+        p = _lib.LidarOverlayParams()
+        p.pictures = C.addressof(pics) + lo * C.sizeof(_lib.LidarOverlayPicture)
+        p.lut, p.out, p.workspace = _ptr(lut), _ptr(out), _ptr(ws)
+        p.out_bytes, p.records_offset, p.workspace_bytes = layout["bytes"], layout["records"] + 16 * lo, ws_bytes
+        p.n_pictures, p.h0, p.w0, p.H, p.W, p.point_size = n, h0, w0, int(H), int(W), int(point_size)
+        with _Timed("lidar_overlay", 0.0, float(n * H * W * 3), f"p{n}"):
+            _lib.check(lib.mobi_lidar_overlay(C.byref(p), _stream()), "mobi_lidar_overlay")
+    return out, layout
+
+
 def paste_patch(patch, frame, top, left, crop_h, crop_w):
     """patch: fp32 [3, hs, ws] RGB in [-1, 1]; frame: uint8 [H, W, 3] BGR (written in place)."""
     lib = _lib.load()
