@@ -512,7 +512,7 @@ __device__ __forceinline__ unsigned pack2(float lo, float hi) {
   return __builtin_bit_cast(unsigned, v);
 }
 
-// QSH: the head dim leaves a padded channel in the last k-step (dh % 16 == 8: 8, 24, 40, 72); the shift then rides in
+// QSH: the head dim leaves a padded channel in the last k-step (dh % 16 == 8: 8, 24, 40, 56, 72); the shift then rides in
 // that channel of Q' against a column of ones in the K image instead of sixteen C-operand registers.
 // H16 (padded head dims with an odd number of k-steps, i.e. dh = 40 / 72: the last 32-channel block of O^T holds 8 channels and
 // the denominator): that block's P.V runs on MFMA 16x16x32 -- D[16 channels][16 queries], two per 32-key half, 16 cycles each
