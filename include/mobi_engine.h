@@ -58,7 +58,8 @@ extern "C" {
  *      mobi_image_grid (mobi_image_grid_source 30); likewise the test bench's camera pictures, mobi_camera_export
  *      (mobi_camera_export_params 31); likewise the one launch that refreshes every trained weight's 16-bit images,
  *      mobi_repack_multi (mobi_repack_entry 32); likewise the test bench's lidar-on-camera overlays, mobi_lidar_overlay +
- *      mobi_lidar_overlay_workspace_bytes (mobi_lidar_overlay_params 33, mobi_lidar_overlay_picture 34) */
+ *      mobi_lidar_overlay_workspace_bytes (mobi_lidar_overlay_params 33, mobi_lidar_overlay_picture 34); likewise the numeric
+ *      health launch, mobi_tensor_health (mobi_health_tensor 35, mobi_health_record 36) */
 #define MOBI_ABI_VERSION 6
 
 enum { MOBI_OK = 0, MOBI_ERR_ARG = -1, MOBI_ERR_UNSUPPORTED = -2, MOBI_ERR_LAUNCH = -3, MOBI_ERR_ALIGN = -4 };
@@ -72,7 +73,8 @@ const char* mobi_error_string(int code);
  * 8 ddim_step, 9 two_key_adapter, 10 range_paste, 11 lidar_metrics, 12 range_prepare, 13 image_prepare, 14 ff_geglu,
  * 15 row_chain, 16 chain_op, 17 layernorm_bwd, 18 attention_bwd, 19 split_source, 20 dpm_step, 21 lpips_distance,
  * 22 image_normalize, 23 mt_tensor, 24 mt_chunk, 25 grad_stats_record, 26 mt_pair, 27 loss_grad, 28 ref_augment, 29 snapshot_record,
- * 30 image_grid_source, 31 camera_export, 32 repack_entry, 33 lidar_overlay, 34 lidar_overlay_picture.
+ * 30 image_grid_source, 31 camera_export, 32 repack_entry, 33 lidar_overlay, 34 lidar_overlay_picture,
+ * 35 health_tensor, 36 health_record.
  * Returns 0 for an unknown id. */
 size_t mobi_struct_size(int id);
 /* Development hook: the library reads its MOBI_* A/B environment variables once, at the first launch
@@ -538,6 +540,34 @@ typedef struct mobi_repack_entry {
 } mobi_repack_entry;
 int mobi_repack_multi(const mobi_repack_entry* entries, int32_t n_entries, const mobi_mt_chunk* tiles, int32_t n_tiles,
                       int32_t dtype, void* stream);
+
+/* The numeric health of up to 64 dense tensors of mixed storage types in ONE launch (mobi_amd/health.py: the probe's rows, the
+ * weight audit): where in fp16's (bf16's, fp32's) range a tensor lies and whether it left it.  Read only; one record per tensor.
+ * Per element, by bit pattern, a = |x| converted to fp32 (exact for both 16-bit types):
+ *   nan          all exponent bits set and mantissa != 0
+ *   inf          all exponent bits set and mantissa == 0
+ *   absmax_bits  the largest fp32 bit pattern of a over the FINITE elements (0 if there are none)
+ *   near         finite and a >= near_abs, as an fp32 compare (near_abs = +inf: never)
+ *   subnormal    exponent bits zero and mantissa != 0, in the tensor's own format
+ * `tensors` is a HOST array: it is checked here and travels to the device inside the launch's own argument block, with the
+ * block count of every tensor as a prefix array (a block finds its tensor and offset from it); no device table, no chunk map.
+ * x: DEVICE, dense, n elements, aligned to its element size (a 16-bit tensor may start on any 2-byte boundary, an fp32 tensor on
+ * any 4-byte boundary: 16-byte loads on the aligned body, element loads on its head and tail).  out: DEVICE [n_tensors], 8-byte
+ * aligned; zeroed on the stream, then every wave reduces what it read and contributes with one vector atomic per field that is
+ * not zero (a max on absmax_bits, 64-bit adds on the counts): integer max and sum commute, so the records are bit-equal run to
+ * run and independent of the grid.  Counts are exact.
+ * NULL tensors / out / x, n_tensors <= 0 or > 64 (a caller splits), n <= 0, a dtype outside {MOBI_F16, MOBI_BF16, MOBI_F32},
+ * near_abs negative or nan: MOBI_ERR_ARG; x off its element size, out off 8 bytes: MOBI_ERR_ALIGN; all before anything is
+ * enqueued.  Addition to ABI 6 (struct ids 35, 36). */
+enum { MOBI_F32 = 2 };   /* accepted by mobi_tensor_health only, beside MOBI_F16 / MOBI_BF16 */
+enum { MOBI_HEALTH_MAX_TENSORS = 64 };
+typedef struct mobi_health_tensor {
+  const void* x; int64_t n; int32_t dtype; float near_abs;
+} mobi_health_tensor;
+typedef struct mobi_health_record {
+  uint32_t absmax_bits, reserved; int64_t inf, nan, near, subnormal;
+} mobi_health_record;
+int mobi_tensor_health(const mobi_health_tensor* tensors, int32_t n_tensors, mobi_health_record* out, void* stream);
 
 typedef struct mobi_attention_bwd_params {
   const void* q; int64_t q_img_stride, q_row_stride;       /* T [image][tq][>= heads*dh], strides in elements */

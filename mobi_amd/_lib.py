@@ -244,6 +244,19 @@ class LidarOverlayParams(C.Structure):
                 ("workspace_bytes", i64), ("n_pictures", i32), ("h0", i32), ("w0", i32), ("H", i32), ("W", i32), ("point_size", i32)]
 
 
+MOBI_F32 = 2                      # accepted by mobi_tensor_health only
+HEALTH_MAX_TENSORS = 64           # per mobi_tensor_health launch
+
+
+class HealthTensor(C.Structure):
+    _fields_ = [("x", vp), ("n", i64), ("dtype", i32), ("near_abs", f32)]
+
+
+class HealthRecord(C.Structure):
+    _fields_ = [("absmax_bits", C.c_uint32), ("reserved", C.c_uint32), ("inf", i64), ("nan", i64), ("near", i64),
+                ("subnormal", i64)]
+
+
 STRUCT_IDS = {0: IgemmParams, 1: GroupNormParams, 2: LayerNormParams, 3: AttentionParams, 4: CtxAttentionParams,
               5: SkinnyLinearParams, 6: ConvSmallCinParams, 7: ConvSmallCoutParams, 8: DdimStepParams, 9: TwoKeyAdapterParams,
               10: RangePasteParams, 11: LidarMetricsParams, 12: RangePrepareParams, 13: ImagePrepareParams,
@@ -251,7 +264,8 @@ STRUCT_IDS = {0: IgemmParams, 1: GroupNormParams, 2: LayerNormParams, 3: Attenti
               17: LayerNormBwdParams, 18: AttentionBwdParams, 19: SplitSource, 20: DpmStepParams,
               21: LpipsDistanceParams, 22: ImageNormalizeParams, 23: MtTensor, 24: MtChunk, 25: GradStatsRecord,
               26: MtPair, 27: LossGradParams, 28: RefAugmentParams, 29: SnapshotRecord, 30: ImageGridSource,
-              31: CameraExportParams, 32: RepackEntry, 33: LidarOverlayParams, 34: LidarOverlayPicture}
+              31: CameraExportParams, 32: RepackEntry, 33: LidarOverlayParams, 34: LidarOverlayPicture,
+              35: HealthTensor, 36: HealthRecord}
 
 # every symbol include/mobi_engine.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -334,6 +348,7 @@ SYMBOLS = {
     "mobi_camera_export": (C.c_int, [C.POINTER(CameraExportParams), vp]),
     "mobi_lidar_overlay_workspace_bytes": (C.c_size_t, [i32, i32, i32]),
     "mobi_lidar_overlay": (C.c_int, [C.POINTER(LidarOverlayParams), vp]),
+    "mobi_tensor_health": (C.c_int, [C.POINTER(HealthTensor), i32, vp, vp]),
     "mobi_paste_patch": (C.c_int, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
     "mobi_gaussian_blur": (C.c_int, [vp, vp, vp, i32, i32, vp, i32, vp]),
     "mobi_blend_frame": (C.c_int, [vp, vp, vp, vp, i32, i32, vp]),

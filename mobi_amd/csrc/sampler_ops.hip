@@ -283,6 +283,8 @@ extern "C" size_t mobi_struct_size(int id) {
     case 32: return sizeof(mobi_repack_entry);
     case 33: return sizeof(mobi_lidar_overlay_params);
     case 34: return sizeof(mobi_lidar_overlay_picture);
+    case 35: return sizeof(mobi_health_tensor);
+    case 36: return sizeof(mobi_health_record);
     default: return 0;
   }
 }

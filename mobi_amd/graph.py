@@ -186,7 +186,7 @@ class StepGraph:
 
 
 def usable(x):
-    return ENABLED and x.is_cuda and ops._PROFILE is None and not torch.cuda.is_current_stream_capturing()
+    return ENABLED and x.is_cuda and ops._PROFILE is None and ops._HEALTH is None and not torch.cuda.is_current_stream_capturing()
 
 
 def get(sampler, kind, x, cond, uncond, scale, kwargs, temperature=1., has_noise=False):

@@ -160,6 +160,7 @@ class ResnetBlock(nn.Module):
         xs = ops.igemm(x, self.nin_shortcut.packed()) if self.in_channels != self.out_channels else x
         return leave(ops.igemm(h, self.conv2.packed(), pad=self.conv2.padding, residual=xs), ext)
 
+    @ops.health_labelled
     def forward_trunk(self, x, trunk):
         """The same block on an fp32 trunk: x = the trunk's 16-bit copy -> (x', trunk')."""
         h = ops.igemm(_gn_swish(self.norm1, x), self.conv1.packed(), pad=self.conv1.padding)
@@ -168,6 +169,7 @@ class ResnetBlock(nn.Module):
             trunk = ops.igemm(x, self.nin_shortcut.packed(), out_mode=OUT_ROWS_F32)
         return ops.trunk_add(trunk, h, x.dtype), trunk
 
+    @ops.health_labelled
     def forward_stream(self, t32):
         """The block on an fp32 stream (see fp32_streams): fp32 [N,H,W,Cin] -> fp32 [N,H,W,Cout]."""
         h32 = ops.igemm(_gn32(self.norm1, t32), self.conv1.packed(), pad=self.conv1.padding, out_mode=OUT_ROWS_F32)
@@ -176,6 +178,7 @@ class ResnetBlock(nn.Module):
             t32 = ops.igemm(ops.trunk_add(t32, None, engine_dtype()), self.nin_shortcut.packed(), out_mode=OUT_ROWS_F32)
         return ops.lincomb4([t32, d32], [1.0, 1.0])
 
+    @ops.health_labelled
     def forward_precise(self, t32, level=1):
         """The block on an fp32 stream, the convolutions' operands split (see precise_level): fp32 [N,H,W,Cin] -> fp32 [N,H,W,Cout]."""
         h32 = ops.igemm(_gn_split(self.norm1, t32, level), _w_split(self.conv1, level), pad=self.conv1.padding, out_mode=OUT_ROWS_F32)
@@ -217,6 +220,7 @@ class AttnBlock(nn.Module):
             return ops.trunk_add(trunk, ops.igemm(o, self.proj_out.packed()), x.dtype), trunk
         return leave(ops.igemm(o, self.proj_out.packed(), residual=x), ext)
 
+    @ops.health_labelled
     def forward_stream(self, t32):
         """The block on an fp32 stream: fp32 [N,H,W,C] -> fp32 (GroupNorm reads fp32, proj_out writes fp32, fp32 add)."""
         n, h, w, c = t32.shape
@@ -282,7 +286,8 @@ class Encoder(nn.Module):
     def forward(self, x):
         """x: fp32 NCHW image / range view -> fp32 NCHW [B, 2*z, h, w]."""
         cin = self.conv_in_lidar if self.lidar_adapter else self.conv_in
-        h = ops.igemm(ops.pack_sources([x.float().contiguous()], engine_dtype()), cin.packed_thin(), pad=cin.padding)
+        with ops.health_scope("conv_in_lidar" if self.lidar_adapter else "conv_in"):
+            h = ops.igemm(ops.pack_sources([x.float().contiguous()], engine_dtype()), cin.packed_thin(), pad=cin.padding)
         if self.lidar_adapter:
             h = self.res_block_lidar2(self.res_block_lidar1(h))
         for i_level in range(self.num_resolutions):
@@ -292,7 +297,8 @@ class Encoder(nn.Module):
                 h = self.down[i_level].downsample(h)
         h = self.mid.block_2(self.mid.attn_1(self.mid.block_1(h)))
         h = _gn_swish(self.norm_out, h)
-        return ops.conv_small_cout(h, self.conv_out.packed_tap_major(), pad=self.conv_out.padding)
+        with ops.health_scope("conv_out"):
+            return ops.conv_small_cout(h, self.conv_out.packed_tap_major(), pad=self.conv_out.padding)
 
 
 class Decoder(nn.Module):
@@ -355,10 +361,12 @@ class Decoder(nn.Module):
                     w = ci.weight.detach().float()
                     parts = [w, w] + ([w - w.to(dt).float()] if lvl == 2 else [])
                     return ops.pack_conv_padded_cin(torch.cat(parts, dim=1), ci.bias, dt, ci.weight.device)
-                t32 = ops.igemm(ops.pack_sources([zhi, zf - zhi] + ([zhi] if lvl == 2 else []), dt), ci._cached(f"thin_split{lvl}", thin_split),
-                                pad=(1, 1), out_mode=OUT_ROWS_F32)
+                with ops.health_scope("conv_in"):
+                    t32 = ops.igemm(ops.pack_sources([zhi, zf - zhi] + ([zhi] if lvl == 2 else []), dt), ci._cached(f"thin_split{lvl}", thin_split),
+                                    pad=(1, 1), out_mode=OUT_ROWS_F32)
             else:
-                t32 = ops.igemm(zin, self.conv_in.packed_thin(), pad=(1, 1), out_mode=OUT_ROWS_F32)
+                with ops.health_scope("conv_in"):
+                    t32 = ops.igemm(zin, self.conv_in.packed_thin(), pad=(1, 1), out_mode=OUT_ROWS_F32)
             t32 = rb(self.mid.block_2, self.mid.attn_1.forward_stream(rb(self.mid.block_1, t32)))
             for i_level in reversed(range(self.num_resolutions)):
                 for i_block in range(self.num_res_blocks + 1):
@@ -379,13 +387,15 @@ class Decoder(nn.Module):
                 norm, cout = self.norm_out_lidar2, self.conv_out_lidar
             else:
                 u32, norm, cout = t32, self.norm_out, self.conv_out
-            if tail:                                               # (the small-cout kernel: hi | lo pairs at every level)
-                return ops.conv_small_cout(_gn_pair(norm, u32), cout.packed_dup(), pad=cout.padding, clamp=clamp)
-            return ops.conv_small_cout(_gn32(norm, u32), cout.packed_tap_major(), pad=cout.padding, clamp=clamp)
+            with ops.health_scope("conv_out_lidar" if self.lidar_adapter else "conv_out"):
+                if tail:                                           # (the small-cout kernel: hi | lo pairs at every level)
+                    return ops.conv_small_cout(_gn_pair(norm, u32), cout.packed_dup(), pad=cout.padding, clamp=clamp)
+                return ops.conv_small_cout(_gn32(norm, u32), cout.packed_tap_major(), pad=cout.padding, clamp=clamp)
         if fp32_trunk():
             dt = engine_dtype()
-            t32 = ops.igemm(zin, self.conv_in.packed_thin(), pad=(1, 1), out_mode=OUT_ROWS_F32)
-            h = ops.trunk_add(t32, None, dt)
+            with ops.health_scope("conv_in"):
+                t32 = ops.igemm(zin, self.conv_in.packed_thin(), pad=(1, 1), out_mode=OUT_ROWS_F32)
+                h = ops.trunk_add(t32, None, dt)
             h, t32 = self.mid.block_1.forward_trunk(h, t32)
             h, t32 = self.mid.attn_1(h, trunk=t32)
             h, t32 = self.mid.block_2.forward_trunk(h, t32)
@@ -402,7 +412,8 @@ class Decoder(nn.Module):
                 u32 = ops.groupnorm(t32, g, b, self.norm_out_lidar1.eps, silu=True, out_mode=ops.GN_OUT_F32, dtype=dt)
                 u32 = self.res_block_lidar2.forward_precise(u32)
                 cout = self.conv_out_lidar
-                return ops.conv_small_cout(_gn_pair(self.norm_out_lidar2, u32), cout.packed_dup(), pad=cout.padding, clamp=clamp)
+                with ops.health_scope("conv_out_lidar"):
+                    return ops.conv_small_cout(_gn_pair(self.norm_out_lidar2, u32), cout.packed_dup(), pad=cout.padding, clamp=clamp)
             if self.lidar_adapter:
                 h, t32 = self.res_block_lidar1.forward_trunk(h, t32)
                 # (GroupNorm + swish of the adapter: a new stream, not a residual update -- model.py:617-618)
@@ -412,8 +423,10 @@ class Decoder(nn.Module):
             else:
                 h = _gn_swish(self.norm_out, h)
                 cout = self.conv_out
-            return ops.conv_small_cout(h, cout.packed_tap_major(), pad=cout.padding, clamp=clamp)
-        h = ops.igemm(zin, self.conv_in.packed_thin(), pad=(1, 1))
+            with ops.health_scope("conv_out_lidar" if self.lidar_adapter else "conv_out"):
+                return ops.conv_small_cout(h, cout.packed_tap_major(), pad=cout.padding, clamp=clamp)
+        with ops.health_scope("conv_in"):
+            h = ops.igemm(zin, self.conv_in.packed_thin(), pad=(1, 1))
         h = self.mid.block_2(self.mid.attn_1(self.mid.block_1(h)))
         for i_level in reversed(range(self.num_resolutions)):
             for i_block in range(self.num_res_blocks + 1):
@@ -427,4 +440,5 @@ class Decoder(nn.Module):
         else:
             h = _gn_swish(self.norm_out, h)
             cout = self.conv_out
-        return ops.conv_small_cout(h, cout.packed_tap_major(), pad=cout.padding, clamp=clamp)
+        with ops.health_scope("conv_out_lidar" if self.lidar_adapter else "conv_out"):
+            return ops.conv_small_cout(h, cout.packed_tap_major(), pad=cout.padding, clamp=clamp)

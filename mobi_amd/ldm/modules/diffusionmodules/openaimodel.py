@@ -287,5 +287,6 @@ class UNetModel(nn.Module):
                 h = module(h, embd, context, skip=hs.pop(), then_groupnorm=then_gn)
         n0 = self.out[0]
         g, b = n0.affine()
-        h = ops.groupnorm(h, g, b, n0.eps, silu=True)
-        return ops.conv_small_cout(h, self.out[2].packed_tap_major(), pad=self.out[2].padding)
+        with ops.health_scope("out"):
+            h = ops.groupnorm(h, g, b, n0.eps, silu=True)
+            return ops.conv_small_cout(h, self.out[2].packed_tap_major(), pad=self.out[2].padding)

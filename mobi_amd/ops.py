@@ -28,6 +28,48 @@ def set_profiler(sink):
     _PROFILE = sink
 
 
+# optional numeric-health sink (mobi_amd/health.py, `health.probe()`): an object whose measure(kind, tensor) runs one
+# mobi_tensor_health launch over a tensor a launch has just written, on the same stream.  None: one `is None` test per launch.
+_HEALTH = None
+
+
+def set_health(sink):
+    global _HEALTH
+    _HEALTH = sink
+
+
+class _NoScope:
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        return False
+
+
+_NO_SCOPE = _NoScope()
+
+
+def health_scope(name):
+    """Labels the rows of the launches inside it `<current module path>.<name>` while a health probe is active (for launches a
+    module issues on behalf of a child it never calls, such as UNetModel's closing `out` block); nothing otherwise."""
+    return _NO_SCOPE if _HEALTH is None else _HEALTH.scope(name)
+
+
+def health_labelled(method):
+    """Decorator for a module's block body that its owner calls directly, not through `module(...)` (the autoencoders'
+    forward_stream / forward_precise / forward_trunk): while a health probe is active the rows of its launches carry the module's
+    own path, as if it had been called; otherwise one `is None` test."""
+    import functools
+
+    @functools.wraps(method)
+    def labelled(self, *args, **kwargs):
+        if _HEALTH is None:
+            return method(self, *args, **kwargs)
+        with _HEALTH.scope(self):
+            return method(self, *args, **kwargs)
+    return labelled
+
+
 class _Timed:
     """Brackets one launch with events on the launch stream when a profiler is installed."""
 
@@ -63,7 +105,7 @@ def set_concurrency(flag):
 
 def concurrently(*fns):
     """Run independent launch sequences concurrently; returns their results in order."""
-    if not _CONCURRENT or _PROFILE is not None or len(fns) == 1:
+    if not _CONCURRENT or _PROFILE is not None or _HEALTH is not None or len(fns) == 1:
         return [f() for f in fns]
     main = torch.cuda.current_stream()
     key = (main.device, main.cuda_stream)
@@ -296,6 +338,8 @@ def ff_geglu(x, pf: PackedFf, residual=None, out=None, ln=None):
     reads = 1 + (residual is not None and (ln is None or residual.data_ptr() != x.data_ptr()))
     with _Timed("ff_geglu", fl, 2.0 * rows * pf.c * (reads + 1), f"rows={rows} c={pf.c} hidden={pf.hidden}"):
         _lib.check(lib.mobi_ff_geglu(C.byref(p), _stream()), "mobi_ff_geglu")
+    if _HEALTH is not None:
+        _HEALTH.measure("ff_geglu", out)
     return out
 
 
@@ -361,7 +405,7 @@ class ChainProgram:
     product's operand; what adapter / rowstats / store work on) and a residual `r` that a `resid` product consumes."""
 
     def __init__(self):
-        self.ops, self.keep = [], []
+        self.ops, self.keep, self.dsts = [], [], []
 
     def _op(self, code, flags=0):
         o = _lib.ChainOp()
@@ -397,6 +441,7 @@ class ChainProgram:
         o.dst, o.dst_img_stride, o.dst_row_stride = self._rows(dst)
         o.dst_img_div = dst_img_div
         self.keep.append(dst)
+        self.dsts.append(dst)
 
     def product(self, cw: ChainWeight, *, fold=False, resid=False, to_s=False, dst=None, dst_img_div=1, bias=None,
                 bias_img_stride=0, bias_img_div=1):
@@ -467,6 +512,14 @@ def row_chain(programs, images, rows_per_image, dtype, adapter=None, flops=0.0, 
         p.ad_image, p.ad_eps = _ptr(image), eps
     with _Timed("row_chain", flops, nbytes, note):
         _lib.check(lib.mobi_row_chain(C.byref(p), _stream()), "mobi_row_chain")
+    if _HEALTH is not None:
+        seen = set()
+        for prog in programs:
+            for d in prog.dsts:                              # (two programs may store into the halves of one tensor)
+                key = (d.data_ptr(), tuple(d.shape), tuple(d.stride()))
+                if key not in seen:
+                    seen.add(key)
+                    _HEALTH.measure("row_chain", d)
 
 
 # --------------------------------------------------------------------------------------
@@ -478,6 +531,9 @@ def trunk_add(trunk, inc, dtype):
     assert trunk.dtype == torch.float32 and trunk.is_contiguous() and (inc is None or (inc.is_contiguous() and inc.shape == trunk.shape))
     x16 = torch.empty(trunk.shape, device=trunk.device, dtype=dtype)
     _lib.check(lib.mobi_trunk_add(_ptr(trunk), _ptr(inc), _ptr(x16), trunk.numel(), _dt(dtype), _stream()), "mobi_trunk_add")
+    if _HEALTH is not None:
+        _HEALTH.measure("trunk_add", trunk)
+        _HEALTH.measure("trunk_add", x16)
     return x16
 
 
@@ -488,6 +544,8 @@ def split_f32(x32, dtype, parts=2):
     c = x32.shape[-1]
     out = torch.empty(tuple(x32.shape[:-1]) + (parts * c,), device=x32.device, dtype=dtype)
     _lib.check(lib.mobi_split_f32(_ptr(x32), _ptr(out), x32.numel() // c, c, parts, _dt(dtype), _stream()), "mobi_split_f32")
+    if _HEALTH is not None:
+        _HEALTH.measure("split_f32", out)
     return out
 
 
@@ -766,6 +824,55 @@ def snapshot_multi(table):
     return rec
 
 
+HEALTH_DTYPE_MAX = {torch.float16: 65504.0, torch.bfloat16: 3.3895313892515355e38, torch.float32: 3.4028234663852886e38}
+_HEALTH_DT = {torch.float16: MOBI_F16, torch.bfloat16: MOBI_BF16, torch.float32: _lib.MOBI_F32}
+
+
+def tensor_health(tensors, near=0.5, *, near_abs=None, out=None):
+    """The numeric health records of dense device tensors (fp16, bf16 or fp32, mixed, any number of them): `mobi_tensor_health`,
+    one launch per 64 tensors on the current stream -> the device records, int64 [len(tensors), 5] (`_lib.HealthRecord`: word 0
+    holds absmax_bits in its low half, then inf, nan, near, subnormal).  near: the fraction of each tensor's dtype maximum from
+    which an element counts as near the ceiling; near_abs: the thresholds themselves, one per tensor, instead.  out: an int64
+    [>= len(tensors), 5] dense device buffer to write into (the probe's record buffer) instead of a fresh tensor.
+    `read_tensor_health` brings the records to the host."""
+    lib = _lib.load()
+    tensors = list(tensors)
+    count = len(tensors)
+    words = C.sizeof(_lib.HealthRecord) // 8
+    if count == 0:
+        return torch.empty((0, words), dtype=torch.int64) if out is None else out[:0]
+    for t in tensors:
+        if t.dtype not in _HEALTH_DT:
+            raise TypeError(f"tensor_health takes float16, bfloat16 and float32 tensors, got {t.dtype}")
+        if not _dev(t).is_contiguous():
+            raise ValueError("tensor_health takes dense tensors")
+    if near_abs is None:
+        near_abs = [float(near) * HEALTH_DTYPE_MAX[t.dtype] for t in tensors]
+    assert len(near_abs) == count
+    if out is None:
+        out = torch.empty((count, words), dtype=torch.int64, device=tensors[0].device)
+    assert out.dtype == torch.int64 and out.is_contiguous() and out.shape[0] >= count and out.shape[1] == words
+    table = (_lib.HealthTensor * min(count, _lib.HEALTH_MAX_TENSORS))()
+    for lo in range(0, count, _lib.HEALTH_MAX_TENSORS):
+        part = tensors[lo:lo + _lib.HEALTH_MAX_TENSORS]
+        for i, t in enumerate(part):
+            e = table[i]
+            e.x, e.n, e.dtype, e.near_abs = t.data_ptr(), t.numel(), _HEALTH_DT[t.dtype], near_abs[lo + i]
+        _lib.check(lib.mobi_tensor_health(table, len(part), _ptr(out[lo:]), _stream()), "mobi_tensor_health")
+    return out[:count]
+
+
+def read_tensor_health(rec):
+    """The device records of `tensor_health` -> a list of dicts {absmax_bits, absmax, inf, nan, near, subnormal} per tensor.
+    One blocking copy of 40 bytes per tensor."""
+    import numpy as np
+    host = rec.cpu().numpy().reshape(-1, C.sizeof(_lib.HealthRecord) // 8)
+    bits = (host[:, 0] & 0xffffffff).astype(np.uint32)
+    absmax = bits.view(np.float32)
+    return [{"absmax_bits": int(bits[i]), "absmax": float(absmax[i]), "inf": int(host[i, 1]), "nan": int(host[i, 2]),
+             "near": int(host[i, 3]), "subnormal": int(host[i, 4])} for i in range(host.shape[0])]
+
+
 def read_snapshot_records(rec):
     """The device records of `snapshot_multi` -> [(digest: int in [0, 2^64), nonfinite: bool)] per pair.  One blocking copy of
     16 bytes per pair."""
@@ -927,6 +1034,7 @@ class Deferred:
 
     def __init__(self, tensor, params, ws, refs, keep):
         self.tensor, self.params, self.ws, self.refs, self.keep = tensor, params, ws, refs, keep
+        self.label = None if _HEALTH is None else _HEALTH.label()     # the producer's module path: its row is made where it is summed
         self.count = _lib.load().mobi_igemm_slab_count(C.byref(params))
         assert self.count >= 2, self.count
         self.done = False
@@ -951,6 +1059,8 @@ class Deferred:
                         f"m={m} n={self.params.n_packed} slabs={self.count}"):
                 _lib.check(_lib.load().mobi_igemm_finish(C.byref(self.params), _stream()), "mobi_igemm_finish")
             self._release()
+            if _HEALTH is not None:
+                _HEALTH.measure("split_finish", self.tensor, label=self.label)
         return self.tensor
 
     def _release(self):
@@ -1058,6 +1168,8 @@ def igemm(x, pw: Packed, *, x2=None, stride=1, pad=None, upsample=False, hout=No
     if deferred:
         # (`refs`: the operands the finishing launch reads must outlive this call)
         return Deferred(out, p, ws, (pw, rowvec, residual, x, x2), keep=defer == "keep")
+    if _HEALTH is not None:
+        _HEALTH.measure("igemm", out)
     return out
 
 
@@ -1128,6 +1240,10 @@ def groupnorm(x, gamma, beta, eps, silu, x2=None, out_mode=GN_OUT_T, dtype=None)
         split._release()
         if not split.keep:
             split.tensor = None                              # (never written: nobody may read it)
+    if _HEALTH is not None:
+        if split is not None and split.keep:
+            _HEALTH.measure("groupnorm_sum", split.tensor, label=split.label)   # the producer's result, summed and written by this launch
+        _HEALTH.measure("groupnorm", out)
     return out
 
 
@@ -1144,6 +1260,8 @@ def layernorm(x, gamma, beta, eps=1e-5):
     p.gamma, p.beta, p.eps, p.dtype = _ptr(gamma), _ptr(beta), eps, _dt(x.dtype)
     with _Timed("layernorm", 0.0, 2.0 * out.numel() * 2):
         _lib.check(lib.mobi_layernorm(C.byref(p), _stream()), "mobi_layernorm")
+    if _HEALTH is not None:
+        _HEALTH.measure("layernorm", out)
     return out
 
 
@@ -1172,6 +1290,8 @@ def attention(q, k, v, heads, scale, v_rows=False, q_log2_scaled=False):
     p.images, p.heads, p.dh, p.tq, p.tk, p.scale, p.dtype = n, heads, dh, tq, tk, scale, _dt(q.dtype)
     with _Timed("attention", 4.0 * n * heads * tq * tk * dh, 0.0, f"n={n} heads={heads} tq={tq} tk={tk} dh={dh}"):
         _lib.check(lib.mobi_attention(C.byref(p), _stream()), "mobi_attention")
+    if _HEALTH is not None:
+        _HEALTH.measure("attention", out)
     return out
 
 
@@ -1185,6 +1305,8 @@ def ctx_attention(q, k, v, heads, scale):
     p.q, p.out, p.k, p.v = _ptr(q), _ptr(out), _ptr(k), _ptr(v)
     p.images, p.heads, p.dh, p.tq, p.tk, p.scale, p.dtype = n, heads, c // heads, t, k.shape[1], scale, _dt(q.dtype)
     _lib.check(lib.mobi_ctx_attention(C.byref(p), _stream()), "mobi_ctx_attention")
+    if _HEALTH is not None:
+        _HEALTH.measure("ctx_attention", out)
     return out
 
 
@@ -1230,6 +1352,10 @@ def two_key_adapter(x, a, a_sum, c, u, b, eps, out=None, ln_pair=None):
         nbytes += x.numel() * 2
     with _Timed("two_key_adapter", 0.0, nbytes):
         _lib.check(lib.mobi_two_key_adapter(C.byref(p), _stream()), "mobi_two_key_adapter")
+    if _HEALTH is not None:
+        _HEALTH.measure("two_key_adapter", out)
+        for tn in lns or ():
+            _HEALTH.measure("two_key_adapter_ln", tn)
     return out if lns is None else (out, lns)
 
 
@@ -1239,6 +1365,8 @@ def softmax_rows(s, dtype):
     out = torch.empty(s.shape, device=s.device, dtype=dtype)
     rows = s.numel() // s.shape[-1]
     _lib.check(lib.mobi_softmax_rows(_ptr(s), _ptr(out), rows, s.shape[-1], _dt(dtype), _stream()), "mobi_softmax_rows")
+    if _HEALTH is not None:
+        _HEALTH.measure("softmax_rows", out)
     return out
 
 
@@ -1260,6 +1388,8 @@ def skinny_linear(x, w, bias=None, pre_act=ACT_NONE, post_act=ACT_NONE, out=None
         p.weight, p.bias, p.out, p.n, p.out_row_stride = _ptr(w), _ptr(bias), _ptr(os_), n, out.stride(0)
         p.pre_act, p.post_act, p.dtype = pre_act, post_act, _dt(w.dtype)
         _lib.check(lib.mobi_skinny_linear(C.byref(p), _stream()), "mobi_skinny_linear")
+    if _HEALTH is not None:
+        _HEALTH.measure("skinny_linear", out)
     return out
 
 
@@ -1272,6 +1402,8 @@ def linear_f32(x, w, bias=None):
     out = torch.empty((x.shape[0], w.shape[0]), device=x.device, dtype=torch.float32)
     _lib.check(lib.mobi_linear_f32(_ptr(x), _ptr(w), _ptr(bias), _ptr(out), x.shape[0], w.shape[0], x.shape[1], x.stride(0),
                                    w.stride(0), out.stride(0), _stream()), "mobi_linear_f32")
+    if _HEALTH is not None:
+        _HEALTH.measure("linear_f32", out)
     return out
 
 
@@ -1282,6 +1414,8 @@ def layernorm_rows_f32(x, gamma, beta, eps=1e-5):
     out = torch.empty((x.shape[0], x.shape[1]), device=x.device, dtype=torch.float32)
     _lib.check(lib.mobi_layernorm_rows_f32(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(out), x.shape[0], x.shape[1], x.stride(0),
                                            out.stride(0), eps, _stream()), "mobi_layernorm_rows_f32")
+    if _HEALTH is not None:
+        _HEALTH.measure("layernorm_rows_f32", out)
     return out
 
 
@@ -1291,6 +1425,8 @@ def quick_gelu(x):
     assert x.is_contiguous() and x.numel() % 8 == 0
     out = torch.empty_like(x)
     _lib.check(lib.mobi_quick_gelu(_ptr(x), _ptr(out), x.numel(), _dt(x.dtype), _stream()), "mobi_quick_gelu")
+    if _HEALTH is not None:
+        _HEALTH.measure("quick_gelu", out)
     return out
 
 
@@ -1301,6 +1437,8 @@ def timestep_embedding(t, freqs):
     out = torch.empty((n, 2 * half), device=t.device, dtype=torch.float32)
     _lib.check(lib.mobi_timestep_embedding(_ptr(t), _ptr(freqs), _ptr(out), n, half, _stream()),
                "mobi_timestep_embedding")
+    if _HEALTH is not None:
+        _HEALTH.measure("timestep_embedding", out)
     return out
 
 
@@ -1322,6 +1460,8 @@ def conv_small_cin(srcs, weight, bias, kh, kw, pad, dtype, out_f32_nchw=False):
         out = torch.empty((n, h, w, cout), device=srcs[0].device, dtype=dtype)
     p.out, p.out_f32_nchw, p.dtype = _ptr(out), int(out_f32_nchw), _dt(dtype)
     _lib.check(lib.mobi_conv_small_cin(C.byref(p), _stream()), "mobi_conv_small_cin")
+    if _HEALTH is not None:
+        _HEALTH.measure("conv_small_cin", out)
     return out
 
 
@@ -1340,6 +1480,8 @@ def conv_small_cout(x, pw: Packed, pad=None, clamp=None):
         p.clamp, p.clamp_lo, p.clamp_hi = 1, clamp[0], clamp[1]
     p.in_scale, p.dtype = 1.0, _dt(x.dtype)
     _lib.check(lib.mobi_conv_small_cout(C.byref(p), _stream()), "mobi_conv_small_cout")
+    if _HEALTH is not None:
+        _HEALTH.measure("conv_small_cout", out)
     return out
 
 
@@ -1354,6 +1496,8 @@ def pack_sources(srcs, dtype, c_pad=32):
     out = torch.empty((n, h, w, c_pad), device=srcs[0].device, dtype=dtype)
     _lib.check(lib.mobi_pack_nchw_sources(_ptr(ss[0]), _ptr(ss[1]), _ptr(ss[2]), cs[0], cs[1], cs[2], n, h * w,
                                           c_pad, _ptr(out), _dt(dtype), _stream()), "mobi_pack_nchw_sources")
+    if _HEALTH is not None:
+        _HEALTH.measure("pack_sources", out)
     return out
 
 
@@ -1364,6 +1508,8 @@ def to_nhwc(x, dtype):
     assert x.dtype == torch.float32 and x.is_contiguous()
     out = torch.empty((n, h, w, c), device=x.device, dtype=dtype)
     _lib.check(lib.mobi_nchw_f32_to_nhwc(_ptr(x), _ptr(out), n, c, h * w, _dt(dtype), _stream()), "nchw_to_nhwc")
+    if _HEALTH is not None:
+        _HEALTH.measure("to_nhwc", out)
     return out
 
 
@@ -1373,6 +1519,8 @@ def to_nchw_f32(x):
     assert x.is_contiguous()
     out = torch.empty((n, c, h, w), device=x.device, dtype=torch.float32)
     _lib.check(lib.mobi_nhwc_to_nchw_f32(_ptr(x), _ptr(out), n, c, h * w, _dt(x.dtype), _stream()), "nhwc_to_nchw")
+    if _HEALTH is not None:
+        _HEALTH.measure("to_nchw_f32", out)
     return out
 
 
@@ -1397,6 +1545,8 @@ def ddim_step(x, e_cond, *, e_uncond=None, noise=None, cfg_scale=1.0, a_t=1.0, a
         assert coef_dev.dtype == torch.float32 and coef_dev.numel() == 4 and coef_dev.is_contiguous()
         p.coef_dev = _ptr(coef_dev)
     _lib.check(lib.mobi_ddim_step(C.byref(p), _stream()), "mobi_ddim_step")
+    if _HEALTH is not None:
+        _HEALTH.measure("sampler", x_prev, pred)             # ONE row per step: the two fp32 outputs of the update
     return x_prev, pred, e_out
 
 
@@ -1419,6 +1569,8 @@ def dpm_step(x, e_cond, x0_hist, *, e_uncond=None, cfg_scale=1.0, inv_alpha_s=1.
         assert coef_dev.dtype == torch.float32 and coef_dev.numel() == 5 and coef_dev.is_contiguous()
         p.coef_dev = _ptr(coef_dev)
     _lib.check(lib.mobi_dpm_step(C.byref(p), _stream()), "mobi_dpm_step")
+    if _HEALTH is not None:
+        _HEALTH.measure("sampler", x_next, pred)
     return x_next, pred
 
 
@@ -1429,6 +1581,8 @@ def lincomb4(es, cs):
     out = torch.empty_like(es[0])
     _lib.check(lib.mobi_lincomb4(_ptr(out), _ptr(es[0]), _ptr(es[1]), _ptr(es[2]), _ptr(es[3]),
                                  cs[0], cs[1], cs[2], cs[3], out.numel(), _stream()), "mobi_lincomb4")
+    if _HEALTH is not None:
+        _HEALTH.measure("lincomb4", out)
     return out
 
 
@@ -1441,6 +1595,8 @@ def q_sample(x0, noise, t, sqrt_ac, sqrt_1m_ac):
     out = torch.empty_like(x0)
     _lib.check(lib.mobi_q_sample(_ptr(x0), _ptr(noise), _ptr(t), _ptr(sqrt_ac), _ptr(sqrt_1m_ac), _ptr(out),
                                  x0.shape[0], x0[0].numel(), sqrt_ac.numel(), _stream()), "mobi_q_sample")
+    if _HEALTH is not None:
+        _HEALTH.measure("q_sample", out)
     return out
 
 
@@ -1487,6 +1643,8 @@ def mask_blend_(img, x0, noise, mask, sqrt_ac_t, sqrt_1m_ac_t):
     b, c, h, w = img.shape
     _lib.check(lib.mobi_mask_blend(_ptr(img), _ptr(x0), _ptr(noise), _ptr(mask), sqrt_ac_t, sqrt_1m_ac_t,
                                    b, c, h * w, _stream()), "mobi_mask_blend")
+    if _HEALTH is not None:
+        _HEALTH.measure("mask_blend", img)
     return img
 
 
@@ -1504,6 +1662,8 @@ def range_denorm(sample, min_d=None, max_d=None, alpha=0.75, object_norm=True, i
     _lib.check(lib.mobi_range_denorm(_ptr(sample), _ptr(min_d), _ptr(max_d), f32(alpha), f32(2 * alpha), f32(alpha - 1),
                                      f32(1 - alpha), int(object_norm), int(int_norm), _ptr(depth), _ptr(inten), b, h * w,
                                      _stream()), "mobi_range_denorm")
+    if _HEALTH is not None:
+        _HEALTH.measure("range_denorm", depth, inten)
     return depth, inten
 
 
@@ -1513,6 +1673,8 @@ def posterior_sample(moments, noise, out, c_off, scale):
     c = c2 // 2
     _lib.check(lib.mobi_posterior_sample(_ptr(moments), _ptr(noise), _ptr(out), b, c, h * w, out.shape[1], c_off,
                                          scale, _stream()), "mobi_posterior_sample")
+    if _HEALTH is not None:
+        _HEALTH.measure("posterior_sample", out[:, c_off:c_off + c])
     return out
 
 
@@ -1531,6 +1693,8 @@ def nearest_resize(src, hout, wout, out=None, c_off=0):
         view = out[:, c_off]
         _lib.check(lib.mobi_nearest_resize(_ptr(src), C.c_void_p(view.data_ptr()), b, h, w, hout, wout,
                                            ct * hout * wout, _stream()), "mobi_nearest_resize")
+    if _HEALTH is not None:
+        _HEALTH.measure("nearest_resize", out if ct == c else out[:, c_off:c_off + 1])
     return out
 
 
