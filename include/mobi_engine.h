@@ -80,8 +80,8 @@ size_t mobi_struct_size(int id);
 /* Development hook: the library reads its MOBI_* A/B environment variables once, at the first launch
  * (mobi_amd/csrc/tuning.h lists them); this re-reads them.  Not needed by a product caller. */
 int mobi_tuning_reload(void);
-/* Bit 0: the library was built with -DMOBI_DEV, i.e. it also carries the A/B partner kernels (lockstep direct-to-LDS
- * igemm, fast-addressing register-staged igemm, software-pipelined attention) that the shipped build leaves out. */
+/* Always 0.  Bit 0 used to mark a development build that also carried measured-slower A/B partner kernels; there is one
+ * build now, and the symbol stays so that the ABI does not change. */
 int mobi_build_info(void);
 
 /* ---------------------------------------------------------------------------
@@ -145,10 +145,10 @@ typedef struct mobi_igemm_params {
                             sums them and applies the epilogue.  Not with GEGLU / transposed /
                             per-image weights.                                              */
   void* ws;              /* mobi_igemm_workspace_bytes(p, split_k) bytes, 16-byte aligned  */
-  int32_t k_order;       /* layout of W's k axis.  0: k = tap*C + c.  1: k = (c/64)*taps*64 + tap*64
-                            + c%64 -- the taps of one 64-channel slice are consecutive k-tiles, so the
-                            9 reads of a 3x3 window's pixels hit L2 instead of being re-fetched per
-                            tap.  Needs C % 64 == 0 (and c0 % 64 == 0 with two sources).        */
+  int32_t k_order;       /* layout of W's k axis.  0: k = tap*C + c, the only one accepted.  1 (k =
+                            (c/64)*taps*64 + tap*64 + c%64, the taps of one 64-channel slice as consecutive
+                            k-tiles) measured slower and is answered with MOBI_ERR_UNSUPPORTED; any other
+                            value with MOBI_ERR_ARG.  The field stays for the struct's layout.    */
   const void* weight_tiled; /* optional second copy of W (k_order 0, groups 1, n_packed % 16 == 0, k % 32 == 0) as
                             [n_packed / 16][k / 32] blocks of 1 KiB: block (p, s) is the LDS image of rows 16 p .. 16 p + 15,
                             k 32 s .. 32 s + 31 -- row r at bytes 64 r, its four 16-byte chunks c at slot c ^ P[(r >> 2) & 3],

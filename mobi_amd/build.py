@@ -53,9 +53,10 @@ def sources_sha16():
 
 
 def _flags_id():
-    """What the library was compiled with besides the sources: a library built with A/B or debug flags
-    (`MOBI_HIPCC_FLAGS=-DMOBI_DBG_...`, timing-only variants with WRONG results) must never pass as current
-    for a plain build, whatever its mtime says."""
+    """What the library was compiled with besides the sources.  There is one build and one set of kernels; what
+    `MOBI_HIPCC_FLAGS` can still change are the compile-time schedule and instrumentation macros (`-DMOBI_PP_...`,
+    `-DMOBI_STAMP=...`, `-DMOBI_DBG_...`: some are timing-only variants with WRONG results), and a library built
+    with any of them must never pass as current for a plain build, whatever its mtime says."""
     return repr((ARCH, os.environ.get("MOBI_HIPCC_FLAGS", "").split(), sorted(EXTRA.items())))
 
 

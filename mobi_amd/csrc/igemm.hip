@@ -13,10 +13,10 @@
 //                      two waves of a SIMD one phase apart: LOAD | MATRIX), deferred register epilogue.  Every
 //                      launch whose tiles are full, whose output is row-major T and that has at most one of
 //                      bias / per-image vector; also the split-K launches with long k ranges (fp32 slabs).
-//   igemm_glds_kernel  same geometry in lockstep, LDS-staged epilogues (transposed / fp32 / ragged / bias AND vector)
 //   igemm_ring_kernel    128-pixel tiles, four waves, two blocks per CU, operands by LDS-DMA into a ring of four 32-deep
-//                      k-slots: small m, split-K ranges, ragged tiles, every output mode
-//   igemm_kernel       128- / 256-pixel tiles staged through registers: operands beyond 2 GB, chunk-major k
+//                      k-slots: small m, split-K ranges, ragged tiles, every output mode; as 256 x 320 tiles also the
+//                      256-pixel launches that need an LDS-staged epilogue (transposed / fp32 / ragged / bias AND vector)
+//   igemm_kernel       128- / 256-pixel tiles staged through registers, generic gather: operands beyond 2 GB
 #include <stdlib.h>
 
 #include <type_traits>
@@ -154,7 +154,7 @@ struct IgemmArgs {
                            // list) then streams ITS slice of the weights instead of all of them (launches whose weights
                            // outweigh their activations: the 16 x 16 / 8 x 8 levels)
   int src0_bytes, src1_bytes, w_bytes, fast, glds;
-  int k_order;             // 0: k = tap*C + c;  1: k = (c/64)*taps*64 + tap*64 + c%64 (FAST shapes only)   // buffer extents for the FAST path's descriptors
+  int k_order;             // always 0 (k = tap*C + c); igemm_pp_kernel still tests it (the field is part of the argument block)
   int wm;                  // waves along the pixel axis (2 or 4): block tile = 64*wm pixels
   int splits, nk_per;      // split-K: blockIdx.y owns k-tiles [y*nk_per, (y+1)*nk_per)
   float* split_ws;         // f32 [splits][M][n_packed] partial sums (NULL: single pass)
@@ -167,7 +167,7 @@ struct IgemmArgs {
   int sm_direct;           // 128 x 160 ring tiles: register epilogue / register slab stores (full tiles)
   const void* w_tiled;     // W as 1-KiB request images (ring kernels), or NULL
   int sm64;                // 128-pixel tiles on the 64-deep-step kernel (igemm_ring64_kernel)
-  int lin_window;          // direct-to-LDS kernel: window pixels are linear in the tap (no upsampling, <= 16 taps)
+  int lin_window;          // always 0 (kept: the struct is the kernels' argument block)
   int epi_direct;          // direct-to-LDS kernel: register epilogue (full tiles, row-major T output)
   int pp;                  // register-epilogue launch on the ping-pong kernel
   int sm;                  // 128-pixel tiles on the LDS-DMA ring kernel (igemm_ring_kernel<.., false>)
@@ -883,11 +883,9 @@ __device__ __forceinline__ int pp_epilogue(const IgemmArgs& a, f32x4 (&acc)[NT][
 // WM = waves along the pixel axis: 2 -> 128-pixel tile, 4 waves, two blocks per CU;
 //                                  4 -> 256-pixel tile, 8 waves, one block per CU (weight tile shared by
 //                                       twice the pixels: fewer LDS writes and L2 reads per FLOP).
-// FAST: channel counts are multiples of 64 (and the concat boundary too), so one k-tile lies inside one filter tap
-//       of one source.  Tap / source / channel bookkeeping is then wave-uniform (SALU), operands are fetched
-//       with buffer loads (SGPR descriptor + 32-bit offset, out-of-range offset = hardware zero fill), and the
-//       per-lane address work per k-tile drops to one add + one select per 16-byte piece.
-template <typename T, int NT, bool TR, int WM, bool FAST>
+// Operands by generic gather (64-bit addresses, per-lane tap / source / channel bookkeeping): the fallback for operands
+// beyond the 2 GB that the other kernels' 32-bit buffer offsets reach.
+template <typename T, int NT, bool TR, int WM>
 __global__ __launch_bounds__(128 * WM, 2) void igemm_kernel(const IgemmArgs a) {
   typedef typename Vec8<T>::type frag_t;
   constexpr int NTHREADS = 128 * WM;
@@ -980,65 +978,7 @@ __global__ __launch_bounds__(128 * WM, 2) void igemm_kernel(const IgemmArgs a) {
   unsigned ok0 = 0, ok1 = 0;
   const T* const zsrc = reinterpret_cast<const T*>(g_zero16);
 
-  // ---- FAST path state (all wave-uniform) ----------------------------------------------------------------
-  int u_tap = 0, u_ky = 0, u_kx = 0, u_c = 0;           // tap and channel offset (multiple of 64) of the next tile
-  unsigned f_row[4] = {0u, 0u, 0u, 0u};                 // byte offset of each row's pixel in the current source/tap
-  unsigned f_w[WP];                                     // byte offset of each weight row (out of range if invalid)
-  int f_tap = -1, f_src = -1;
-  if constexpr (FAST) {
-    const long long c_first = (long long)kt_begin * 64;
-    if (a.k_order) {                       // channel-chunk-major k: tile = (64-channel chunk, tap), taps innermost
-      const int taps_ = a.kh * a.kw;
-      const int cc = kt_begin / taps_;
-      u_tap = kt_begin - cc * taps_; u_c = cc * 64;
-    } else {                               // tap-major k: tile = (tap, 64-channel chunk)
-      u_tap = (int)(c_first / a.C); u_c = (int)(c_first - (long long)u_tap * a.C);
-    }
-    u_ky = u_tap / a.kw; u_kx = u_tap - u_ky * a.kw;
-#pragma unroll
-    for (int i = 0; i < WP; ++i) {
-      const int n = n0 + row_b + RP * i;
-      const bool ok = (row_b + RP * i < BN) && n < a.n_packed;
-      f_w[i] = ok ? (unsigned)n * (unsigned)a.ktot * 2u + (unsigned)seg * 16u : 0x80000000u;
-    }
-  }
-  auto load_tile_fast = [&](int kt, u32x4 (&xr)[4], u32x4 (&wr)[WP]) {
-    const bool tile_ok = kt < kt_end;                         // uniform
-    const int src = u_c >= a.c0 ? 1 : 0;                       // uniform
-    if (u_tap != f_tap || src != f_src) {                      // uniform branch, no loads inside
-      f_tap = u_tap; f_src = src;
-      const unsigned cs2 = (unsigned)(src ? a.c1 : a.c0) * 2u;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int hi = x_h[i] + u_ky, wi = x_w[i] + u_kx;
-        const bool ok = ((x_okm >> i) & 1u) && hi >= 0 && hi < hlog && wi >= 0 && wi < wlog;
-        const unsigned pix = (unsigned)(x_gp[i] + (hi >> a.up) * a.win + (wi >> a.up));
-        f_row[i] = ok ? pix * cs2 + (unsigned)seg * 16u : 0x80000000u;
-      }
-    }
-    // descriptors are rebuilt from scalars every tile (a few SALU ops); a tile past the k range gets 0 records,
-    // i.e. every piece of it reads as zero
-    const void* xbase = src ? a.src1 : a.src0;
-    const int xbytes = tile_ok ? (src ? a.src1_bytes : a.src0_bytes) : 0;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(xbase), 0, xbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(wgt), 0, tile_ok ? a.w_bytes : 0, 0x00020000);
-    const unsigned chb = (unsigned)(src ? u_c - a.c0 : u_c) * 2u;    // uniform channel byte offset
-#pragma unroll
-    for (int i = 0; i < 4; ++i) xr[i] = __builtin_amdgcn_raw_buffer_load_b128(rx, f_row[i] + chb, 0, 0);
-    const unsigned kb = (unsigned)kt * 128u;
-#pragma unroll
-    for (int i = 0; i < WP; ++i) wr[i] = __builtin_amdgcn_raw_buffer_load_b128(rw, f_w[i] + kb, 0, 0);
-    if (a.k_order) {
-      ++u_tap;
-      if (++u_kx == a.kw) { u_kx = 0; if (++u_ky == a.kh) { u_ky = 0; u_tap = 0; u_c += 64; } }
-    } else {
-      u_c += 64;
-      if (u_c >= a.C) { u_c = 0; ++u_tap; if (++u_kx == a.kw) { u_kx = 0; ++u_ky; } }
-    }
-  };
-
-  auto load_tile_generic = [&](int kt, u32x4 (&xr)[4], u32x4 (&wr)[WP], unsigned& okm) {
+  auto load_tile = [&](int kt, u32x4 (&xr)[4], u32x4 (&wr)[WP], unsigned& okm) {
     if (tap != t_tap) {                       // no loads inside this branch
       t_tap = tap;
       t_okm = 0;
@@ -1076,10 +1016,6 @@ __global__ __launch_bounds__(128 * WM, 2) void igemm_kernel(const IgemmArgs a) {
     // advance this thread's chunk by one k-tile (two chunks)
     cc += 2;
     while (cc >= cpt) { cc -= cpt; ++tap; if (++kx == a.kw) { kx = 0; ++ky; } }
-  };
-  auto load_tile = [&](int kt, u32x4 (&xr)[4], u32x4 (&wr)[WP], unsigned& okm) {
-    if constexpr (FAST) load_tile_fast(kt, xr, wr);
-    else load_tile_generic(kt, xr, wr, okm);
   };
   auto store_tile = [&](int buf, const u32x4 (&xr)[4], const u32x4 (&wr)[WP], unsigned okm) {
     unsigned char* xb = lds + buf * X_TILE;
@@ -1159,316 +1095,6 @@ __global__ __launch_bounds__(128 * WM, 2) void igemm_kernel(const IgemmArgs a) {
   float* stage = reinterpret_cast<float*>(lds) + wave * (STAGE_BYTES / 4);
   igemm_epilogue<T, NT, TR, 32>(a, stage, acc, lane, group, n0 + wn * WAVE_N, m0 + wm * 64);
 }
-
-#ifdef MOBI_DEV   // development build only (A/B partner of the ping-pong kernel, MOBI_IGEMM_PP=0): the shipped library routes
-                  // every launch it used to take (LDS-staged epilogues of the 256-pixel geometry) to igemm_ring_kernel
-// =========================================================================================================
-// Direct-to-LDS main loop (FAST shapes only):  256 pixels x (2 * WAVE_N) channels, 8 waves (4 x 2), THREE LDS
-// stages filled by global_load_lds_dwordx4 (no VGPR staging, no ds_write), one raw s_barrier per k-tile and a
-// COUNTED s_waitcnt vmcnt: the tile being multiplied is complete while the next tile's DMA stays in flight.
-//   step i:  wait(k-tile i landed) ; barrier ; issue DMA of k-tile i+2 into stage (i+2)%3 ; multiply stage i%3
-// The barrier also proves every wave finished reading stage (i-1)%3 == (i+2)%3 before it is overwritten.
-//
-// PERSISTENT: one block per CU walks output tiles blockIdx.x, +gridDim.x, ...; the k-tile sequence runs on
-// ACROSS output tiles, so the first two k-tiles of the next output tile are already in flight while this tile's
-// epilogue runs (measured per output tile before: 3.1 us entry-to-first-tile + 1.2 us block turnaround, every
-// tile; now once per block).  The epilogue stages through the LDS stage of the tile's LAST k-tile, the only one
-// that is free at that point (the other two are DMA targets).
-// LDS image = [row][8 x 16 B], lane-linear per wave instruction (8 rows = 1 KiB); the XOR swizzle is applied on
-// the SOURCE side: the lane that fills slot s of row r fetches piece s ^ (r & 7).  Padded / out-of-range pieces
-// are fetched from the 16-byte zero block.
-// =========================================================================================================
-// MODE 0: LDS-staged epilogue, row-major output    1: LDS-staged epilogue, transposed output
-//      2: register epilogue (plain)                  3: register epilogue (GEGLU)
-template <typename T, int NT, int MODE>
-__global__ __launch_bounds__(512, 2) void igemm_glds_kernel(const IgemmArgs a) {
-  typedef typename Vec8<T>::type frag_t;
-  constexpr bool TR = MODE == 1;
-  constexpr bool DIRECT = MODE >= 2;
-  constexpr int BM = 256;
-  constexpr int WAVE_N = NT * 16;
-  constexpr int BN = 2 * WAVE_N;
-  constexpr int X_TILE = BM * 128, W_TILE = BN * 128;
-  constexpr int STAGE = X_TILE + W_TILE;
-  constexpr int WJ = (BN + 63) / 64;                         // weight DMA instructions per thread and tile
-  constexpr int PIECES = 4 + WJ;                             // DMA instructions per thread and tile
-  constexpr int RPP = 16;                                    // epilogue rows per pass: 8 wave stages fit one k-stage
-  constexpr int EPI_WAVE = EpiGeom<RPP, TR, NT>::BYTES;
-  static_assert(8 * EPI_WAVE <= STAGE, "the epilogue must fit the one free k-stage");
-  static_assert(PIECES == 6 || PIECES == 7, "vmcnt immediates below");
-  __shared__ __attribute__((aligned(16))) unsigned char lds[3 * STAGE];
-  typedef __attribute__((address_space(3))) void* lds_ptr_t;
-  typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave & 3, wn = wave >> 2;
-  const int group = blockIdx.z;
-  const int nblk = a.tiles_m * a.tiles_n;
-  MOBI_STAMP_AT(0);
-  const T* __restrict__ wgt = reinterpret_cast<const T*>(a.weight) + (long long)group * a.w_group_stride;
-  const unsigned char* const zsrc = reinterpret_cast<const unsigned char*>(g_zero16);
-
-  const int rloc = lane >> 3;                                // row inside the wave's 8-row DMA piece
-  const int sg = (lane & 7) ^ rloc;                          // source piece that lands in this lane's slot
-  const int kt_begin = blockIdx.y * a.nk_per;
-  const int kt_end = min(a.nk, kt_begin + a.nk_per);
-  const int hlog = a.hin << a.up, wlog = a.win << a.up;
-
-  // ---- fetch side: state of the output tile whose k-tiles are being requested --------------------------------
-  int f_bid = blockIdx.x;                                    // output tile being fetched (>= nblk: nothing left)
-  int f_kt = kt_begin;                                       // its next k-tile
-  int f_slot = 0;                                            // LDS stage of the next request (0, 1, 2, 0, ...)
-  int x_gp[4], x_h[4], x_w[4];                               // activation rows of this thread: 8 * wave + rloc + 64 j
-  unsigned x_okm = 0;
-  const unsigned char* w_src[WJ];
-  int w_lds[WJ];
-  int u_tap = 0, u_ky = 0, u_kx = 0, u_c = 0;                // wave-uniform (tap, channel offset) of the next k-tile
-  unsigned f_row[4] = {0u, 0u, 0u, 0u};
-  unsigned f_okm = 0;
-  int f_tap = -1, f_src = -1;
-  // linear window (no upsampling, <= 16 taps): pixel(tap) = x_pix0[j] + ky * win + kx, so a tap change costs one
-  // wave-uniform offset and a mask shift instead of re-deriving four windows (what made the taps-innermost k order
-  // slower than it had to be)
-  const bool lin = a.lin_window != 0;
-  int x_pix0[4] = {0, 0, 0, 0};                              // x_gp + x_h * win + x_w (may be "negative": only used when valid)
-  unsigned long long x_tapok = 0;                            // bit 4 * tap + j: row j's window pixel of that tap is inside
-  unsigned f_rowbase[4] = {0u, 0u, 0u, 0u};
-  unsigned f_tapoff = 0;
-
-  auto set_fetch_tile = [&]() {
-    const int L = xcd_remap(f_bid, nblk);
-    MOBI_TILE_OF(L, tile_m, tile_n);
-    const int m0 = tile_m * BM, n0 = tile_n * BN;
-    x_okm = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int m = m0 + 8 * wave + rloc + 64 * j;
-      const bool ok = m < a.M;
-      x_okm |= ok ? (1u << j) : 0u;
-      const int mm = ok ? m : 0;
-      const int img = mm / a.hw_out, rem = mm - img * a.hw_out;
-      const int ho = rem / a.wout, wo = rem - ho * a.wout;
-      x_gp[j] = (group * a.imgs_per_group + img) * a.img_pix_stride;
-      x_h[j] = ho * a.stride - a.pad_h;
-      x_w[j] = wo * a.stride - a.pad_w;
-    }
-    if (lin) {
-      x_tapok = 0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        x_pix0[j] = x_gp[j] + x_h[j] * a.win + x_w[j];
-        if ((x_okm >> j) & 1u) {
-          for (int ky = 0; ky < a.kh; ++ky)
-            for (int kx = 0; kx < a.kw; ++kx) {
-              const int hi = x_h[j] + ky, wi = x_w[j] + kx;
-              if (hi >= 0 && hi < hlog && wi >= 0 && wi < wlog) x_tapok |= 1ull << ((ky * a.kw + kx) * 4 + j);
-            }
-        }
-      }
-    }
-    // weight rows: j < WJ-1 (or all, when BN % 64 == 0): 8 * wave + rloc + 64 j; the last partial group of 32 rows
-    // is fetched by waves 0-3 and (identically, benign duplicate) by waves 4-7 so that every wave issues PIECES DMAs
-#pragma unroll
-    for (int j = 0; j < WJ; ++j) {
-      const bool partial = (BN % 64 != 0) && (j == WJ - 1);
-      const int r = partial ? 64 * j + 8 * (wave & 3) + rloc : 64 * j + 8 * wave + rloc;
-      const int n = n0 + r;
-      w_lds[j] = (partial ? 64 * j + 8 * (wave & 3) : 64 * j + 8 * wave) * 128;
-      w_src[j] = n < a.n_packed ? reinterpret_cast<const unsigned char*>(wgt + (long long)n * a.ktot) + sg * 16 : nullptr;
-    }
-    const long long c_first = (long long)kt_begin * 64;
-    if (a.k_order) {                       // channel-chunk-major k: tile = (64-channel chunk, tap), taps innermost
-      const int taps_ = a.kh * a.kw;
-      const int cc = kt_begin / taps_;
-      u_tap = kt_begin - cc * taps_; u_c = cc * 64;
-    } else {                               // tap-major k: tile = (tap, 64-channel chunk)
-      u_tap = (int)(c_first / a.C); u_c = (int)(c_first - (long long)u_tap * a.C);
-    }
-    u_ky = u_tap / a.kw; u_kx = u_tap - u_ky * a.kw;
-    f_tap = -1; f_src = -1;
-  };
-
-  // request the next k-tile of the sequence (caller checked f_bid < nblk) and advance the sequence
-  // every vector-memory instruction this wave issues is counted (wave-uniform); mk0 / mk1 / mk2 = the count right
-  // after the requests of the oldest / next / youngest k-tile that has not been multiplied yet
-  int vm_issued = 0, mk0 = 0, mk1 = 0, mk2 = 0;
-  auto issue_next = [&]() {
-    unsigned char* st = lds + f_slot * STAGE;
-    f_slot = f_slot == 2 ? 0 : f_slot + 1;
-    const int src = u_c >= a.c0 ? 1 : 0;
-    if (lin) {
-      if (src != f_src) {
-        f_src = src;
-        const unsigned cs2 = (unsigned)(src ? a.c1 : a.c0) * 2u;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) f_rowbase[j] = (unsigned)x_pix0[j] * cs2 + (unsigned)sg * 16u;
-        f_tap = -1;
-      }
-      if (u_tap != f_tap) {
-        f_tap = u_tap;
-        f_tapoff = (unsigned)(u_ky * a.win + u_kx) * ((unsigned)(src ? a.c1 : a.c0) * 2u);     // wave-uniform
-        f_okm = (unsigned)(x_tapok >> (u_tap * 4)) & 15u;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) f_row[j] = f_rowbase[j] + f_tapoff;
-      }
-    } else if (u_tap != f_tap || src != f_src) {
-      f_tap = u_tap; f_src = src; f_okm = 0;
-      const unsigned cs2 = (unsigned)(src ? a.c1 : a.c0) * 2u;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int hi = x_h[j] + u_ky, wi = x_w[j] + u_kx;
-        const bool ok = ((x_okm >> j) & 1u) && hi >= 0 && hi < hlog && wi >= 0 && wi < wlog;
-        f_okm |= ok ? (1u << j) : 0u;
-        f_row[j] = (unsigned)(x_gp[j] + (hi >> a.up) * a.win + (wi >> a.up)) * cs2 + (unsigned)sg * 16u;
-      }
-    }
-    const unsigned char* xbase = reinterpret_cast<const unsigned char*>(src ? a.src1 : a.src0) +
-                                 (unsigned)(src ? u_c - a.c0 : u_c) * 2u;
-#if !(MOBI_DBG_SKIP & 1)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const unsigned char* g = ((f_okm >> j) & 1u) ? xbase + f_row[j] : zsrc;
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)g, (lds_ptr_t)(st + (8 * wave + 64 * j) * 128), 16, 0, 0);
-    }
-    vm_issued += 4;
-#endif
-    const unsigned kb = (unsigned)f_kt * 128u;
-#if !(MOBI_DBG_SKIP & 2)
-#pragma unroll
-    for (int j = 0; j < WJ; ++j) {
-      const unsigned char* g = w_src[j] ? w_src[j] + kb : zsrc;
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)g, (lds_ptr_t)(st + X_TILE + w_lds[j]), 16, 0, 0);
-    }
-    vm_issued += WJ;
-#endif
-    if (++f_kt == kt_end) {                                  // the sequence moves on to this block's next output tile
-      f_kt = kt_begin;
-      f_bid += gridDim.x;
-      if (f_bid < nblk) set_fetch_tile();
-    } else if (a.k_order) {
-      ++u_tap;
-      if (++u_kx == a.kw) { u_kx = 0; if (++u_ky == a.kh) { u_ky = 0; u_tap = 0; u_c += 64; } }
-    } else {
-      u_c += 64;
-      if (u_c >= a.C) { u_c = 0; ++u_tap; if (++u_kx == a.kw) { u_kx = 0; ++u_ky; } }
-    }
-  };
-
-  const int r16 = lane & 15, g4 = lane >> 4;
-  f32x4 acc[NT][4];
-
-  if (kt_begin >= kt_end) return;                            // never launched: the host trims empty split-K ranges
-
-  set_fetch_tile();
-  int ahead = 0;                                             // requested k-tiles not yet multiplied
-  int c_slot = 0;                                            // LDS stage of the k-tile to multiply next
-  issue_next(); ++ahead; mk0 = vm_issued;
-  if (f_bid < nblk) { issue_next(); ++ahead; mk1 = vm_issued; }
-  DirectEpiRegs<DIRECT ? NT : 1> dq;
-  MOBI_PHASE_DECL;
-
-  for (int bid = blockIdx.x; bid < nblk; bid += gridDim.x) {
-#pragma unroll
-    for (int i = 0; i < NT; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const int L = xcd_remap(bid, nblk);
-    MOBI_TILE_OF(L, tm_, tn_);
-    const int nw0 = tn_ * BN + wn * WAVE_N, mw0 = tm_ * BM + wm * 64;
-    int mk_req = 0;
-    if constexpr (DIRECT) {                                  // bias / residual rows of this output tile: in flight
-      vm_issued += direct_epilogue_request<T, NT>(a, dq, lane, group, nw0, mw0);      // for the whole k loop
-      mk_req = vm_issued;
-    }
-
-    for (int kt = kt_begin; kt < kt_end; ++kt) {
-      // the oldest requested k-tile has landed once only operations issued AFTER its requests are outstanding
-      // (vector-memory operations retire in issue order).  LDS-staged epilogues issue loads / stores that are not
-      // counted: under-counting only makes the wait stricter.
-      MOBI_PHASE(0);
-      wait_vmcnt_le(vm_issued - mk0);
-      MOBI_PHASE(1);
-      __builtin_amdgcn_s_barrier();
-      MOBI_PHASE(2);
-#if MOBI_STAMP
-      if (kt == kt_begin && bid == (int)blockIdx.x) MOBI_STAMP_AT(1);
-#endif
-      const unsigned char* st = lds + c_slot * STAGE;
-      const unsigned char* xb = st + (wm * 64 + r16) * 128;
-      const unsigned char* wb = st + X_TILE + (wn * WAVE_N + r16) * 128;
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        // the DMA of the k-tile two steps ahead is issued between the two k-steps: its (expensive) issue slots
-        // then sit in the shadow of the first k-step's MFMAs instead of delaying the first fragment reads
-        if (ks == MOBI_DMA_KS) MOBI_PHASE(3);
-        if (ks == MOBI_DMA_KS && f_bid < nblk) {
-          issue_next(); ++ahead;
-          if (ahead == 2) mk1 = vm_issued; else mk2 = vm_issued;
-        }
-        if (ks == MOBI_DMA_KS) MOBI_PHASE(4);
-        const int sw = ((ks * 4 + g4) ^ (r16 & 7)) << 4;
-        frag_t xf[4], wf[NT];
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi) xf[mi] = __builtin_bit_cast(frag_t, ld16(xb + mi * 16 * 128 + sw));
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni) wf[ni] = __builtin_bit_cast(frag_t, ld16(wb + ni * 16 * 128 + sw));
-#if MOBI_DBG_SKIP & 4
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi) asm volatile("" :: "v"(xf[mi]));
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni) asm volatile("" :: "v"(wf[ni]));
-#else
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni)
-#pragma unroll
-          for (int mi = 0; mi < 4; ++mi)
-            acc[ni][mi] = TR ? mfma16(xf[mi], wf[ni], acc[ni][mi]) : mfma16(wf[ni], xf[mi], acc[ni][mi]);
-#endif
-      }
-      MOBI_PHASE(5);
-      MOBI_PHASE_ACC();
-      --ahead; mk0 = mk1; mk1 = mk2;
-      if (kt + 1 < kt_end) c_slot = c_slot == 2 ? 0 : c_slot + 1;
-    }
-    if constexpr (DIRECT) {
-      // registers only: no barrier, the waves drift by at most one epilogue until the next k-tile's barrier
-      MOBI_STAMP_AT(2);
-      wait_vmcnt_le(vm_issued - mk_req);                     // bias / residual registers are complete
-      vm_issued += direct_epilogue<T, NT, MODE == 3>(a, acc, dq, lane, group, nw0, mw0);
-    } else {
-      // every wave is past its last fragment read of stage c_slot: it is free until the k-tile three steps on is
-      // requested, which happens after the next barrier, i.e. after every wave has left this epilogue
-      __syncthreads();
-      MOBI_STAMP_AT(2);
-      float* stage = reinterpret_cast<float*>(lds + c_slot * STAGE) + wave * (EPI_WAVE / 4);
-      igemm_epilogue<T, NT, TR, RPP>(a, stage, acc, lane, group, nw0, mw0);
-    }
-    c_slot = c_slot == 2 ? 0 : c_slot + 1;
-  }
-#if MOBI_STAMP
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the stamp then covers this wave's stores too
-  MOBI_STAMP_AT(3);
-  if (g_stamps && threadIdx.x == 0) {
-    unsigned hw, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    unsigned long long* d = g_stamps + (size_t)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) * 8;
-    d[4] = ((unsigned long long)xcc << 32) | hw;
-    d[5] = (unsigned long long)(kt_end - kt_begin);
-    d[6] = (unsigned long long)((nblk - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x);
-  }
-#if MOBI_STAMP == 2
-  if (g_phase && lane == 0) {
-    unsigned long long* d = g_phase + ((size_t)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) * 8 + wave) * 8;
-    for (int i = 0; i < 5; ++i) d[i] = ph_acc[i];
-    d[5] = ph_n;
-  }
-#endif
-#endif
-}
-
-#endif  // MOBI_DEV
 
 // =========================================================================================================
 // PING-PONG main loop (register-epilogue launches of the direct-to-LDS geometry: full 256 x (2 * WAVE_N) tiles,
@@ -2864,16 +2490,9 @@ static int launch_igemm(const mobi_igemm_params* p, const IgemmArgs& a, int grou
   const bool tr = p->out_mode == MOBI_OUT_TRANSPOSED;
   const bool nt5 = (a.n_packed % 160) == 0;
   dim3 grid(a.tiles_m * a.tiles_n, a.splits, groups);
-#define MOBI_IGEMM_LAUNCH(NT_, TR_, WM_, FAST_) \
-  hipLaunchKernelGGL((igemm_kernel<T, NT_, TR_, WM_, FAST_>), grid, dim3(128 * WM_), 0, st, a)
-#ifdef MOBI_DEV   // the register-staged kernel's fast-addressing instances: A/B partners of the ring kernel only
-#define MOBI_IGEMM_BY_FAST(NT_, TR_, WM_) \
-  do { if (a.fast) MOBI_IGEMM_LAUNCH(NT_, TR_, WM_, true); else MOBI_IGEMM_LAUNCH(NT_, TR_, WM_, false); } while (0)
-#else             // shipped: the generic-gather instance is the fallback for operands beyond 2 GB / chunk-major k
-#define MOBI_IGEMM_BY_FAST(NT_, TR_, WM_) MOBI_IGEMM_LAUNCH(NT_, TR_, WM_, false)
-#endif
+#define MOBI_IGEMM_LAUNCH(NT_, TR_, WM_) hipLaunchKernelGGL((igemm_kernel<T, NT_, TR_, WM_>), grid, dim3(128 * WM_), 0, st, a)
 #define MOBI_IGEMM_BY_TR(NT_, WM_) \
-  do { if (tr) MOBI_IGEMM_BY_FAST(NT_, true, WM_); else MOBI_IGEMM_BY_FAST(NT_, false, WM_); } while (0)
+  do { if (tr) MOBI_IGEMM_LAUNCH(NT_, true, WM_); else MOBI_IGEMM_LAUNCH(NT_, false, WM_); } while (0)
   if (a.epilogue == MOBI_EPI_LEAKY_RELU) {
     // (igemm_prepare has put every such launch on the ring kernels' staged epilogue: 256- or 128-pixel tiles)
     if (a.wide == 2) {
@@ -2912,20 +2531,6 @@ static int launch_igemm(const mobi_igemm_params* p, const IgemmArgs& a, int grou
 #undef MOBI_PP_LAUNCH
     }
   }
-#ifdef MOBI_DEV
-  else if (a.wm == 4 && a.fast && a.glds) {
-    dim3 block(512);
-    dim3 pgrid(grid.x < (unsigned)compute_units() ? grid.x : (unsigned)compute_units(), grid.y, grid.z);
-    const int mode = tr ? 1 : (a.epi_direct ? (a.epilogue == MOBI_EPI_GEGLU ? 3 : 2) : 0);
-#define MOBI_GLDS_LAUNCH(NT_, MODE_) hipLaunchKernelGGL((igemm_glds_kernel<T, NT_, MODE_>), pgrid, block, 0, st, a)
-#define MOBI_GLDS_BY_MODE(NT_)                                                                     \
-  do { switch (mode) { case 0: MOBI_GLDS_LAUNCH(NT_, 0); break; case 1: MOBI_GLDS_LAUNCH(NT_, 1); break; \
-                       case 2: MOBI_GLDS_LAUNCH(NT_, 2); break; default: MOBI_GLDS_LAUNCH(NT_, 3); break; } } while (0)
-    if (nt5) MOBI_GLDS_BY_MODE(5); else MOBI_GLDS_BY_MODE(4);
-#undef MOBI_GLDS_BY_MODE
-#undef MOBI_GLDS_LAUNCH
-  }
-#endif
   else if (a.wm == 4) { if (nt5) MOBI_IGEMM_BY_TR(5, 4); else MOBI_IGEMM_BY_TR(4, 4); }
   else if (a.sm && a.sm64) {
     // requests dealt out between the MFMAs (MOBI_IGEMM_SM64_OVL=0: the sequential step, the A/B partner)
@@ -2951,7 +2556,6 @@ static int launch_igemm(const mobi_igemm_params* p, const IgemmArgs& a, int grou
   }
   else                { if (nt5) MOBI_IGEMM_BY_TR(5, 2); else MOBI_IGEMM_BY_TR(4, 2); }
 #undef MOBI_IGEMM_BY_TR
-#undef MOBI_IGEMM_BY_FAST
 #undef MOBI_IGEMM_LAUNCH
   MOBI_CHECK_LAUNCH();
   // (with `sync` the tile's last block has summed the slabs; with defer_finish the consumer does -- mobi_groupnorm's src0_split --
@@ -3135,24 +2739,21 @@ static int igemm_prepare(const mobi_igemm_params* p, mobi::IgemmArgs& a) {
   a.tiles_m = (a.M + 64 * a.wm - 1) / (64 * a.wm);
   bool ring_ok = false;
   {
-    // FAST path: k-tiles never straddle a tap or a source, and every byte offset fits 31 bits
+    // a.fast (what the ping-pong kernel needs): k-tiles never straddle a tap or a source, and every byte offset fits 31 bits
     const long long ext0 = (((long long)p->batch - 1) * ips + hw_in) * p->c0 * 2;
     const long long ext1 = p->c1 ? (((long long)p->batch - 1) * ips + hw_in) * p->c1 * 2 : 0;
     const long long wext = (long long)p->n_packed * a.ktot * 2;
     a.fast = (a.C % 64 == 0) && (p->c1 == 0 || p->c0 % 64 == 0) && ext0 < 0x7fffffffLL && ext1 < 0x7fffffffLL &&
              wext < 0x7fffffffLL;
     if (tuning().fast == 0) a.fast = 0;
-    a.k_order = p->k_order;
-    if (p->k_order != 0 && p->k_order != 1) return MOBI_ERR_ARG;
-#ifndef MOBI_DEV
-    if (p->k_order == 1) return MOBI_ERR_UNSUPPORTED;      // chunk-major k: development build only (measured slower)
-#endif
-    if (p->k_order == 1 && !a.fast) return MOBI_ERR_UNSUPPORTED;      // the generic gather walks k tap-major only
+    // tap-major k only: the chunk-major order (1) measured slower and no kernel is routed for it any more
+    if (p->k_order != 0) return p->k_order == 1 ? MOBI_ERR_UNSUPPORTED : MOBI_ERR_ARG;
+    a.k_order = 0;
     a.glds = 1;
     if (tuning().glds == 0) a.glds = 0;
-    // 128-pixel tiles: the LDS-DMA ring kernel whenever the 32-bit buffer offsets reach every operand byte and k runs
-    // tap-major (k-steps are 32 deep there: channel counts are multiples of 32 by the ABI's own rule)
-    ring_ok = p->k_order == 0 && ext0 < 0x7fffffffLL && ext1 < 0x7fffffffLL && wext < 0x7fffffffLL;
+    // 128-pixel tiles: the LDS-DMA ring kernel whenever the 32-bit buffer offsets reach every operand byte
+    // (k-steps are 32 deep there: channel counts are multiples of 32 by the ABI's own rule)
+    ring_ok = ext0 < 0x7fffffffLL && ext1 < 0x7fffffffLL && wext < 0x7fffffffLL;
     a.sm = a.wm == 2 && ring_ok;
     if (tuning().sm == 0) a.sm = 0;
     a.src0_bytes = (int)(ext0 < 0x7fffffffLL ? ext0 : 0);
@@ -3172,10 +2773,7 @@ static int igemm_prepare(const mobi_igemm_params* p, mobi::IgemmArgs& a) {
   if (p->defer_finish != 0 && p->defer_finish != 1) return MOBI_ERR_ARG;
   // deferred finish: the slabs are the launch's result -- T rows only (what a consumer reconstructs), never with `sync`
   if (p->defer_finish && (!a.split_ws || p->sync || p->out_mode != MOBI_OUT_ROWS)) return MOBI_ERR_UNSUPPORTED;
-  // (taps-innermost k order only: it changes tap every k-tile; measured 1.5-3 % slower than the window re-derivation
-  //  on tap-major k, where a tap lasts C/64 k-tiles -- tools/sweep_korder.py)
-  a.lin_window = p->k_order == 1 && p->upsample == 0 && p->kh * p->kw <= 16;
-  if (tuning().lin == 0) a.lin_window = 0;
+  a.lin_window = 0;                                         // (it belonged to the chunk-major k order)
   // register epilogue of the direct-to-LDS kernel: every tile full, row-major T output, no per-image vector
   // (a per-image vector takes the bias registers: never both, and every wave's 64 pixels inside one image)
   a.epi_direct = a.wm == 4 && a.fast && a.glds && p->out_mode == MOBI_OUT_ROWS && !a.split_ws &&
@@ -3212,14 +2810,12 @@ static int igemm_prepare(const mobi_igemm_params* p, mobi::IgemmArgs& a) {
     // a channel tile that is half padding or more (128 output channels in a 256-wide tile: the VAEs' 128-channel levels)
     // loses to the ping-pong kernel's 256 x 128 tile: 878 vs 1160 us on 128 -> 128 3x3 at 512 x 512 x 8 (tools/kbench.py conv)
     if (tuning().wide <= 0 && pick == 2 && p->n_packed * 2 <= bnw && a.pp) pick = 0;
-#ifndef MOBI_DEV
     // launches of the 256-pixel geometry that the ping-pong kernel's register epilogue does not take (transposed / fp32
     // output, ragged tiles, bias AND per-image vector, per-image weights): the ring kernel's LDS-staged epilogue does
     // (a source of fewer than 64 channels into a wide layer -- the UNet's 9-channel input, padded to 32: a tap per k-step --
     //  stays on the register-staged kernel: 38 against 104 us on 9 -> 320 at 64 x 64 x 16)
     if (!pick && a.wm == 4 && !a.pp && (a.C >= 64 || p->out_mode != MOBI_OUT_ROWS || p->n_packed < 256)) pick = 2;
     if (lnf) pick = a.wm == 4 ? 2 : 0;                      // the LayerNorm fold lives in the 256 x 320 / 128 x 160 ring tiles
-#endif
     if (pick) {
       a.wide = pick;
       a.wm = pick == 2 ? 4 : 2;
@@ -3247,7 +2843,7 @@ static int igemm_prepare(const mobi_igemm_params* p, mobi::IgemmArgs& a) {
            (long long)a.tiles_m * a.tiles_n * a.splits * p->groups <= (long long)compute_units() && tuning().sm64 != 0;
   if (tuning().sm64 == 1 && a.sm && a.C % 64 == 0 && (p->c1 == 0 || p->c0 % 64 == 0)) a.sm64 = 1;
   a.w_tiled = (p->weight_tiled && !a.sm64 && (a.sm || a.wide) &&
-               (p->groups == 1 || p->w_group_stride == (long long)p->n_packed * a.ktot) && p->k_order == 0 && p->n_packed % 16 == 0 &&
+               (p->groups == 1 || p->w_group_stride == (long long)p->n_packed * a.ktot) && p->n_packed % 16 == 0 &&
                a.ktot % 32 == 0 && !(reinterpret_cast<uintptr_t>(p->weight_tiled) & 15) && tuning().w_tiled != 0)
                   ? p->weight_tiled : nullptr;
   // 128 x 160 ring tiles: register epilogue / slab stores when every tile is full (the staged epilogue keeps ragged tiles,

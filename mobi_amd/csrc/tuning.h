@@ -9,9 +9,8 @@ struct Tuning {
   int wm;               // MOBI_IGEMM_WM              2 | 4: force the 128- / 256-pixel block
   int fast;             // MOBI_IGEMM_FAST            0: generic gather addressing
   int glds;             // MOBI_IGEMM_GLDS            0: register-staged loads instead of direct-to-LDS
-  int lin;              // MOBI_IGEMM_LIN             0: no linear window stepping (chunk-major k order)
   int epi_direct;       // MOBI_IGEMM_EPI_DIRECT      0: LDS-staged epilogue
-  int pp;               // MOBI_IGEMM_PP              0: lockstep schedule instead of ping-pong
+  int pp;               // MOBI_IGEMM_PP              0: never the ping-pong kernel: its launches go to the ring kernel's 256 x 320 tiles (A/B)
   int sm;               // MOBI_IGEMM_SM              0: 128-pixel tiles on the register-staged kernel (A/B)
   int wide;             // MOBI_IGEMM_WIDE            0: never the eight-wave ring kernel; 2 / 1: always its 256 / 128 x 320 tiles (A/B)
   int wide128;          // MOBI_IGEMM_WIDE128         1: route the 128 x 320 tiles where they fill the chip (A/B; measured slower)
@@ -31,7 +30,6 @@ struct Tuning {
   int small_conv_m;     // MOBI_IGEMM_SMALL_CONV_M    most output pixels of a 3 x 3 launch routed to it (sweeps)
   int tka_mfma;         // MOBI_TKA_MFMA              0: two-key adapter on the vector-ALU kernel; 2 / 1: the LDS-tile kernel to C = 320 / 640 (A/B)
   int attn_nw;          // MOBI_ATTN_NW               4 | 8: waves per attention block
-  int attn_sp;          // MOBI_ATTN_SP               1: software-pipelined attention kernel (dh 33..48)
   int tka_rows;         // MOBI_TKA_ROWS              rows per block of the register two-key adapter kernel (sweeps)
   int attn_nw8_blocks;  // MOBI_ATTN_NW8_BLOCKS       8-wave attention blocks from this many blocks on (default 256; 1024 = rounds 1-3; A/B)
   int attn_h16;         // MOBI_ATTN_H16              1: dh = 40 attention runs the P.V of its last (3/4 padded) channel block on MFMA 16x16x32 (A/B: measured slower)
@@ -41,8 +39,7 @@ struct Tuning {
   int gn_coop;          // MOBI_GN_COOP               1: GroupNorm as pixel chunks meeting through memory wherever the geometry fits; 0: never (A/B)
   int gn_fused;         // MOBI_GN_FUSED              0: two-launch GroupNorm; 1: one launch, slab in LDS, where it fits (A/B)
   int gn_split_pw4;     // MOBI_GN_SPLIT_PW4          1: split-K slabs also into the 8-byte-piece geometry of the register GroupNorm (A/B; default: 16-byte pieces only)
-  int attn_v3;          // MOBI_ATTN_V3               0: V row-major launches stay on attention_kernel (A/B); development build: 2 / 3 = the
-                        //                            software-pipelined variants of attention_rows_kernel
+  int attn_v3;          // MOBI_ATTN_V3               0: V row-major launches stay on attention_kernel instead of attention_rows_kernel (A/B)
 };
 const Tuning& tuning();
 }  // namespace mobi

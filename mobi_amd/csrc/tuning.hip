@@ -20,7 +20,6 @@ void read_env() {
   g_tuning.wm = env_int("MOBI_IGEMM_WM");
   g_tuning.fast = env_int("MOBI_IGEMM_FAST");
   g_tuning.glds = env_int("MOBI_IGEMM_GLDS");
-  g_tuning.lin = env_int("MOBI_IGEMM_LIN");
   g_tuning.epi_direct = env_int("MOBI_IGEMM_EPI_DIRECT");
   g_tuning.pp = env_int("MOBI_IGEMM_PP");
   g_tuning.sm = env_int("MOBI_IGEMM_SM");
@@ -42,7 +41,6 @@ void read_env() {
   g_tuning.small_conv_m = env_int("MOBI_IGEMM_SMALL_CONV_M");
   g_tuning.tka_mfma = env_int("MOBI_TKA_MFMA");
   g_tuning.attn_nw = env_int("MOBI_ATTN_NW");
-  g_tuning.attn_sp = env_int("MOBI_ATTN_SP");
   g_tuning.attn_v3 = env_int("MOBI_ATTN_V3");
   g_tuning.gn_fused = env_int("MOBI_GN_FUSED");
   g_tuning.gn_coop = env_int("MOBI_GN_COOP");
@@ -68,10 +66,4 @@ extern "C" int mobi_tuning_reload(void) {
   return MOBI_OK;
 }
 
-extern "C" int mobi_build_info(void) {
-#ifdef MOBI_DEV
-  return 1;
-#else
-  return 0;
-#endif
-}
+extern "C" int mobi_build_info(void) { return 0; }      // (there is one build; the symbol is part of the ABI)

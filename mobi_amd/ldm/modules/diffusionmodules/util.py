@@ -93,13 +93,6 @@ def zero_module(module):
 # --------------------------------------------------------------------------------------
 # parameter holders
 # --------------------------------------------------------------------------------------
-import os as _os
-
-# measured on MI355X (tools/kbench.py): the chunk-major k order is 10-15 % SLOWER than tap-major for the UNet's 3x3
-# convolutions (per-tile re-derivation of the tap window outweighs the L2 reuse) -> off by default, kept for study
-_CHUNK_MAJOR = _os.environ.get("MOBI_CHUNK_MAJOR", "0") == "1"
-
-
 # bumped whenever parameters are replaced wholesale (load_state_dict, .to() / .cuda() / .float()): captured step
 # graphs (mobi_amd/graph.py) hold the addresses of the packed copies and are dropped when this moves
 WEIGHTS_EPOCH = [0]
@@ -165,8 +158,7 @@ class Conv2d(_Holder):
 
     def packed(self):
         """T [O][kh*kw*I] for the matrix-core / small-cout kernels."""
-        return self._cached("mfma", lambda: ops.pack_conv(self.weight, self.bias, engine_dtype(), self.weight.device,
-                                                          chunk_major=_CHUNK_MAJOR))
+        return self._cached("mfma", lambda: ops.pack_conv(self.weight, self.bias, engine_dtype(), self.weight.device))
 
     def packed_tap_major(self):
         """k = tap*C + c order (the small-cout direct kernel)."""

@@ -5,7 +5,7 @@ list covers what it promises (`missing`).
 
 A body is forced with the A/B environment of csrc/tuning.hip:
   staged128   SM=0 WM=2 WIDE=0            igemm_kernel<.., WM 2>
-  staged256   WM=4 WIDE=0 PP=0            igemm_kernel<.., WM 4> (reported as direct_lds where C % 64 == 0: the shipped build
+  staged256   WM=4 WIDE=0 PP=0            igemm_kernel<.., WM 4> (reported as direct_lds where C % 64 == 0: the library
                                           has no direct-to-LDS kernel and runs the register-staged one)
   pingpong    WM=4 WIDE=0                 igemm_pp_kernel (eligible shapes only)
   ring256s    WM=4 WIDE=2 RING_DIRECT=0       igemm_ring_kernel<.., 8, 8>, LDS-staged epilogue
@@ -311,8 +311,8 @@ def in_launch_mode(case, knobs, mode):
 
 
 def expected_instantiations():
-    """(kernel, epilogue form) of igemm_ref.plan for everything launch_igemm (csrc/igemm.hip:2863-2961) can select in the
-    shipped build -> (its eligibility allows a ragged pixel tile, a ragged channel tile)."""
+    """(kernel, epilogue form) of igemm_ref.plan for everything launch_igemm (csrc/igemm.hip) can select
+    -> (its eligibility allows a ragged pixel tile, a ragged channel tile)."""
     want = {}
     for nt, tr, wm in itertools.product((4, 5), (0, 1), (2, 4)):
         want[(f"staged<{nt},{tr},{wm}>", "staged")] = True

@@ -294,19 +294,25 @@ def slab_products(case, o, split_k, dtype, absolute=False):
 # ----------------------------------------------------------------------------------------------------------------------
 # the kernels' arithmetic
 def restated(case, o, dtype, acc_hook=None, leaky_after_residual=False):
-    """The same operation in fp32 torch with the rounding points the kernels document and nothing else (line numbers of
-    csrc/igemm.hip at the commit that added this file):
+    """The same operation in fp32 torch with the rounding points the kernels document and nothing else (csrc/igemm.hip, cited
+    as function + a phrase of the line; the register epilogues are direct_epilogue, ring_register_epilogue and pp_epilogue):
       * operands are T, their products exact, every sum fp32 (the MFMAs accumulate in fp32: `f32x4 acc[NT][..]`);
-      * LayerNorm fold: sum and sum of squares of the RAW rows in fp32 (rowstat_acc :1953-1972), mean = sum / k,
-        var = max(sumsq / k - mean^2, 0), rstd = rsqrt(var + eps) (:1987-1991), acc <- rstd (acc - mean svec) (:2009);
-      * v = acc * scale + bias in fp32 (:289, :299; the register epilogues :672-676; the ping-pong / 256 x 320 ring
-        register forms start the sums from bias or rowvec instead -- another order, no other rounding);
-      * GEGLU value * gelu_erf(gate) in fp32 (:340, :686, :758, :853);
-      * + rowvec (:364), leaky 0.1 (:368), + residual read as T (:374, :694, :766, :873), all fp32;
-      * split-K: each slab is acc * scale in fp32 (:289 with use_bias false, stored :323); the finish sums them in ascending
-        order from 0.0f, then + bias + rowvec + residual (igemm_splitk_reduce_kernel :2784-2827);
-      * ONE rounding to T (pack8 :381, :344, :401, from_f32 :408, :696, :768, :875, :2833); fp32 outputs are stored as they
-        are (:378-379, :2830-2831).
+      * LayerNorm fold: sum and sum of squares of the RAW rows in fp32 (both rowstat_acc overloads), `mean = sm * inv_k`,
+        var = max(sumsq / k - mean^2, 0), `rsqrtf(var + a.ln_eps)` and `rstd * (acc[ni][mi] - mean * sv) + bv` (ln_fold_acc);
+      * v = acc * scale + bias in fp32 (igemm_epilogue `v = v * scale + bias4[ni]`, twice; direct_epilogue
+        `acc[ni][2 * p] * scale`; the ping-pong / 256 x 320 ring register forms start the sums from bias or rowvec
+        instead -- another order, no other rounding);
+      * GEGLU value * gelu_erf(gate) in fp32 (igemm_epilogue `av[j] * gelu_erf_f(gv[j])`; `xs[r] * gelu_erf_f(ys[r])` in each
+        register epilogue);
+      * + rowvec (`o[j] += rv[j]`), leaky 0.1 (`0.1f * o[j]`), + residual read as T (`o[j] += rf[j]`, igemm_epilogue and each
+        register epilogue), all fp32;
+      * split-K: each slab is acc * scale in fp32 (igemm_epilogue `v = v * scale + bias4[ni]` with use_bias false, stored by its
+        `*reinterpret_cast<f32x4*>(d) =` copy); the finish sums them in ascending order from `o[j] = 0.f`, then + bias +
+        rowvec + residual (igemm_splitk_reduce_kernel);
+      * ONE rounding to T (`pack8<T>(o)` in igemm_epilogue's three `st16(outT + ...` stores, in each register epilogue's
+        `vm_store16(rowp + ...` and in igemm_splitk_reduce_kernel; `from_f32<T>(o[j])` in igemm_epilogue's ragged transposed
+        store); fp32 outputs are stored as they are (`*reinterpret_cast<f32x4*>(outF + off)` in igemm_epilogue and
+        igemm_splitk_reduce_kernel).
     acc_hook(acc) -> acc and leaky_after_residual plant faults (tests/test_igemm_ref_cpu.py); a launch has neither.
     Returns fp32 in the case's output layout."""
     f32 = torch.float32
@@ -463,7 +469,7 @@ def _exact_log2(v):
 
 
 def _small_tile(case, t, split_k):
-    """small_tile, csrc/igemm.hip:2974-2998."""
+    """small_tile of csrc/igemm.hip."""
     if t("SMALL") == 0:
         return 0
     if t("SMALL") < 0 and (t("WM") in (2, 4) or t("WIDE") >= 0 or t("SM") == 0):
@@ -488,9 +494,9 @@ def _small_tile(case, t, split_k):
 
 def plan(case, knobs=None, cu=COMPUTE_UNITS):
     """The body (MOBI_IGEMM_*) and the sub-forms a launch of `case` takes under the MOBI_IGEMM_* environment `knobs`
-    ({'WM': 2, ...}, unset = -1): a restatement of the predicates of igemm_prepare (csrc/igemm.hip:3067-3313) and the
-    instantiation launch_igemm picks (:2863-2961) for operands far below 2 GB, tap-major k and the shipped (non-MOBI_DEV)
-    build.  The GPU test asserts `body` against mobi_igemm_kernel_variant; nothing in the library reports the other fields
+    ({'WM': 2, ...}, unset = -1): a restatement of the predicates of igemm_prepare (csrc/igemm.hip; the comments
+    below quote the line each one restates) and the instantiation launch_igemm picks, for operands far below 2 GB and
+    tap-major k (the only order there is).  The GPU test asserts `body` against mobi_igemm_kernel_variant; nothing in the library reports the other fields
     (sm64, sm_direct, ring_direct, epi_direct / pp, in-launch finish, w_tiled, the kernel symbol): they are a restated claim,
     only as good as this reading of the code."""
     knobs = knobs or {}
@@ -500,11 +506,11 @@ def plan(case, knobs=None, cu=COMPUTE_UNITS):
     npk, C, hw = case.n_packed, case.C, case.hw
     bias, rowvec, resid = case.bias, case.rowvec, bool(case.residual)
     split_k = case.split_k if case.split_k > 1 else 0
-    M = (case.n // case.groups) * hw                                    # rows of ONE group (:3117-3118)
+    M = (case.n // case.groups) * hw                                    # rows of ONE group (`a.M = a.imgs_per_group * a.hw_out`)
     nk = (case.ktot + 63) // 64
     bn = 160 if npk % 160 == 0 else 128
     up = lambda a, b: (a + b - 1) // b
-    tiles256 = up(M, 256) * up(npk, bn)                                 # :3128-3133
+    tiles256 = up(M, 256) * up(npk, bn)                                 # `const long long tiles256 =` .. `a.wm = tuning().wm`
     wm = 4 if tiles256 >= 256 else 2
     if split_k and M % 256 == 0 and tiles256 * split_k >= 256 and nk // split_k >= 16:
         wm = 4
@@ -513,26 +519,26 @@ def plan(case, knobs=None, cu=COMPUTE_UNITS):
     if t("WM") in (2, 4):
         wm = t("WM")
     tiles_m, tiles_n = up(M, 64 * wm), up(npk, bn)
-    fast = C % 64 == 0 and (case.c1 == 0 or case.c0 % 64 == 0) and t("FAST") != 0        # :3142-3144
+    fast = C % 64 == 0 and (case.c1 == 0 or case.c0 % 64 == 0) and t("FAST") != 0        # `a.fast =` (extents < 2 GB here)
     glds = t("GLDS") != 0
-    sm = wm == 2 and t("SM") != 0                                       # :3156-3157 (ring_ok: small operands, k_order 0)
+    sm = wm == 2 and t("SM") != 0                                       # `a.sm = a.wm == 2 && ring_ok` (small operands)
     splits, nk_per = 1, nk
-    if split_k:                                                         # :3165-3171
+    if split_k:                                                         # `if (p->split_k > 1) {`
         nk_per = up(nk, split_k)
         splits = up(nk, nk_per)
     split_ws = bool(split_k)
     vec_ok = lambda mult: not rowvec or (not bias and hw % mult == 0)
     epi_direct = (wm == 4 and fast and glds and rows and not split_ws and vec_ok(64) and M % 256 == 0 and npk % bn == 0 and
-                  nk_per >= 3 and t("EPI_DIRECT") != 0)                 # :3181-3184
+                  nk_per >= 3 and t("EPI_DIRECT") != 0)                 # `a.epi_direct =`
     shifts = _exact_log2(hw) >= 6 and _exact_log2(case.wo) >= 0
-    pp = epi_direct and splits == 1 and case.scale == 1.0 and shifts    # :3188
+    pp = epi_direct and splits == 1 and case.scale == 1.0 and shifts    # `a.pp = a.epi_direct &&`
     if split_ws and wm == 4 and fast and glds and not tr and M % 256 == 0 and npk % bn == 0 and nk_per >= 3 and \
-            case.scale == 1.0 and shifts:                               # :3191-3194
+            case.scale == 1.0 and shifts:                               # `if (a.split_ws && a.wm == 4 && a.fast`
         pp = True
     if t("PP") == 0:
         pp = False
     wide = 0
-    if (wm == 4 or t("WIDE") > 0) and t("WIDE") != 0:                   # :3202-3230
+    if (wm == 4 or t("WIDE") > 0) and t("WIDE") != 0:                   # `if ((a.wm == 4 || tuning().wide > 0) && ring_ok`
         bnw = 320 if npk % 160 == 0 else 256
         tn = up(npk, bnw)
 
@@ -551,34 +557,34 @@ def plan(case, knobs=None, cu=COMPUTE_UNITS):
             wide, wm, sm = pick, (4 if pick == 2 else 2), False
             tiles_m, tiles_n = up(M, 64 * wm), tn
     k64 = C % 64 == 0 and (case.c1 == 0 or case.c0 % 64 == 0)
-    sm64 = sm and k64 and nk_per >= 1 and tiles_m * tiles_n * splits * case.groups <= cu and t("SM64") != 0     # :3246-3248
+    sm64 = sm and k64 and nk_per >= 1 and tiles_m * tiles_n * splits * case.groups <= cu and t("SM64") != 0     # `a.sm64 =`
     if t("SM64") == 1 and sm and k64:
         sm64 = True
     dense_groups = case.groups == 1 or case.w_gap == 0
     tileable = case.w_tiled and dense_groups and npk % 16 == 0 and case.ktot % 32 == 0 and t("WTILED") != 0
-    w_tiled = tileable and not sm64 and (sm or wide > 0)                # :3249-3252
+    w_tiled = tileable and not sm64 and (sm or wide > 0)                # `a.w_tiled =`
     sm_direct = ((sm or wide == 1) and (rows or split_ws) and not tr and M % 128 == 0 and
-                 npk % (2 * bn if wide == 1 else bn) == 0 and (split_ws or vec_ok(64)) and t("SM_DIRECT") != 0)    # :3257-3259
+                 npk % (2 * bn if wide == 1 else bn) == 0 and (split_ws or vec_ok(64)) and t("SM_DIRECT") != 0)    # `a.sm_direct =`
     bnw = 320 if npk % 160 == 0 else 256
     rd = (wide == 2 and rows and not split_ws and case.groups == 1 and vec_ok(128) and M % 256 == 0 and npk % bnw == 0 and
           case.scale == 1.0)
-    ring_direct = (rd and not resid and t("RING_DIRECT") != 0) or (rd and resid and t("RING_DIRECT") == 1)        # :3262-3269
-    if leaky:                                                           # :3271-3291
+    ring_direct = (rd and not resid and t("RING_DIRECT") != 0) or (rd and resid and t("RING_DIRECT") == 1)        # `a.ring_direct =`
+    if leaky:                                                           # `if (leaky) {`
         pp = epi_direct = sm_direct = ring_direct = sm64 = False
         if wm == 4 and npk >= 256:
             wide, sm, tiles_m, tiles_n = 2, False, up(M, 256), up(npk, bnw)
         else:
             wide, wm, sm, tiles_m, tiles_n = 0, 2, True, up(M, 128), up(npk, bn)
         w_tiled = tileable
-    small = 0 if lnf or leaky else _small_tile(case, t, split_k)        # :3292
+    small = 0 if lnf or leaky else _small_tile(case, t, split_k)        # `a.small =`
     pp_launch = not wide and wm == 4 and fast and glds and pp
     sync_mode = 0
-    if split_ws and case.finish == "sync" and not small and t("FUSED_SPLIT") != 0 and splits <= 4:                # :3300-3311
+    if split_ws and case.finish == "sync" and not small and t("FUSED_SPLIT") != 0 and splits <= 4:                # `if (a.split_ws && p->sync && !a.small`
         mode = 1 if t("FUSED_SPLIT") == 1 else 2
         tiles = tiles_m * tiles_n
         if ((wide or sm) or (pp_launch and tiles <= cu)) and (mode == 1 or tiles % 8 == 0):
             sync_mode = mode
-    # mobi_igemm_kernel_variant (:3359-3368) and launch_igemm (:2863-2961)
+    # mobi_igemm_kernel_variant and launch_igemm
     nt = 5 if npk % 160 == 0 else 4
     flag = lambda b: "1" if b else "0"
     if small:
@@ -595,8 +601,8 @@ def plan(case, knobs=None, cu=COMPUTE_UNITS):
         body, kernel = PINGPONG, f"pp<{nt},geglu{flag(geglu and not split_ws)},slab{flag(split_ws)}>"
         epi = "slab" if split_ws else "register"
     elif wm == 4:
-        body = DIRECT_LDS if fast and glds else STAGED_256              # the shipped build has no direct-to-LDS kernel: the
-        kernel, epi = f"staged<{nt},{flag(tr)},4>", "staged"            # register-staged one runs (MOBI_IGEMM_BY_FAST)
+        body = DIRECT_LDS if fast and glds else STAGED_256              # the library has no direct-to-LDS kernel: the
+        kernel, epi = f"staged<{nt},{flag(tr)},4>", "staged"            # register-staged one runs (MOBI_IGEMM_BY_TR)
     elif sm and sm64:
         body, kernel = RING_128, f"ring64<{nt},{flag(tr)},lnf{flag(lnf)},ovl{flag(t('SM64_OVL') != 0)}>"
         epi = "register" if sm_direct else "staged"

@@ -832,8 +832,6 @@ class LaunchShadow:
                w_group_stride=0, split_k=None, groups=1, defer=None, leaky=False):
         ops = self.ops
         x, x2, residual = ops.finished(x), ops.finished(x2), ops.finished(residual)
-        if pw.k_order:
-            raise NotImplementedError("launch shadow: the chunk-major k order exists in the development build only")
         if w_group_stride and not weight_per_image and groups == 1:
             raise NotImplementedError("launch shadow: a weight group stride without per-image weights or groups")
         n, hin, win, _ = x.shape

@@ -312,8 +312,8 @@ def test_mobi_configs_resolve_onto_engine_classes(name):
 
 def test_shipped_library_has_no_scratch_and_no_dev_kernels():
     """Every kernel of the shipped library keeps its state in registers (no scratch_load / scratch_store in the gfx950
-    code objects: a spilling main loop was the round-1 library's slowest igemm path) and the A/B partner kernels of the
-    development build (-DMOBI_DEV) are not in it."""
+    code objects: a spilling main loop was the round-1 library's slowest igemm path) and the measured-slower A/B partner
+    kernels that a development-only build used to carry are not in it (there is one build: mobi_build_info() is 0)."""
     import shutil
     import subprocess
     import tempfile

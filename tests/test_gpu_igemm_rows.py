@@ -313,8 +313,7 @@ def test_wrapper_derives_strides_and_pointers(lib, tune, dtype):
 
 
 def test_every_instantiation_and_axis_value_has_a_case():
-    """Closing check on the list the tests above ran: every (kernel, epilogue form) launch_igemm can select in the shipped
-    build, with a ragged pixel and channel tile where its eligibility allows them, and every axis value on an LDS-DMA body
+    """Closing check on the list the tests above ran: every (kernel, epilogue form) launch_igemm can select, with a ragged pixel and channel tile where its eligibility allows them, and every axis value on an LDS-DMA body
     and on a register-staged one (igemm_cases.missing names what is not there)."""
     assert not IC.missing(), "\n".join(IC.missing())
 
@@ -368,6 +367,7 @@ def test_refusals(lib, tune):
         ("strided source with two sources", rep(base, c1=64), dict(src_img_stride=64 * 20), ERR_UNSUPPORTED),
         ("src_img_stride % c0", base, dict(src_img_stride=64 * 16 + 8), ERR_UNSUPPORTED),
         ("k_order 2", base, dict(k_order=2), ERR_ARG),
+        ("chunk-major k", base, dict(k_order=1), ERR_UNSUPPORTED),
         ("split without workspace", split, dict(ws=None), ERR_UNSUPPORTED),
         ("split with groups", rep(split, groups=2), {}, ERR_UNSUPPORTED),
         ("split transposed", rep(split, out_mode="tr"), {}, ERR_UNSUPPORTED),
@@ -379,8 +379,6 @@ def test_refusals(lib, tune):
         ("defer_finish fp32", rep(split, out_mode="f32"), dict(defer_finish=1), ERR_UNSUPPORTED),
         ("sync alignment", rep(split, finish="sync"), dict(sync=(1 << 20) + 2), ERR_ALIGN),
     ]
-    if not lib.mobi_build_info() & 1:
-        cases.append(("chunk-major k in the shipped build", base, dict(k_order=1), ERR_UNSUPPORTED))
     bad = []
     for name, case, fields, want in cases:
         got = _query(lib, case, **fields)

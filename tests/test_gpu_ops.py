@@ -32,13 +32,6 @@ def rel(a, b):
     return err
 
 
-def _k_orders():
-    """The chunk-major k order of the packed weights (measured 10-15 % slower, kept for study) exists in the development
-    build only (-DMOBI_DEV); the shipped library answers MOBI_ERR_UNSUPPORTED."""
-    from mobi_amd import _lib
-    return (False, True) if _lib.load().mobi_build_info() & 1 else (False,)
-
-
 def rnd(name, shape, dtype, scale=1.0):
     """deterministic input, rounded to the storage type; returns (fp32 cpu copy, device tensor)."""
     x = (W.synth_input(name, shape) * scale).to(dtype)
@@ -485,33 +478,6 @@ def test_attention_shift_path(ops, dtype, nw, dh, tq, tk, kind, tune):
 
 
 @pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("dh,tq,tk", [(40, 300, 40), (40, 1, 64), (48, 257, 100), (40, 256, 128), (40, 70, 190),
-                                      (40, 512, 300), (40, 33, 1)])
-def test_attention_software_pipelined(ops, dtype, dh, tq, tk, tune):
-    from mobi_amd import _lib
-    if not _lib.load().mobi_build_info() & 1:
-        pytest.skip("attention_sp_kernel is an A/B kernel of the development build (-DMOBI_DEV), not in the shipped library")
-    """the software-pipelined 8-wave kernel (head dims 33..48) on 1..5 key tiles, ragged last tiles and ragged query blocks;
-    it is an A/B alternative (MOBI_ATTN_SP=1, slower than the default kernel) and must agree with the default kernel."""
-    n, heads = 2, 4
-    c = heads * dh
-    qf, qd = rnd(f"ap.q{dh}.{tq}", (n, tq, c), dtype, 1.5)
-    kf, kd = rnd(f"ap.k{dh}.{tk}", (n, tk, c), dtype, 1.5)
-    vf, vd = rnd(f"ap.v{dh}.{tk}", (n, tk, c), dtype)
-    sp = lambda t: t.reshape(n, -1, heads, dh).permute(0, 2, 1, 3)
-    sim = torch.einsum("bhid,bhjd->bhij", sp(qf), sp(kf)) * dh ** -0.5
-    ref = torch.einsum("bhij,bhjd->bhid", sim.softmax(-1), sp(vf)).permute(0, 2, 1, 3).reshape(n, tq, c)
-    tune.setenv("MOBI_ATTN_NW", "8")
-    tune.setenv("MOBI_ATTN_SP", "1")
-    y = ops.attention(qd, kd, vd, heads, dh ** -0.5, v_rows=True)
-    assert torch.isfinite(y.float()).all()
-    assert rel(y.float(), ref) < TOL[dtype]
-    tune.setenv("MOBI_ATTN_SP", "0")
-    y0 = ops.attention(qd, kd, vd, heads, dh ** -0.5, v_rows=True)
-    assert rel(y.float(), y0.float()) < 1e-6 + (0 if dtype == torch.float32 else 4e-3)
-
-
-@pytest.mark.parametrize("dtype", DT)
 def test_attention_strided_partner_and_spike(ops, dtype, tune):
     """q from the camera half, k/v from the lidar half of an interleaved batch (image strides), with
     q/k packed in one [.., 2C] tensor (row stride > C) and one huge score (online-softmax rescale)."""
@@ -533,12 +499,9 @@ def test_attention_strided_partner_and_spike(ops, dtype, tune):
     kvd = torch.cat([xd[:, :, c:], vd], dim=2)
     y2 = ops.attention(xd[::2, :, :c], kvd[1::2, :, :c], kvd[1::2, :, c:], heads, dh ** -0.5, v_rows=True)
     assert rel(y2.float(), ref) < TOL[dtype]
-    tune.setenv("MOBI_ATTN_NW", "8")                         # the same through 8-wave blocks, both schedules
+    tune.setenv("MOBI_ATTN_NW", "8")                         # the same through 8-wave blocks
     y3 = ops.attention(xd[::2, :, :c], kvd[1::2, :, :c], kvd[1::2, :, c:], heads, dh ** -0.5, v_rows=True)
-    tune.setenv("MOBI_ATTN_SP", "1")
-    y4 = ops.attention(xd[::2, :, :c], kvd[1::2, :, :c], kvd[1::2, :, c:], heads, dh ** -0.5, v_rows=True)
     assert rel(y3.float(), ref) < TOL[dtype]
-    assert rel(y4.float(), ref) < TOL[dtype]
 
 
 @pytest.mark.parametrize("dtype", DT)
@@ -762,14 +725,18 @@ def test_error_codes_on_device(ops):
 @pytest.mark.parametrize("dtype", DT)
 @pytest.mark.parametrize("split", [None, 2, 5, 8])
 def test_igemm_split_k(ops, dtype, split):
-    from mobi_amd import _lib as _l
-    if not _l.load().mobi_build_info() & 1:               # shipped build: chunk-major weights are refused, loudly
-        x_ = torch.zeros(1, 8, 8, 64, dtype=dtype, device="cuda")
-        pw_ = ops.pack_conv(torch.zeros(64, 64, 3, 3), None, dtype, "cuda", chunk_major=True)
-        with pytest.raises(_l.EngineError):
-            ops.igemm(x_, pw_)
     """Small-m / long-k convolution (the 8x8 UNet level): k cut over workgroups, fp32 slabs, reduce launch
     with bias + per-image vector + residual.  split=None exercises the library's own plan."""
+    import ctypes as C
+    from mobi_amd import _lib as _l
+    x_, w_ = torch.zeros(1, 8, 8, 64, dtype=dtype, device="cuda"), torch.zeros(64, 576, dtype=dtype, device="cuda")
+    o_ = torch.zeros(1, 8, 8, 64, dtype=dtype, device="cuda")
+    p_ = _l.IgemmParams(src0=x_.data_ptr(), c0=64, batch=1, hin=8, win=8, hout=8, wout=8, kh=3, kw=3, stride=1, pad_h=1, pad_w=1,
+                        weight=w_.data_ptr(), groups=1, n_packed=64, cout=64, out=o_.data_ptr(), scale=1.0,
+                        dtype=ops._dt(dtype))
+    assert _l.load().mobi_igemm_kernel_variant(C.byref(p_)) >= 0
+    p_.k_order = 1                                          # chunk-major weights are refused, loudly (MOBI_ERR_UNSUPPORTED)
+    assert _l.load().mobi_igemm(C.byref(p_), None) == -2 and float(o_.float().abs().sum()) == 0
     xf, xd = rnd("sk.x", (2, 8, 8, 640), dtype)
     x1f, x1d = rnd("sk.x1", (2, 8, 8, 320), dtype)
     rf, rd = rnd("sk.res", (2, 8, 8, 320), dtype)
@@ -777,10 +744,9 @@ def test_igemm_split_k(ops, dtype, split):
     bias = torch.from_numpy(W.synth_param("sk.bias", (320,)))
     rv = W.synth_input("sk.rowvec", (2, 320))
     ref = _conv_ref(torch.cat([xf, x1f], 3), wf, bias) + rv[:, None, None, :] + rf
-    for chunk_major in _k_orders():
-        pw = ops.pack_conv(wf, bias, dtype, "cuda", chunk_major=chunk_major)
-        y = ops.igemm(xd, pw, x2=x1d, rowvec=rv.cuda(), residual=rd, split_k=split)
-        assert rel(y.float(), ref) < TOL[dtype], chunk_major
+    pw = ops.pack_conv(wf, bias, dtype, "cuda")
+    y = ops.igemm(xd, pw, x2=x1d, rowvec=rv.cuda(), residual=rd, split_k=split)
+    assert rel(y.float(), ref) < TOL[dtype]
     if split is None:
         from mobi_amd import _lib
         import ctypes as C
@@ -904,13 +870,12 @@ def test_igemm_block_heights(ops, dtype, wm, tune):
         wf = torch.from_numpy(W.synth_param(name + ".weight", (cout, cin, kh, kw))).to(dtype).float()
         bias = torch.from_numpy(W.synth_param(name + ".bias", (cout,)))
         pad = (kh // 2, kw // 2)
-        for chunk_major in _k_orders():              # both k orders of the packed weights (development build)
-            pw = ops.pack_conv(wf, bias, dtype, "cuda", chunk_major=chunk_major)
-            if asym:
-                y = ops.igemm(xd, pw, stride=2, pad=(0, 0), hout=(h + 1 - 3) // 2 + 1, wout=(w + 1 - 3) // 2 + 1)
-            else:
-                y = ops.igemm(xd, pw, stride=stride, pad=pad, upsample=up)
-            assert rel(y.float(), _conv_ref(xf, wf, bias, stride, pad, up, asym)) < TOL[dtype], (name, chunk_major)
+        pw = ops.pack_conv(wf, bias, dtype, "cuda")
+        if asym:
+            y = ops.igemm(xd, pw, stride=2, pad=(0, 0), hout=(h + 1 - 3) // 2 + 1, wout=(w + 1 - 3) // 2 + 1)
+        else:
+            y = ops.igemm(xd, pw, stride=stride, pad=pad, upsample=up)
+        assert rel(y.float(), _conv_ref(xf, wf, bias, stride, pad, up, asym)) < TOL[dtype], name
     xf, xd = rnd("bh.x", (2, 300, 320), dtype)
     wf = torch.from_numpy(W.synth_param("bh.g.weight", (2560, 320))).to(dtype).float()
     bf = torch.from_numpy(W.synth_param("bh.g.bias", (2560,)))

@@ -164,8 +164,8 @@ def test_the_next_step_hits_the_installed_copies(net, monkeypatch):
             assert (pt.w is im["w_t"] and pt.wt is im["wt_t"]) if pt else (im["w_t"] is None and im["wt_t"] is None)
             assert (pw.bias is None) == (m.bias is None) and (pw.bias is None or pw.bias.data_ptr() == m.bias.data_ptr())
             want = ops.pack_linear(m.weight, m.bias, torch.float16, m.weight.device)
-            assert (pw.kh, pw.kw, pw.cin, pw.cout, pw.n_packed, pw.geglu, pw.k_order) == \
-                   (want.kh, want.kw, want.cin, want.cout, want.n_packed, want.geglu, want.k_order)
+            assert (pw.kh, pw.kw, pw.cin, pw.cout, pw.n_packed, pw.geglu) == \
+                   (want.kh, want.kw, want.cin, want.cout, want.n_packed, want.geglu)
             assert (pw.wt is None) == (want.wt is None) and torch.equal(pw.w, want.w)
             for t in (pw.w, pw.wt) + ((pt.w, pt.wt) if pt else ()):
                 assert t is None or lo <= t.data_ptr() < hi

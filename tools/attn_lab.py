@@ -44,8 +44,6 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--qscale", type=float, default=1.0)
-    ap.add_argument("--stamp", default="", help="hipcc flags of ONE variant built with -DMOBI_ATTN_STAMP: prints the "
-                    "s_memtime stamps of waves 0 and NW/2 of block (1,1,1), steps 16..23 (attention_pipe_kernel)")
     ap.add_argument("variants", nargs="*")
     a = ap.parse_args()
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float16
@@ -74,26 +72,6 @@ def main():
     p.dtype = _lib.MOBI_BF16 if dt == torch.bfloat16 else _lib.MOBI_F16
     stream = torch.cuda.current_stream().cuda_stream
 
-    if a.stamp is not None and a.stamp != "":
-        dbg = torch.zeros(128, dtype=torch.int64, device="cuda")
-        os.environ["MOBI_ATTN_STAMP_PTR"] = hex(dbg.data_ptr())
-        lib = build("stamp", ["-DMOBI_ATTN_STAMP"] + [f for f in a.stamp.split() if f != "-"])
-        lib.mobi_attention.argtypes = [C.c_void_p, C.c_void_p]
-        for _ in range(3):
-            assert lib.mobi_attention(C.byref(p), stream) == 0
-        torch.cuda.synchronize()
-        d = dbg.cpu().view(2, 8, 8)
-        names = ["top", "staged", "reads issued", "MFMA gaps", "fix", "rotate", "barrier"]
-        print("# ns between stamps (s_memrealtime, 10 ns ticks), steps 16..23; columns:", ", ".join(f"{names[i]}->{names[i + 1]}" for i in range(6)),
-              ", barrier->next top, whole step")
-        for w, tag in ((0, "wave 0 (early)"), (1, "wave NW/2 (late)")):
-            for st in range(7):
-                row = [int(d[w, st, i + 1] - d[w, st, i]) for i in range(6)]
-                row.append(int(d[w, st + 1, 0] - d[w, st, 6]))
-                row.append(int(d[w, st + 1, 0] - d[w, st, 0]))
-                print(f"{tag:18s} step {16 + st}: " + " ".join(f"{x:6d}" for x in row))
-        print("# late - early offsets of the step tops:", [int(d[1, st, 0] - d[0, st, 0]) for st in range(8)])
-        return
     variants = []
     for spec in a.variants or ['base=']:
         name, _, flags = spec.partition("=")

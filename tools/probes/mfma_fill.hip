@@ -125,7 +125,7 @@ __global__ __launch_bounds__(512) void split(float* out, unsigned long long* cyc
   if (threadIdx.x == 0) cyc[blockIdx.x] = t1 - t0;
 }
 
-// Emulation of attention_pipe_kernel's step at two waves per SIMD: 14 MFMAs, each followed by 2-3 exp + cvt_pk (+ or3);
+// Emulation of a whole-tile software-pipelined attention step (a removed variant of attention_rows_kernel) at two waves per SIMD: 14 MFMAs, each followed by 2-3 exp + cvt_pk (+ or3);
 // EMU bit 0 = a barrier per step, bit 1 = an LDS fragment read behind every MFMA (8 x 2 ds_read_b64_tr_b16, 6 x ds_read_b128)
 // that nobody consumes (s_waitcnt lgkmcnt(0) before the barrier), bit 2 = the MFMA's A operand IS last step's read (counted
 // waits), bit 3 = two ds_write_b128 at the top of the step.
