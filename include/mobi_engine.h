@@ -59,7 +59,8 @@ extern "C" {
  *      (mobi_camera_export_params 31); likewise the one launch that refreshes every trained weight's 16-bit images,
  *      mobi_repack_multi (mobi_repack_entry 32); likewise the test bench's lidar-on-camera overlays, mobi_lidar_overlay +
  *      mobi_lidar_overlay_workspace_bytes (mobi_lidar_overlay_params 33, mobi_lidar_overlay_picture 34); likewise the numeric
- *      health launch, mobi_tensor_health (mobi_health_tensor 35, mobi_health_record 36) */
+ *      health launch, mobi_tensor_health (mobi_health_tensor 35, mobi_health_record 36); likewise the camera pictures of the
+ *      test bench's copy-paste baseline, mobi_camera_copy_paste (mobi_camera_export_params 31 as it is, no new struct) */
 #define MOBI_ABI_VERSION 6
 
 enum { MOBI_OK = 0, MOBI_ERR_ARG = -1, MOBI_ERR_UNSUPPORTED = -2, MOBI_ERR_LAUNCH = -3, MOBI_ERR_ALIGN = -4 };
@@ -999,6 +1000,24 @@ typedef struct mobi_camera_export_params {
   int32_t batch, hs, ws, ref_h, ref_w, H, W, frames;
 } mobi_camera_export_params;
 int mobi_camera_export(const mobi_camera_export_params* p, void* stream);
+
+/* The export launch in copy-paste mode: the baseline row of the realism table (scripts/inference_test_bench.py --copy-paste,
+ * :503-516), which pastes the reference image over the object instead of the sample.  The struct, the output layout, the five
+ * pictures, the status words, the limits, the refusals (all before any launch), what frames == 0 reads and the launch count are
+ * those of mobi_camera_export; `taps` is ignored and may be NULL.  Three things differ per object, in the terms above:
+ *   pred         P(patch_pred) inside the crop window and 0 elsewhere, then pred[y1:y2, x1:x2] = the object_ref picture (picture 4)
+ *                resized from 224 x 224 to (y2 - y1) x (x2 - x1) with the same integer restatement of cv2's 8-bit INTER_LINEAR;
+ *                y1, y2, x1, x2 is the box of the UNdilated mask, max exclusive; it is not clipped to the crop window
+ *   m            cv2.dilate(mask, ones(5, 5)): the maximum of mask over the 5 x 5 neighbourhood, over pixels inside the frame only
+ *                (OpenCV's default border value for a dilation never wins); it replaces the blur
+ *   recon        m * I + (1 - m) * pred as before: fp32, every operation rounded on its own, nearest even, clamped
+ * so that frame / patch_pred are this recon, patch_gt and object_ref are unchanged and object_pred is pred[y1:y2, x1:x2] -- the
+ * resized reference -- resized again to 224 x 224.  An empty exclusive box: status 1, nothing is pasted and object_pred is not
+ * written.  The paste is computed from `ref`; no picture this launch writes is read.  Integer arithmetic and single fp32
+ * operations in a fixed order: no atomics, and every byte is defined whatever order the threads run in.  With frames == 0 the
+ * launch reads each crop window and its 2-pixel halo of image / mask.  Parity with cv2's dilate and resize unpinned (cv2 absent),
+ * as the rest of the paste-back.  Addition to ABI 6 (struct id 31, unchanged). */
+int mobi_camera_copy_paste(const mobi_camera_export_params* p, void* stream);
 
 /* Lidar-on-camera overlays of a whole sampled batch (scripts/inference_test_bench.py, overlay_lidar_on_image and its two calls
  * per object): a sweep's points projected into a frame and drawn over it, coloured by depth; every picture [H][W][3] uint8 RGB

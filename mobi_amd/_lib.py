@@ -346,6 +346,7 @@ SYMBOLS = {
     "mobi_drop_context": (C.c_int, [vp, vp, vp, vp, i32, i32, i64, vp]),
     "mobi_image_grid": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, vp, i64, vp]),
     "mobi_camera_export": (C.c_int, [C.POINTER(CameraExportParams), vp]),
+    "mobi_camera_copy_paste": (C.c_int, [C.POINTER(CameraExportParams), vp]),
     "mobi_lidar_overlay_workspace_bytes": (C.c_size_t, [i32, i32, i32]),
     "mobi_lidar_overlay": (C.c_int, [C.POINTER(LidarOverlayParams), vp]),
     "mobi_tensor_health": (C.c_int, [C.POINTER(HealthTensor), i32, vp, vp]),

@@ -550,11 +550,14 @@ __global__ __launch_bounds__(256) void image_grid_kernel(const ig_table t, unsig
 // from where whole rows go out as dwords (single bytes only up to a row's first and after its last 4-byte boundary).
 // The blend tile holds the mask with its 7-pixel halo in LDS and takes both blur passes from there.  The expressions are those
 // of paste_patch_kernel / blur_pass_kernel / blend_kernel above; this file is compiled without FMA contraction.
+// The copy-paste baseline (mobi_camera_copy_paste) is a second kernel over the same walk and the same tile bodies, templated on
+// the mode: the mask dilated 5 x 5 in place of the blur, the reference resized onto the mask's box in pred.
 // ---------------------------------------------------------------------------------------------------------
 constexpr int CE_TW = 64, CE_TH = 32, CE_R = 7, CE_K = 15;
 constexpr int CE_MW = CE_TW + 16, CE_MH = CE_TH + 2 * CE_R;          // mask tile: columns x0 - 8 .. x0 + 71, rows y0 - 7 .. y0 + 38
 constexpr int CE_OBW = CE_TW * 3;
 constexpr int CE_MAX_OBJECTS = 32, CE_BOX_PARTS = 64, CE_REF = 224;
+constexpr int CE_EXPORT = 0, CE_COPY_PASTE = 1, CE_DR = 2;  // the two modes of the export launch; the 5 x 5 dilation's radius
 struct ce_object {
   int left, top, cw, ch;
   long long off[5];                                          // frame, patch_pred, patch_gt, object_pred, object_ref
@@ -652,11 +655,96 @@ __device__ __forceinline__ void ce_store(const unsigned char* ob, int tx0, int t
   }
 }
 
+// taps of OpenCV's 8-bit INTER_LINEAR resize (ldm/data/nuscenes.py:resize_linear_u8): position in fp64, every operation
+// rounded on its own, the fraction rounded to fp32, 11-bit integer weights
+__device__ __forceinline__ void ce_cv_taps(int d, int n_dst, int n_src, int& i0, int& i1, int& w0, int& w1) {
+  const double scale = (double)n_src / (double)n_dst;
+  const double f = __dsub_rn(__dmul_rn(__dadd_rn((double)d, 0.5), scale), 0.5);
+  const double fl = floor(f);
+  i0 = (int)fl;
+  float frac = (float)__dsub_rn(f, fl);
+  if (i0 < 0) { i0 = 0; frac = 0.f; }
+  if (i0 >= n_src - 1) { i0 = n_src - 1; frac = 0.f; }
+  i1 = i0 + 1 < n_src - 1 ? i0 + 1 : n_src - 1;
+  w1 = (int)rintf(frac * 2048.0f);
+  w0 = (int)rintf((1.0f - frac) * 2048.0f);
+}
+
+// one byte of the object_ref picture: (ref * std[c] + mean[c]) * 255, each operation rounded, clamped, truncated (CLIP's constants)
+__device__ __forceinline__ int ce_ref_byte(const float* __restrict__ ref, int c, int y, int x) {
+  const float stdv[3] = {(float)0.26862954, (float)0.26130258, (float)0.27577711};
+  const float mean[3] = {(float)0.48145466, (float)0.4578275, (float)0.40821073};
+  float u = ref[((long long)c * CE_REF + y) * CE_REF + x] * stdv[c];
+  u = u + mean[c];
+  u = u * 255.0f;
+  u = u < 0.f ? 0.f : (u > 255.f ? 255.f : u);
+  return (int)u;
+}
+
+// the copy-paste baseline's paste: one byte of the object_ref picture resized to the mask's box, from the taps of its row and
+// column -- computed from `ref`, never read from the picture this launch writes
+__device__ __forceinline__ int ce_paste_byte(const float* __restrict__ ref, int c, int y0, int y1, int b0, int b1, int x0, int x1,
+                                             int a0, int a1) {
+  const int r0 = ce_ref_byte(ref, c, y0, x0) * a0 + ce_ref_byte(ref, c, y0, x1) * a1;
+  const int r1 = ce_ref_byte(ref, c, y1, x0) * a0 + ce_ref_byte(ref, c, y1, x1) * a1;
+  const int v = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
+  return v < 0 ? 0 : (v > 255 ? 255 : v);
+}
+
+// the copy-paste baseline's m on a blend tile, up to the vertical maximum: mt = the mask of one object with a 2-pixel halo around
+// the tile's part [ax0, ax1) x [ay0, ay1) of the region (what lies outside the frame, or is not needed, holds -inf and never wins),
+// hb = its horizontal 5-pixel maximum on the rows the vertical one reads.  Laid out as the blur's tiles.
+__device__ __forceinline__ void ce_dilate_rows(const ce_args& a, const float* __restrict__ mask, bool vec, int x0, int y0, int ax0,
+                                               int ax1, int ay0, int ay1, float* mt, float* hb) {
+  const int tid = threadIdx.x;
+  const float out = -__builtin_inff();
+  for (int i = tid; i < CE_MH * (CE_MW / 4); i += 256) {                 // the mask and its 2-pixel halo, 16 bytes a lane where whole
+    const int j = i / (CE_MW / 4), c4 = (i - j * (CE_MW / 4)) * 4;
+    const int y = y0 - CE_R + j, q0 = x0 - 8 + c4;
+    float4 v = make_float4(out, out, out, out);
+    if (y >= ay0 - CE_DR && y < ay1 + CE_DR && y >= 0 && y < a.H) {
+      const float* row = mask + (long long)y * a.W;
+      if (vec && q0 >= 0 && q0 + 3 < a.W && q0 >= ax0 - CE_DR && q0 + 3 < ax1 + CE_DR) {
+        v = *reinterpret_cast<const float4*>(row + q0);
+      } else {
+        const int lo = ax0 - CE_DR > 0 ? ax0 - CE_DR : 0, hi = ax1 + CE_DR < a.W ? ax1 + CE_DR : a.W;
+        v.x = (q0 >= lo && q0 < hi) ? row[q0] : out;
+        v.y = (q0 + 1 >= lo && q0 + 1 < hi) ? row[q0 + 1] : out;
+        v.z = (q0 + 2 >= lo && q0 + 2 < hi) ? row[q0 + 2] : out;
+        v.w = (q0 + 3 >= lo && q0 + 3 < hi) ? row[q0 + 3] : out;
+      }
+    }
+    *reinterpret_cast<float4*>(mt + j * CE_MW + c4) = v;
+  }
+  __syncthreads();
+  // horizontal maximum of the rows the vertical one reads: pixel lx of row j reads mask columns lx + 6 .. lx + 10
+  for (int i = tid; i < (CE_TH + 2 * CE_DR) * (CE_TW / 4); i += 256) {
+    const int j = CE_R - CE_DR + i / (CE_TW / 4), i4 = (i & (CE_TW / 4 - 1)) * 4;
+    float s[12];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      const float4 t = *reinterpret_cast<const float4*>(mt + j * CE_MW + i4 + 4 + 4 * q);
+      s[4 * q] = t.x; s[4 * q + 1] = t.y; s[4 * q + 2] = t.z; s[4 * q + 3] = t.w;
+    }
+    float acc[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      acc[e] = s[e + 2];
+#pragma unroll
+      for (int k = 1; k < 2 * CE_DR + 1; ++k) acc[e] = s[e + 2 + k] > acc[e] ? s[e + 2 + k] : acc[e];
+    }
+    *reinterpret_cast<float4*>(hb + j * CE_TW + i4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+  }
+}
+
 // tile kind 0: recon = m * I + (1 - m) * pred on the tile at (x0, y0) of the frame, x0 % 64 == 0; written to the frame picture
 // (frames) and, where the tile meets the crop window, to patch_pred.  Only what the tile's part of the region (the frame, or the
 // crop window when no frame is written) needs is read: its pixels of image, its pixels and a 7-pixel halo of mask.
-__device__ __forceinline__ void ce_tile_blend(const ce_args& a, const ce_object& o, int b, int x0, int y0, float* mt, float* hb,
-                                              unsigned char* ob) {
+// MODE CE_COPY_PASTE: m is the 5 x 5 maximum of mask over the pixels inside the frame (a 2-pixel halo; what lies outside the frame
+// or is not read holds -inf and never wins) and pred carries the resized reference on the mask's box.
+template <int MODE>
+__device__ __forceinline__ void ce_tile_blend(const ce_args& a, const ce_object& o, int b, int x0, int y0, const int* box, float* mt,
+                                              float* hb, unsigned char* ob) {
   const int tid = threadIdx.x;
   const int gx0 = a.frames ? 0 : o.left, gy0 = a.frames ? 0 : o.top;
   const int gx1 = a.frames ? a.W : o.left + o.cw, gy1 = a.frames ? a.H : o.top + o.ch;
@@ -666,53 +754,69 @@ __device__ __forceinline__ void ce_tile_blend(const ce_args& a, const ce_object&
   const float* mask = a.mask + (long long)b * plane;
   const float* image = a.image + (long long)b * 3 * plane;
   const bool vec = (a.W & 3) == 0 && ((reinterpret_cast<uintptr_t>(a.mask) | reinterpret_cast<uintptr_t>(a.image)) & 15) == 0;
-  for (int i = tid; i < CE_MH * (CE_MW / 4); i += 256) {                 // the mask and its halo, 16 bytes a lane where whole
-    const int j = i / (CE_MW / 4), c4 = (i - j * (CE_MW / 4)) * 4;
-    const int y = y0 - CE_R + j, q0 = x0 - 8 + c4;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (y >= ay0 - CE_R && y < ay1 + CE_R) {
-      const float* row = mask + (long long)ce_reflect(y, a.H) * a.W;
-      if (vec && q0 >= 0 && q0 + 3 < a.W && q0 >= ax0 - CE_R && q0 + 3 < ax1 + CE_R) {
-        v = *reinterpret_cast<const float4*>(row + q0);
-      } else {
-        v.x = (q0 >= ax0 - CE_R && q0 < ax1 + CE_R) ? row[ce_reflect(q0, a.W)] : 0.f;
-        v.y = (q0 + 1 >= ax0 - CE_R && q0 + 1 < ax1 + CE_R) ? row[ce_reflect(q0 + 1, a.W)] : 0.f;
-        v.z = (q0 + 2 >= ax0 - CE_R && q0 + 2 < ax1 + CE_R) ? row[ce_reflect(q0 + 2, a.W)] : 0.f;
-        v.w = (q0 + 3 >= ax0 - CE_R && q0 + 3 < ax1 + CE_R) ? row[ce_reflect(q0 + 3, a.W)] : 0.f;
+  if constexpr (MODE == CE_COPY_PASTE) {
+    ce_dilate_rows(a, mask, vec, x0, y0, ax0, ax1, ay0, ay1, mt, hb);
+  } else {
+    for (int i = tid; i < CE_MH * (CE_MW / 4); i += 256) {                 // the mask and its halo, 16 bytes a lane where whole
+      const int j = i / (CE_MW / 4), c4 = (i - j * (CE_MW / 4)) * 4;
+      const int y = y0 - CE_R + j, q0 = x0 - 8 + c4;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (y >= ay0 - CE_R && y < ay1 + CE_R) {
+        const float* row = mask + (long long)ce_reflect(y, a.H) * a.W;
+        if (vec && q0 >= 0 && q0 + 3 < a.W && q0 >= ax0 - CE_R && q0 + 3 < ax1 + CE_R) {
+          v = *reinterpret_cast<const float4*>(row + q0);
+        } else {
+          v.x = (q0 >= ax0 - CE_R && q0 < ax1 + CE_R) ? row[ce_reflect(q0, a.W)] : 0.f;
+          v.y = (q0 + 1 >= ax0 - CE_R && q0 + 1 < ax1 + CE_R) ? row[ce_reflect(q0 + 1, a.W)] : 0.f;
+          v.z = (q0 + 2 >= ax0 - CE_R && q0 + 2 < ax1 + CE_R) ? row[ce_reflect(q0 + 2, a.W)] : 0.f;
+          v.w = (q0 + 3 >= ax0 - CE_R && q0 + 3 < ax1 + CE_R) ? row[ce_reflect(q0 + 3, a.W)] : 0.f;
+        }
       }
+      *reinterpret_cast<float4*>(mt + j * CE_MW + c4) = v;
     }
-    *reinterpret_cast<float4*>(mt + j * CE_MW + c4) = v;
-  }
-  __syncthreads();
-  for (int i = tid; i < CE_MH * (CE_TW / 4); i += 256) {                 // horizontal pass: pixel lx reads mask columns lx + 1 + k
-    const int j = i / (CE_TW / 4), i4 = (i - j * (CE_TW / 4)) * 4;
-    float s[20];
+    __syncthreads();
+    for (int i = tid; i < CE_MH * (CE_TW / 4); i += 256) {                 // horizontal pass: pixel lx reads mask columns lx + 1 + k
+      const int j = i / (CE_TW / 4), i4 = (i - j * (CE_TW / 4)) * 4;
+      float s[20];
 #pragma unroll
-    for (int q = 0; q < 5; ++q) {
-      const float4 t = *reinterpret_cast<const float4*>(mt + j * CE_MW + i4 + 4 * q);
-      s[4 * q] = t.x; s[4 * q + 1] = t.y; s[4 * q + 2] = t.z; s[4 * q + 3] = t.w;
+      for (int q = 0; q < 5; ++q) {
+        const float4 t = *reinterpret_cast<const float4*>(mt + j * CE_MW + i4 + 4 * q);
+        s[4 * q] = t.x; s[4 * q + 1] = t.y; s[4 * q + 2] = t.z; s[4 * q + 3] = t.w;
+      }
+      float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int k = 0; k < CE_K; ++k) {
+        const float t = a.taps[k];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] += t * s[e + k + 1];
+      }
+      *reinterpret_cast<float4*>(hb + j * CE_TW + i4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
     }
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < CE_K; ++k) {
-      const float t = a.taps[k];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[e] += t * s[e + k + 1];
-    }
-    *reinterpret_cast<float4*>(hb + j * CE_TW + i4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
   }
   __syncthreads();
   const float sy = (float)a.hs / (float)o.ch, sx = (float)a.ws / (float)o.cw;
   const float* patch = a.patch_pred + (long long)b * 3 * a.hs * a.ws;
+  const int bx1 = box[0], by1 = box[2], sw = box[1] - bx1, sh = box[3] - by1;       // (read in copy-paste mode only)
+  const float* ref = a.ref + (long long)b * 3 * CE_REF * CE_REF;
   for (int p = 0; p < 2; ++p) {                                          // vertical pass and the blend, four pixels a lane
     const int ly = (tid >> 4) + 16 * p, lx4 = (tid & 15) * 4, y = y0 + ly, x = x0 + lx4;
     if (y < ay0 || y >= ay1 || x >= ax1 || x + 3 < ax0) continue;
     float m[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (MODE == CE_COPY_PASTE) {
+      const float4 h0 = *reinterpret_cast<const float4*>(hb + (ly + CE_R - CE_DR) * CE_TW + lx4);
+      m[0] = h0.x; m[1] = h0.y; m[2] = h0.z; m[3] = h0.w;
 #pragma unroll
-    for (int k = 0; k < CE_K; ++k) {
-      const float t = a.taps[k];
-      const float4 h = *reinterpret_cast<const float4*>(hb + (ly + k) * CE_TW + lx4);
-      m[0] += t * h.x; m[1] += t * h.y; m[2] += t * h.z; m[3] += t * h.w;
+      for (int k = 1; k < 2 * CE_DR + 1; ++k) {
+        const float4 h = *reinterpret_cast<const float4*>(hb + (ly + CE_R - CE_DR + k) * CE_TW + lx4);
+        m[0] = h.x > m[0] ? h.x : m[0]; m[1] = h.y > m[1] ? h.y : m[1]; m[2] = h.z > m[2] ? h.z : m[2]; m[3] = h.w > m[3] ? h.w : m[3];
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < CE_K; ++k) {
+        const float t = a.taps[k];
+        const float4 h = *reinterpret_cast<const float4*>(hb + (ly + k) * CE_TW + lx4);
+        m[0] += t * h.x; m[1] += t * h.y; m[2] += t * h.z; m[3] += t * h.w;
+      }
     }
     const bool whole = vec && x >= ax0 && x + 3 < ax1;
     const int cy = y - o.top;
@@ -720,6 +824,18 @@ __device__ __forceinline__ void ce_tile_blend(const ce_args& a, const ce_object&
     int py0 = 0, py1 = 0;
     float ply = 0.f;
     if (row_in) ce_taps(sy, cy, a.hs, py0, py1, ply);
+    const bool paste_row = MODE == CE_COPY_PASTE && sw > 0 && sh > 0 && y >= by1 && y < by1 + sh;
+    int ry0 = 0, ry1 = 0, rb0 = 0, rb1 = 0;
+    int rx0[4] = {0, 0, 0, 0}, rx1[4] = {0, 0, 0, 0}, ra0[4] = {0, 0, 0, 0}, ra1[4] = {0, 0, 0, 0};
+    bool paste[4] = {false, false, false, false};                        // the paste's taps: one set per row and per column, not per channel
+    if (paste_row) {
+      ce_cv_taps(y - by1, sh, CE_REF, ry0, ry1, rb0, rb1);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        paste[e] = x + e >= bx1 && x + e < bx1 + sw;
+        if (paste[e]) ce_cv_taps(x + e - bx1, sw, CE_REF, rx0[e], rx1[e], ra0[e], ra1[e]);
+      }
+    }
     unsigned bytes[12];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -746,6 +862,7 @@ __device__ __forceinline__ void ce_tile_blend(const ce_args& a, const ce_object&
           ce_taps(sx, cx, a.ws, px0, px1, plx);
           pred = (float)ce_patch_byte(pc, a.ws, py0, py1, px0, px1, ply, plx);
         }
+        if (paste[e]) pred = (float)ce_paste_byte(ref, c, ry0, ry1, rb0, rb1, rx0[e], rx1[e], ra0[e], ra1[e]);
         const float r = m[e] * iu + (1.0f - m[e]) * pred;
         int q = __float2int_rn(r);                                       // nearest even, saturating
         q = q < 0 ? 0 : (q > 255 ? 255 : q);
@@ -787,21 +904,6 @@ __device__ __forceinline__ void ce_tile_patch(const ce_args& a, const ce_object&
   ce_store(ob, x0, y0, x0, y0, x1, y1, a.out + o.off[2], (long long)o.cw * 3, 0, 0);
 }
 
-// taps of OpenCV's 8-bit INTER_LINEAR resize (ldm/data/nuscenes.py:resize_linear_u8): position in fp64, every operation
-// rounded on its own, the fraction rounded to fp32, 11-bit integer weights
-__device__ __forceinline__ void ce_cv_taps(int d, int n_dst, int n_src, int& i0, int& i1, int& w0, int& w1) {
-  const double scale = (double)n_src / (double)n_dst;
-  const double f = __dsub_rn(__dmul_rn(__dadd_rn((double)d, 0.5), scale), 0.5);
-  const double fl = floor(f);
-  i0 = (int)fl;
-  float frac = (float)__dsub_rn(f, fl);
-  if (i0 < 0) { i0 = 0; frac = 0.f; }
-  if (i0 >= n_src - 1) { i0 = n_src - 1; frac = 0.f; }
-  i1 = i0 + 1 < n_src - 1 ? i0 + 1 : n_src - 1;
-  w1 = (int)rintf(frac * 2048.0f);
-  w0 = (int)rintf((1.0f - frac) * 2048.0f);
-}
-
 // pred at frame pixel (y, x): P(patch_pred) inside the crop window, 0 elsewhere -- recomputed, not read from another block's tile
 __device__ __forceinline__ int ce_pred_at(const ce_args& a, const ce_object& o, const float* __restrict__ pc, float sy, float sx,
                                           int y, int x) {
@@ -815,6 +917,8 @@ __device__ __forceinline__ int ce_pred_at(const ce_args& a, const ce_object& o, 
 }
 
 // tile kind 2: object_pred = cv2.resize(pred[y1:y2, x1:x2], (224, 224)) on the tile at (x0, y0) of the 224 x 224 picture
+// MODE CE_COPY_PASTE: the box of pred holds the pasted reference and nothing else, so every tap is a `ce_paste_byte`
+template <int MODE>
 __device__ __forceinline__ void ce_tile_object(const ce_args& a, const ce_object& o, int b, int x0, int y0, const int* box,
                                                unsigned char* ob) {
   const int bx1 = box[0], bx2 = box[1], by1 = box[2], by2 = box[3];
@@ -825,16 +929,34 @@ __device__ __forceinline__ void ce_tile_object(const ce_args& a, const ce_object
   const int lx = threadIdx.x & 63, x = x0 + lx;
   int xi0 = 0, xi1 = 0, a0 = 0, a1 = 0;
   if (x < CE_REF) ce_cv_taps(x, CE_REF, sw, xi0, xi1, a0, a1);
+  const float* ref = a.ref + (long long)b * 3 * CE_REF * CE_REF;
+  int tx[2][4] = {}, ty[2][4] = {};                                      // copy-paste: the paste's taps at box columns xi0, xi1 / rows yi0, yi1
+  if (MODE == CE_COPY_PASTE && x < CE_REF) {
+    ce_cv_taps(xi0, sw, CE_REF, tx[0][0], tx[0][1], tx[0][2], tx[0][3]);
+    ce_cv_taps(xi1, sw, CE_REF, tx[1][0], tx[1][1], tx[1][2], tx[1][3]);
+  }
   for (int ly = threadIdx.x >> 6; ly < CE_TH; ly += 4) {
     const int y = y0 + ly;
     if (x >= CE_REF || y >= CE_REF) continue;
     int yi0, yi1, b0, b1;
     ce_cv_taps(y, CE_REF, sh, yi0, yi1, b0, b1);
+    if constexpr (MODE == CE_COPY_PASTE) {
+      ce_cv_taps(yi0, sh, CE_REF, ty[0][0], ty[0][1], ty[0][2], ty[0][3]);
+      ce_cv_taps(yi1, sh, CE_REF, ty[1][0], ty[1][1], ty[1][2], ty[1][3]);
+    }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const float* pc = patch + (long long)c * a.hs * a.ws;
-      const int r0 = ce_pred_at(a, o, pc, sy, sx, by1 + yi0, bx1 + xi0) * a0 + ce_pred_at(a, o, pc, sy, sx, by1 + yi0, bx1 + xi1) * a1;
-      const int r1 = ce_pred_at(a, o, pc, sy, sx, by1 + yi1, bx1 + xi0) * a0 + ce_pred_at(a, o, pc, sy, sx, by1 + yi1, bx1 + xi1) * a1;
+      int r0, r1;
+      if constexpr (MODE == CE_COPY_PASTE) {
+        r0 = ce_paste_byte(ref, c, ty[0][0], ty[0][1], ty[0][2], ty[0][3], tx[0][0], tx[0][1], tx[0][2], tx[0][3]) * a0 +
+             ce_paste_byte(ref, c, ty[0][0], ty[0][1], ty[0][2], ty[0][3], tx[1][0], tx[1][1], tx[1][2], tx[1][3]) * a1;
+        r1 = ce_paste_byte(ref, c, ty[1][0], ty[1][1], ty[1][2], ty[1][3], tx[0][0], tx[0][1], tx[0][2], tx[0][3]) * a0 +
+             ce_paste_byte(ref, c, ty[1][0], ty[1][1], ty[1][2], ty[1][3], tx[1][0], tx[1][1], tx[1][2], tx[1][3]) * a1;
+      } else {
+        const float* pc = patch + (long long)c * a.hs * a.ws;
+        r0 = ce_pred_at(a, o, pc, sy, sx, by1 + yi0, bx1 + xi0) * a0 + ce_pred_at(a, o, pc, sy, sx, by1 + yi0, bx1 + xi1) * a1;
+        r1 = ce_pred_at(a, o, pc, sy, sx, by1 + yi1, bx1 + xi0) * a0 + ce_pred_at(a, o, pc, sy, sx, by1 + yi1, bx1 + xi1) * a1;
+      }
       int v = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
       v = v < 0 ? 0 : (v > 255 ? 255 : v);
       ob[ly * CE_OBW + lx * 3 + c] = (unsigned char)v;
@@ -847,28 +969,22 @@ __device__ __forceinline__ void ce_tile_object(const ce_args& a, const ce_object
 
 // tile kind 3: object_ref = un_norm_clip(ref) * 255 on the tile at (x0, y0) of the 224 x 224 picture
 __device__ __forceinline__ void ce_tile_ref(const ce_args& a, const ce_object& o, int b, int x0, int y0, unsigned char* ob) {
-  const float stdv[3] = {(float)0.26862954, (float)0.26130258, (float)0.27577711};
-  const float mean[3] = {(float)0.48145466, (float)0.4578275, (float)0.40821073};
   const float* ref = a.ref + (long long)b * 3 * CE_REF * CE_REF;
   const int lx = threadIdx.x & 63, x = x0 + lx;
   for (int ly = threadIdx.x >> 6; ly < CE_TH; ly += 4) {
     const int y = y0 + ly;
     if (x >= CE_REF || y >= CE_REF) continue;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      float u = ref[((long long)c * CE_REF + y) * CE_REF + x] * stdv[c];
-      u = u + mean[c];
-      u = u * 255.0f;
-      u = u < 0.f ? 0.f : (u > 255.f ? 255.f : u);
-      ob[ly * CE_OBW + lx * 3 + c] = (unsigned char)(int)u;
-    }
+    for (int c = 0; c < 3; ++c) ob[ly * CE_OBW + lx * 3 + c] = (unsigned char)ce_ref_byte(ref, c, y, x);
   }
   __syncthreads();
   const int x1 = x0 + CE_TW < CE_REF ? x0 + CE_TW : CE_REF, y1 = y0 + CE_TH < CE_REF ? y0 + CE_TH : CE_REF;
   ce_store(ob, x0, y0, x0, y0, x1, y1, a.out + o.off[4], (long long)CE_REF * 3, 0, 0);
 }
 
-__global__ __launch_bounds__(256) void camera_export_kernel(const ce_args a, const ce_table t) {
+// the walk of both export kernels: MODE picks the form of the blend and object tiles
+template <int MODE>
+__device__ __forceinline__ void ce_walk(const ce_args& a, const ce_table& t) {
   __shared__ __attribute__((aligned(16))) float mt[CE_MH * CE_MW];
   __shared__ __attribute__((aligned(16))) float hb[CE_MH * CE_TW];
   __shared__ __attribute__((aligned(16))) unsigned char ob[CE_TH * CE_OBW];
@@ -895,14 +1011,14 @@ __global__ __launch_bounds__(256) void camera_export_kernel(const ce_args a, con
   __syncthreads();
   for (int i = blockIdx.x; i < total; i += gridDim.x) {
     if (i < n_blend) {
-      ce_tile_blend(a, o, b, (bx0 + i % nbx) * CE_TW, (by0 + i / nbx) * CE_TH, mt, hb, ob);
+      ce_tile_blend<MODE>(a, o, b, (bx0 + i % nbx) * CE_TW, (by0 + i / nbx) * CE_TH, box, mt, hb, ob);
     } else if (i < n_blend + n_patch) {
       const int k = i - n_blend;
       ce_tile_patch(a, o, b, (k % npx) * CE_TW, (k / npx) * CE_TH, ob);
     } else if (i < n_blend + n_patch + N_REF) {
       const int k = i - n_blend - n_patch;
       if (k == 0 && threadIdx.x == 0) a.status[b] = (box[1] - box[0] <= 0 || box[3] - box[2] <= 0) ? 1 : 0;
-      ce_tile_object(a, o, b, (k % NRX) * CE_TW, (k / NRX) * CE_TH, box, ob);
+      ce_tile_object<MODE>(a, o, b, (k % NRX) * CE_TW, (k / NRX) * CE_TH, box, ob);
     } else {
       const int k = i - n_blend - n_patch - N_REF;
       ce_tile_ref(a, o, b, (k % NRX) * CE_TW, (k / NRX) * CE_TH, ob);
@@ -910,6 +1026,11 @@ __global__ __launch_bounds__(256) void camera_export_kernel(const ce_args a, con
     __syncthreads();
   }
 }
+
+__global__ __launch_bounds__(256) void camera_export_kernel(const ce_args a, const ce_table t) { ce_walk<CE_EXPORT>(a, t); }
+
+// the copy-paste baseline (include/mobi_engine.h, mobi_camera_copy_paste): the same tiles, with the dilated mask and the pasted reference
+__global__ __launch_bounds__(256) void camera_copy_paste_kernel(const ce_args a, const ce_table t) { ce_walk<CE_COPY_PASTE>(a, t); }
 
 // ---------------------------------------------------------------------------------------------------------
 // Lidar-on-camera overlays of a batch (include/mobi_engine.h, mobi_lidar_overlay): a sweep's points projected into a frame and
@@ -1144,9 +1265,9 @@ extern "C" int mobi_image_grid(const mobi_image_grid_source* sources, int32_t n_
   return MOBI_OK;
 }
 
-extern "C" int mobi_camera_export(const mobi_camera_export_params* p, void* stream) {
-  if (!p || !p->patch_pred || !p->patch_gt || !p->ref || !p->image || !p->mask || !p->taps || !p->crop || !p->offsets ||
-      !p->box_ws || !p->out) return MOBI_ERR_ARG;
+static int camera_export_launch(const mobi_camera_export_params* p, void* stream, int mode) {
+  if (!p || !p->patch_pred || !p->patch_gt || !p->ref || !p->image || !p->mask || (mode == CE_EXPORT && !p->taps) || !p->crop ||
+      !p->offsets || !p->box_ws || !p->out) return MOBI_ERR_ARG;
   if (p->batch <= 0 || p->hs <= 0 || p->ws <= 0 || p->ref_h <= 0 || p->ref_w <= 0 || p->H <= 0 || p->W <= 0 || p->out_bytes <= 0)
     return MOBI_ERR_ARG;
   if (p->ref_h != CE_REF || p->ref_w != CE_REF || p->batch > CE_MAX_OBJECTS) return MOBI_ERR_UNSUPPORTED;
@@ -1180,9 +1301,17 @@ extern "C" int mobi_camera_export(const mobi_camera_export_params* p, void* stre
   ce_args a = {p->patch_pred, p->patch_gt, p->ref, p->image, p->mask, p->taps, p->box_ws, p->out,
                reinterpret_cast<int*>(p->out + p->status_offset), p->hs, p->ws, p->H, p->W, p->frames != 0};
   hipLaunchKernelGGL(camera_box_kernel, dim3(CE_BOX_PARTS, p->batch), dim3(256), 0, ST(stream), p->mask, p->box_ws, p->H, p->W);
-  hipLaunchKernelGGL(camera_export_kernel, dim3(most > 2048 ? 2048 : most, p->batch), dim3(256), 0, ST(stream), a, t);
+  const dim3 grid(most > 2048 ? 2048 : most, p->batch);
+  if (mode == CE_COPY_PASTE) hipLaunchKernelGGL(camera_copy_paste_kernel, grid, dim3(256), 0, ST(stream), a, t);
+  else hipLaunchKernelGGL(camera_export_kernel, grid, dim3(256), 0, ST(stream), a, t);
   MOBI_CHECK_LAUNCH();
   return MOBI_OK;
+}
+
+extern "C" int mobi_camera_export(const mobi_camera_export_params* p, void* stream) { return camera_export_launch(p, stream, CE_EXPORT); }
+
+extern "C" int mobi_camera_copy_paste(const mobi_camera_export_params* p, void* stream) {
+  return camera_export_launch(p, stream, CE_COPY_PASTE);
 }
 
 static inline long long lo_key_stride(long long H, long long W) { return (H * W + 3) & ~3LL; }

@@ -119,7 +119,37 @@ def paste_camera_patch(*, patch_pred, image, mask, crop, ksize=15, sigma=7.0):
     return ops.blend_frame(blur, image, frame), frame
 
 
-def export_camera_batch(*, patch_pred, patch_gt, ref_image, image, mask, crop, frames=True, ksize=15, sigma=7.0, return_device=False):
+def copy_paste_camera_patch(pred_u8, image, mask, ref_u8):
+    """The copy-paste baseline's paste-back of ONE object in numpy (scripts/inference_test_bench.py:503-516 with --copy-paste), the
+    documented meaning of `mobi_camera_copy_paste` (include/mobi_engine.h) and the slow path.  pred_u8: uint8 [H, W, 3], P(patch_pred)
+    on the crop window and 0 elsewhere; image: fp32 [3, H, W] in [-1, 1]; mask: [H, W] (1 = keep); ref_u8: uint8 [224, 224, 3], the
+    object_ref picture.  Returns (recon uint8 [H, W, 3], pred uint8 [H, W, 3], (y1, y2, x1, x2)):
+      box    the rows / columns of the pixels with 1 - mask != 0, max exclusive, from the UNdilated mask
+      pred   pred_u8 with pred[y1:y2, x1:x2] = resize_linear_u8(ref_u8, y2 - y1, x2 - x1)
+      m      the maximum of mask over the 5 x 5 neighbourhood, over pixels inside the frame only (cv2.dilate(mask, ones(5, 5)))
+      recon  m * I + (1 - m) * pred in fp32, every operation rounded on its own, to nearest even, clamped
+    An empty exclusive box (box = None): nothing is pasted.  Channel order is the caller's: every step is per channel."""
+    from .nuscenes import resize_linear_u8
+    mask = np.asarray(mask, dtype=np.float32)
+    H, W = mask.shape
+    pred = np.array(pred_u8, dtype=np.uint8)
+    ys, xs = np.nonzero(np.float32(1) - mask)
+    box = (int(ys.min()), int(ys.max()), int(xs.min()), int(xs.max())) if len(ys) else None
+    if box is not None and (box[1] - box[0] <= 0 or box[3] - box[2] <= 0):
+        box = None
+    if box is not None:
+        y1, y2, x1, x2 = box
+        pred[y1:y2, x1:x2] = resize_linear_u8(np.asarray(ref_u8, dtype=np.uint8), y2 - y1, x2 - x1)
+    padded = np.full((H + 4, W + 4), -np.inf, dtype=np.float32)
+    padded[2:H + 2, 2:W + 2] = mask
+    m = np.max([padded[dy:dy + H, dx:dx + W] for dy in range(5) for dx in range(5)], axis=0)[..., None]
+    I = frame_u8(image).astype(np.float32)
+    recon = m * I + (np.float32(1) - m) * pred.astype(np.float32)
+    return np.clip(np.rint(recon), 0, 255).astype(np.uint8), pred, box
+
+
+def export_camera_batch(*, patch_pred, patch_gt, ref_image, image, mask, crop, frames=True, ksize=15, sigma=7.0, return_device=False,
+                        copy_paste=False):
     """The camera results of scripts/inference_test_bench.py:478-527 for the WHOLE batch: `mobi_camera_export`, then ONE copy into
     pinned host memory.  patch_pred / patch_gt: fp32 [B, 3, hs, ws] in [-1, 1]; ref_image: [B, 3, h, w] CLIP-normalised (resized to
     224 x 224 first, as un_norm_clip does); image: [B, 3, H, W] in [-1, 1]; mask: [B, H, W] (1 = keep); crop: B x (left, top,
@@ -127,14 +157,14 @@ def export_camera_batch(*, patch_pred, patch_gt, ref_image, image, mask, crop, f
     BGR arrays: frame (only with `frames`), patch_pred (the composited crop), patch_gt, object_pred, object_ref.  ValueError
     names an object whose mask box is empty once its last row and column are excluded, as the reference slices it.
     return_device: (pictures, the uint8 device buffer, its `ops.camera_export_layout`) -- for `overlay_lidar_batch`, which reads the
-    recomposed frames in place."""
+    recomposed frames in place.  copy_paste: the baseline's pictures instead (`mobi_camera_copy_paste`, `copy_paste_camera_patch`)."""
     assert ksize == 15, "mobi_camera_export is built for the reference's 15-tap blur"
     dev = patch_pred.device
     f = lambda t: _as_dev(t, dev).float().contiguous()
     crops = [tuple(int(v) for v in c) for c in (crop.tolist() if isinstance(crop, torch.Tensor) else crop)]
     ref = _resize(f(ref_image), (224, 224)).contiguous()
-    taps = torch.from_numpy(gaussian_kernel1d(ksize, sigma)).to(dev)
-    out, layout = ops.camera_export(f(patch_pred), f(patch_gt), ref, f(image), f(mask), crops, taps, frames=frames)
+    taps = None if copy_paste else torch.from_numpy(gaussian_kernel1d(ksize, sigma)).to(dev)
+    out, layout = ops.camera_export(f(patch_pred), f(patch_gt), ref, f(image), f(mask), crops, taps, frames=frames, copy_paste=copy_paste)
     host = torch.empty(layout["bytes"], dtype=torch.uint8, pin_memory=True)
     with ops._Timed("camera_export_d2h", 0.0, float(layout["bytes"])):
         host.copy_(out, non_blocking=True)

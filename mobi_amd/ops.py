@@ -1951,18 +1951,19 @@ def camera_export_layout(crops, H, W, frames=True):
     return {"objects": objects, "status": offset, "bytes": offset + 4 * len(objects)}
 
 
-def camera_export(patch_pred, patch_gt, ref, image, mask, crops, taps, *, frames=True):
+def camera_export(patch_pred, patch_gt, ref, image, mask, crops, taps, *, frames=True, copy_paste=False):
     """The test bench's camera pictures of a batch (include/mobi_engine.h, mobi_camera_export): patch_pred / patch_gt fp32
     [B, 3, hs, ws], ref fp32 [B, 3, 224, 224], image fp32 [B, 3, H, W], mask fp32 [B, H, W], crops B x (left, top, crop_W, crop_H)
     on the host, taps fp32 [15] -> (uint8 device buffer, `camera_export_layout`).  A box reduction and one export launch per 32
-    objects, whatever the crops."""
+    objects, whatever the crops.  copy_paste: the same launch in copy-paste mode (mobi_camera_copy_paste: the reference pasted on
+    the mask's box, the mask dilated 5 x 5 instead of blurred); taps may then be None."""
     lib = _lib.load()
-    for t_ in (patch_pred, patch_gt, ref, image, mask, taps):
+    for t_ in (patch_pred, patch_gt, ref, image, mask) + (() if copy_paste else (taps,)):
         assert _dev(t_).dtype == torch.float32 and t_.is_contiguous() and t_.device == patch_pred.device
     b, _, hs, ws = patch_pred.shape
     _, _, H, W = image.shape
     assert patch_pred.shape[1] == 3 and patch_gt.shape == patch_pred.shape and ref.dim() == 4 and ref.shape[:2] == (b, 3)
-    assert image.shape[:2] == (b, 3) and tuple(mask.shape) == (b, H, W) and taps.numel() == 15 and len(crops) == b
+    assert image.shape[:2] == (b, 3) and tuple(mask.shape) == (b, H, W) and (copy_paste or taps.numel() == 15) and len(crops) == b
     layout = camera_export_layout(crops, H, W, frames)
     out = torch.empty(layout["bytes"], device=image.device, dtype=torch.uint8)
     box_ws = torch.empty((b, 64, 4), device=image.device, dtype=torch.int32)
@@ -1973,11 +1974,12 @@ def camera_export(patch_pred, patch_gt, ref, image, mask, crops, taps, *, frames
         offs = (C.c_int64 * (5 * n))(*[o.get(name, (0,))[0] for o in layout["objects"][lo:lo + n] for name in CAMERA_EXPORT_PICTURES])
         p = _lib.CameraExportParams()
         p.patch_pred, p.patch_gt, p.ref, p.image, p.mask = (_ptr(t_[lo:]) for t_ in (patch_pred, patch_gt, ref, image, mask))
-        p.taps, p.crop, p.offsets = _ptr(taps), C.cast(crop, C.c_void_p), C.cast(offs, C.c_void_p)
+        p.taps, p.crop, p.offsets = (None if copy_paste else _ptr(taps)), C.cast(crop, C.c_void_p), C.cast(offs, C.c_void_p)
         p.box_ws, p.out, p.out_bytes, p.status_offset = _ptr(box_ws[lo:]), _ptr(out), layout["bytes"], layout["status"] + 4 * lo
         p.batch, p.hs, p.ws, p.ref_h, p.ref_w, p.H, p.W, p.frames = n, hs, ws, ref.shape[2], ref.shape[3], H, W, int(bool(frames))
-        with _Timed("camera_export", 0.0, float(layout["bytes"]), f"b{n}"):
-            _lib.check(lib.mobi_camera_export(C.byref(p), _stream()), "mobi_camera_export")
+        entry = "mobi_camera_copy_paste" if copy_paste else "mobi_camera_export"
+        with _Timed("camera_export", 0.0, float(layout["bytes"]), f"b{n}{'.cp' if copy_paste else ''}"):
+            _lib.check(getattr(lib, entry)(C.byref(p), _stream()), entry)
     return out, layout
 
 

@@ -8,9 +8,13 @@
    rounded crop window, the resized ground-truth patch, the object crop resized to 224 x 224 with F.interpolate -- not OpenCV's
    integer resize, which torch lacks -- and the un-normalised reference image).  Device events around a replayed graph of 20 calls,
    median of 10, inputs warmed, the sides alternating in one process.  The byte floor of frames on is one read of image and mask and
-   one write of the uint8 frame per object, at the bandwidth `mobi_drop_context` reaches in the same run.
-2. The wall clock of one batch of `python -m mobi_amd.test_bench` at mobi_nusc_512 (8 objects, PLMS-50, scale 5, both save flags) on
-   a synthetic database, by stage (`--timing`: a synchronise after every stage).
+   one write of the uint8 frame per object, at the bandwidth `mobi_drop_context` reaches in the same run.  The same launch in
+   copy-paste mode (`mobi_camera_copy_paste`, frames on / off) alternates with them; its bar is the export with frames on.
+2. The wall clock of one batch of `python -m mobi_amd.bench_tree` at mobi_nusc_512 (8 objects, PLMS-50, scale 5, both save flags) on
+   a synthetic database, by stage (`--timing`: a synchronise after every stage), in three variants on one model: without the
+   lidar-on-camera overlays (`--no_overlays`) and with them, alternating twice, then one copy-paste batch
+   (`python -m mobi_amd.copy_paste`: one sampling step), then six copy-paste batches in a row with every lap printed: whether the
+   writer's `put` ever waits shows only in a run longer than its queue is deep.  (profiles/camera_copy_paste.txt)
 """
 import argparse
 import os
@@ -96,6 +100,10 @@ def main():
     flags = torch.ones(B, dtype=torch.int32, device="cuda")
     sides = {"export, frames on": lambda: ops.camera_export(patch_pred, patch_gt, ref, image, mask, crops, taps, frames=True),
              "export, frames off": lambda: ops.camera_export(patch_pred, patch_gt, ref, image, mask, crops, taps, frames=False),
+             "copy-paste, frames on": lambda: ops.camera_export(patch_pred, patch_gt, ref, image, mask, crops, None, frames=True,
+                                                                copy_paste=True),
+             "copy-paste, frames off": lambda: ops.camera_export(patch_pred, patch_gt, ref, image, mask, crops, None, frames=False,
+                                                                 copy_paste=True),
              "replaced: 8 x paste_camera_patch + torch pictures": replaced,
              "mobi_drop_context [8, 3, 900, 1600]": lambda: ops.drop_context(gt, inpaint, mask[:, None], flags)}
     graphs = {k: graph_of(fn) for k, fn in sides.items()}
@@ -121,6 +129,8 @@ def main():
         f"export, frames on is {med['export, frames on'] / (floor_bytes / bw * 1e3):.2f} x the floor")
     say(f"   export, frames on / replaced = {med['export, frames on'] / med['replaced: 8 x paste_camera_patch + torch pictures']:.3f}; "
         f"frames off / replaced = {med['export, frames off'] / med['replaced: 8 x paste_camera_patch + torch pictures']:.3f}")
+    say(f"   copy-paste, frames on / export, frames on = {med['copy-paste, frames on'] / med['export, frames on']:.3f}; "
+        f"frames off / export, frames off = {med['copy-paste, frames off'] / med['export, frames off']:.3f}")
     if not a.skip_batch:
         batch_by_stage(say)
     say()
@@ -128,6 +138,8 @@ def main():
 
 def batch_by_stage(say):
     from bench import build_model
+    from mobi_amd import copy_paste as cp
+    from mobi_amd import bench_tree as bt
     from mobi_amd import test_bench as tb
     from mobi_amd.ldm.util import load_config
     from tests import mini_db
@@ -136,17 +148,36 @@ def batch_by_stage(say):
     data = "data.params.test.params."
     overrides = ["model.params.lidar_stage_config.params.ckpt_path=null", "ref_mode=id-ref", "classes=[car]", f"{data}object_database_path={csv}",
                  f"{data}scene_database_path={pkl}", f"{data}num_samples_per_class=16", f"{data}min_lidar_points=8"]
-    opt = tb.build_parser().parse_args(["--outdir", os.path.join(tmp, "out"), "--plms", "--ddim_steps", "50", "--scale", "5",
-                                        "--n_samples", "8", "--n_workers", "0", "--save_samples", "--save_visualisations", "--timing"])
-    tb.seed_everything(opt.seed)
-    config = load_config(os.path.join(ROOT, "configs", "mobi_nusc_512.yaml"), overrides)
+    config_path = os.path.join(ROOT, "configs", "mobi_nusc_512.yaml")
     model = build_model("mobi_nusc_512").cuda().eval()
-    spent = tb.run(opt, config, model)
-    n = len(next(iter(spent.values())))
-    say(f"-- one test-bench batch at mobi_nusc_512 (random weights, synthetic database, 8 objects, PLMS-50, scale 5, --save_samples "
-        f"--save_visualisations, 900 x 1600 frames), wall clock by stage, ms; {n} batches, the first includes graph capture")
-    for name, laps in spent.items():
-        say(f"   {name:36s} first {1e3 * laps[0]:9.1f}   last {1e3 * laps[-1]:9.1f}")
+    common = ["--plms", "--ddim_steps", "50", "--scale", "5", "--n_samples", "8", "--n_workers", "0", "--save_samples",
+              "--save_visualisations", "--timing"]
+    say("-- one test-bench batch at mobi_nusc_512 (random weights, synthetic database, 8 objects, PLMS-50, scale 5, --save_samples "
+        "--save_visualisations, 900 x 1600 frames), wall clock by stage, ms; 2 batches per run, the first of the first run includes "
+        "graph capture; the runs in this order on one model")
+    variants = [("without overlays (--no_overlays)", bt.build_parser().parse_args, ["--no_overlays"]),
+                ("with overlays", bt.build_parser().parse_args, [])] * 2 + [("copy-paste (one step), with overlays", cp.parse, [])]
+    at_the_end = "waiting for the writer at the end"                     # (once per run, not a stage of a batch)
+    for k, (name, parse, extra) in enumerate(variants):
+        opt = parse(["--outdir", os.path.join(tmp, f"out{k}")] + common + extra)
+        tb.seed_everything(opt.seed)
+        spent = bt.run(opt, load_config(config_path, overrides), model)
+        say(f"   run {k + 1}: {name}")
+        for stage, laps in spent.items():
+            say(f"      {stage:36s} first {1e3 * laps[0]:9.1f}   last {1e3 * laps[-1]:9.1f}")
+        whole = sum(stage_laps[-1] for stage, stage_laps in spent.items() if stage != at_the_end)
+        say(f"      a whole batch (the last)             {1e3 * whole:9.1f}")
+    # does `put` ever wait?  Two batches against a queue two batches deep cannot show it: six copy-paste batches, every lap printed
+    csv, pkl = mini_db.build(os.path.join(tmp, "db48"), n_scenes=48, image_hw=(900, 1600))
+    long_run = [o for o in overrides if "database_path" not in o and "num_samples_per_class" not in o]
+    long_run += [f"{data}object_database_path={csv}", f"{data}scene_database_path={pkl}", f"{data}num_samples_per_class=48"]
+    opt = cp.parse(["--outdir", os.path.join(tmp, "out_long")] + common)
+    tb.seed_everything(opt.seed)
+    spent = bt.run(opt, load_config(config_path, long_run), model)
+    n = len(spent["sampling"])
+    say(f"   run {len(variants) + 1}: copy-paste (one step), with overlays, {n} batches of 8 objects; every batch, ms")
+    for stage, laps in spent.items():
+        say(f"      {stage:36s} " + " ".join(f"{1e3 * t:8.1f}" for t in laps))
 
 
 if __name__ == "__main__":
