@@ -1266,7 +1266,7 @@ def test_linear_f32(ops, m, n, k):
 def test_ff_geglu_fused(ops, dtype, rows, hidden, residual):
     """mobi_ff_geglu: (x W1v^T + b1v) * gelu(x W1g^T + b1g) . W2^T + b2 + residual in one launch (C = 320) against fp32
     torch with the hidden activation rounded to the storage type (as both engine paths do), and against the two-launch
-    path (GEGLU projection, then the output projection)."""
+    path (GEGLU projection, then the output projection).  Per row and channel, odd chunk counts, tile edges: test_gpu_ff_rows.py."""
     c = 320
     xf, xd = rnd(f"ff.x{rows}", (rows, c), dtype)
     rf, rd = rnd(f"ff.r{rows}", (rows, c), dtype)
