@@ -60,7 +60,8 @@ extern "C" {
  *      mobi_repack_multi (mobi_repack_entry 32); likewise the test bench's lidar-on-camera overlays, mobi_lidar_overlay +
  *      mobi_lidar_overlay_workspace_bytes (mobi_lidar_overlay_params 33, mobi_lidar_overlay_picture 34); likewise the numeric
  *      health launch, mobi_tensor_health (mobi_health_tensor 35, mobi_health_record 36); likewise the camera pictures of the
- *      test bench's copy-paste baseline, mobi_camera_copy_paste (mobi_camera_export_params 31 as it is, no new struct) */
+ *      test bench's copy-paste baseline, mobi_camera_copy_paste (mobi_camera_export_params 31 as it is, no new struct); likewise
+ *      the attention probe, mobi_attention_health (mobi_attention_health_record 37; mobi_attention_params 3 as it is) */
 #define MOBI_ABI_VERSION 6
 
 enum { MOBI_OK = 0, MOBI_ERR_ARG = -1, MOBI_ERR_UNSUPPORTED = -2, MOBI_ERR_LAUNCH = -3, MOBI_ERR_ALIGN = -4 };
@@ -75,7 +76,7 @@ const char* mobi_error_string(int code);
  * 15 row_chain, 16 chain_op, 17 layernorm_bwd, 18 attention_bwd, 19 split_source, 20 dpm_step, 21 lpips_distance,
  * 22 image_normalize, 23 mt_tensor, 24 mt_chunk, 25 grad_stats_record, 26 mt_pair, 27 loss_grad, 28 ref_augment, 29 snapshot_record,
  * 30 image_grid_source, 31 camera_export, 32 repack_entry, 33 lidar_overlay, 34 lidar_overlay_picture,
- * 35 health_tensor, 36 health_record.
+ * 35 health_tensor, 36 health_record, 37 attention_health_record.
  * Returns 0 for an unknown id. */
 size_t mobi_struct_size(int id);
 /* Development hook: the library reads its MOBI_* A/B environment variables once, at the first launch
@@ -569,6 +570,42 @@ typedef struct mobi_health_record {
   uint32_t absmax_bits, reserved; int64_t inf, nan, near, subnormal;
 } mobi_health_record;
 int mobi_tensor_health(const mobi_health_tensor* tensors, int32_t n_tensors, mobi_health_record* out, void* stream);
+
+/* The attention probe: a second, independent launch that recomputes one mobi_attention launch from the launch's own operands
+ * and says, per (image, head), where the operands and the scores lie, how far the scores rise behind the first 32 keys and how
+ * far the production result is from the exact one (mobi_amd/health.py: probe(attention=True); attention_health_ref is the
+ * definition in fp64 numpy).  p: the SAME params mobi_attention was given, p->out already written by it on this
+ * stream.  Read only: the records are the only bytes written.  In exact arithmetic on the stored 16-bit operands (q is NOT
+ * re-rounded: this is the mathematical launch, not a restatement of a kernel body), with cexp = 1 if q_log2_scaled else
+ * scale * log2(e):
+ *   e_ij = cexp * sum_c q_ic k_jc     the score as an exponent of two
+ *   m_i = max_j e_ij,  f_i = max_{j < min(32, tk)} e_ij,  rise_i = m_i - f_i >= 0
+ *   p_ij = 2^(e_ij - m_i),  l_i = sum_j p_ij,  o_i = sum_j p_ij v_j / l_i       (p stays fp32: never rounded to the storage type)
+ * Record, one per (image, head), out[image * heads + head]:
+ *   q / k / v_absmax_bits   fp32 bit pattern of the largest finite magnitude of this head's slice of the operand
+ *   in_nonfinite            inf + nan elements of this head's q, k and v slices
+ *   out_nonfinite           inf + nan elements of this head's slice of p->out
+ *   e_max, e_min            over all (i, j);   rise_max = max_i rise_i;   rows_rise_over = #{i: rise_i > rise_limit}
+ *   ref_absmax_bits         fp32 bit pattern of the largest |o_ic|
+ *   err_max                 max |float(out_ic) - o_ic| over the FINITE elements of out (0 without one)
+ *   err_row                 the smallest i that attains err_max; -1 if this head's slice of out has no finite element
+ * The three absmax fields and the two counts are always defined; with in_nonfinite > 0 the other fields of THAT head are
+ * unspecified (the launch is still safe, other heads' records are not affected).  The kernel computes the scores with fp32-
+ * accumulated MFMAs (products of 16-bit values are exact), the shift is the exact running row maximum, and every row's sums run
+ * in key order whatever the grid or the batch: no atomics, two launches give bit-equal records.  One block per (image, head):
+ * this is an instrument that runs under a probe, not a fast path.
+ * Accepts and rejects what mobi_attention does, with its codes, plus out NULL / rise_limit nan (MOBI_ERR_ARG) and out off 4
+ * bytes (MOBI_ERR_ALIGN); all before anything is enqueued.  Addition to ABI 6 (struct id 37). */
+typedef struct mobi_attention_health_record {
+  uint32_t q_absmax_bits, k_absmax_bits, v_absmax_bits;
+  int32_t in_nonfinite, out_nonfinite;
+  float e_max, e_min, rise_max;
+  int32_t rows_rise_over;
+  uint32_t ref_absmax_bits;
+  float err_max;
+  int32_t err_row;
+} mobi_attention_health_record;
+int mobi_attention_health(const mobi_attention_params* p, float rise_limit, mobi_attention_health_record* out, void* stream);
 
 typedef struct mobi_attention_bwd_params {
   const void* q; int64_t q_img_stride, q_row_stride;       /* T [image][tq][>= heads*dh], strides in elements */

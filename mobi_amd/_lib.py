@@ -257,6 +257,12 @@ class HealthRecord(C.Structure):
                 ("subnormal", i64)]
 
 
+class AttentionHealthRecord(C.Structure):
+    _fields_ = [("q_absmax_bits", C.c_uint32), ("k_absmax_bits", C.c_uint32), ("v_absmax_bits", C.c_uint32),
+                ("in_nonfinite", i32), ("out_nonfinite", i32), ("e_max", f32), ("e_min", f32), ("rise_max", f32),
+                ("rows_rise_over", i32), ("ref_absmax_bits", C.c_uint32), ("err_max", f32), ("err_row", i32)]
+
+
 STRUCT_IDS = {0: IgemmParams, 1: GroupNormParams, 2: LayerNormParams, 3: AttentionParams, 4: CtxAttentionParams,
               5: SkinnyLinearParams, 6: ConvSmallCinParams, 7: ConvSmallCoutParams, 8: DdimStepParams, 9: TwoKeyAdapterParams,
               10: RangePasteParams, 11: LidarMetricsParams, 12: RangePrepareParams, 13: ImagePrepareParams,
@@ -265,7 +271,7 @@ STRUCT_IDS = {0: IgemmParams, 1: GroupNormParams, 2: LayerNormParams, 3: Attenti
               21: LpipsDistanceParams, 22: ImageNormalizeParams, 23: MtTensor, 24: MtChunk, 25: GradStatsRecord,
               26: MtPair, 27: LossGradParams, 28: RefAugmentParams, 29: SnapshotRecord, 30: ImageGridSource,
               31: CameraExportParams, 32: RepackEntry, 33: LidarOverlayParams, 34: LidarOverlayPicture,
-              35: HealthTensor, 36: HealthRecord}
+              35: HealthTensor, 36: HealthRecord, 37: AttentionHealthRecord}
 
 # every symbol include/mobi_engine.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -350,6 +356,7 @@ SYMBOLS = {
     "mobi_lidar_overlay_workspace_bytes": (C.c_size_t, [i32, i32, i32]),
     "mobi_lidar_overlay": (C.c_int, [C.POINTER(LidarOverlayParams), vp]),
     "mobi_tensor_health": (C.c_int, [C.POINTER(HealthTensor), i32, vp, vp]),
+    "mobi_attention_health": (C.c_int, [C.POINTER(AttentionParams), f32, vp, vp]),
     "mobi_paste_patch": (C.c_int, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
     "mobi_gaussian_blur": (C.c_int, [vp, vp, vp, i32, i32, vp, i32, vp]),
     "mobi_blend_frame": (C.c_int, [vp, vp, vp, vp, i32, i32, vp]),

@@ -285,6 +285,7 @@ extern "C" size_t mobi_struct_size(int id) {
     case 34: return sizeof(mobi_lidar_overlay_picture);
     case 35: return sizeof(mobi_health_tensor);
     case 36: return sizeof(mobi_health_record);
+    case 37: return sizeof(mobi_attention_health_record);
     default: return 0;
   }
 }

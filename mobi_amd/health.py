@@ -23,6 +23,18 @@ include/mobi_engine.h (mobi_tensor_health) and DESIGN.md state it:
     near         finite and a >= near_abs (fp32 compare)       subnormal   exponent bits zero, mantissa != 0
     headroom     dtype max / absmax (inf for an all-zero tensor)
 
+`probe(attention=True)` looks inside the attention launches as well: every `ops.attention` launch is followed, on the same stream,
+by one `mobi_attention_health` launch (csrc/attention_health.hip) that recomputes it from its own operands with the exact row
+maximum as the shift and fp32 probabilities, into the probe's own record buffers (still ONE read-back, in `report()`):
+    rep.attention              one AttentionRow per launch; rep.rows is what it is without the flag, seq for seq
+    rep.attention_for(seq)     the AttentionRow of the launch whose own row is rep.rows[seq], or None
+An AttentionRow says whether the operands were already bad (in_nonfinite), where the scores lie as exponents of two (e_max, e_min),
+how far they rise behind the first 32 keys (rise_max; rows_rise_over counts the rows past RISE_LIMIT), and how far the production
+result is from the exact one (err_max at err_row of worst_head, against ref_absmax; out_nonfinite).  `attention_health_ref` is the
+definition in fp64 numpy (DESIGN.md 5a states it).  RISE_LIMIT only LABELS rows: it is what the comments of csrc/attention.hip
+state for the first pass of attention_rows_kernel and does not claim to predict which branch that kernel takes.  `ctx_attention`
+and `attention_bwd` launches are not probed.
+
 `audit_weights` measures a model's parameters as they will be rounded to a storage type, `heavy_tailed_` is a deterministic
 stand-in for trained weights, and `python -m mobi_amd.health` runs both on the model a config describes (see `main`).
 """
@@ -99,6 +111,163 @@ def tensor_health_ref(array_or_bits, dtype, near_abs):
             "inf": int(inf.sum()), "nan": int(nan.sum()), "near": int(near.sum()), "subnormal": int(sub.sum())}
 
 
+# --------------------------------------------------------------------------------------
+# the attention probe: the definition and its rows
+# --------------------------------------------------------------------------------------
+LOG2E = 1.4426950408889634
+# octaves a row's scores may rise above the maximum of its first 32 keys before the row is counted in rows_rise_over: the reach
+# csrc/attention.hip's comments give the first pass of attention_rows_kernel, which keeps the first 32 keys' shift (2^-24 is the
+# last fp16 probability that is not flushed, bf16 has fp32's exponent).  A label for rows, not a prediction of the kernel's branch.
+RISE_LIMIT = {"fp16": 20.0, "bf16": 120.0}
+_FLOAT_FIELDS = ("e_max", "e_min", "rise_max", "err_max")
+ATTENTION_REF_DTYPE = np.dtype([("q_absmax_bits", "<u4"), ("k_absmax_bits", "<u4"), ("v_absmax_bits", "<u4"), ("in_nonfinite", "<i4"),
+                                ("out_nonfinite", "<i4"), ("e_max", "<f8"), ("e_min", "<f8"), ("rise_max", "<f8"),
+                                ("rows_rise_over", "<i4"), ("ref_absmax_bits", "<u4"), ("err_max", "<f8"), ("err_row", "<i4"),
+                                ("ref_absmax", "<f8"), ("dot_abs_max", "<f8")])
+
+
+def _f32_bits(x):
+    return int(np.array([x], dtype=np.float32).view(np.uint32)[0])
+
+
+def _bits_f32(b):
+    return float(np.array([b], dtype=np.uint32).view(np.float32)[0])
+
+
+def attention_health_ref(q, k, v, out, heads, scale, v_rows=False, q_log2_scaled=False, rise_limit=None, rises=False):
+    """The definition of `mobi_attention_health`'s record in fp64 numpy.  q [n, tq, C], k [n, tk, C], v [n, tk, C] (v_rows) or
+    V^T [n, C, tk], out [n, tq, C]: torch tensors of one 16-bit storage type, any device, any strides.  On the stored values,
+    with cexp = 1 if q_log2_scaled else float32(scale) * log2(e) (the launch holds `scale` as fp32):
+        e_ij = cexp * sum_c q_ic k_jc,   m_i = max_j e_ij,   f_i = max_{j < min(32, tk)} e_ij,   rise_i = m_i - f_i
+        p_ij = 2^(e_ij - m_i),   l_i = sum_j p_ij,   o_i = sum_j p_ij v_j / l_i
+    -> a structured array, one element per (image, head), image-major: the record's fields (floats as fp64; ref_absmax_bits
+    is the pattern of ref_absmax rounded to fp32) plus ref_absmax and dot_abs_max = cexp * max_ij sum_c |q_ic k_jc| (what an
+    fp32 dot-product error bound scales with).  rise_limit: RISE_LIMIT of the storage type by default.  With in_nonfinite > 0
+    the fields behind the two counts are whatever numpy makes of the non-finite values: unspecified.  rises=True: also the
+    rise of every row, [n * heads, tq]."""
+    name = dtype_name(q.dtype)
+    if rise_limit is None:
+        rise_limit = RISE_LIMIT[name]
+    f64 = lambda t: t.detach().cpu().double().numpy()
+    qd, kd, od = f64(q), f64(k), f64(out)
+    vd = f64(v) if v_rows else f64(v).transpose(0, 2, 1)
+    n, tq, c = qd.shape
+    tk, dh = kd.shape[1], c // heads
+    cexp = 1.0 if q_log2_scaled else float(np.float32(scale)) * LOG2E
+    rec = np.zeros(n * heads, dtype=ATTENTION_REF_DTYPE)
+    all_rises = np.zeros((n * heads, tq))
+    with np.errstate(all="ignore"):
+        for i in range(n):
+            for h in range(heads):
+                r = rec[i * heads + h]
+                sl = slice(h * dh, (h + 1) * dh)
+                qh, kh, vh, oh = qd[i, :, sl], kd[i, :, sl], vd[i, :, sl], od[i, :, sl]
+                for tag, x in (("q", qh), ("k", kh), ("v", vh)):
+                    fin = np.isfinite(x)
+                    r[tag + "_absmax_bits"] = _f32_bits(np.abs(x[fin]).max()) if fin.any() else 0
+                    r["in_nonfinite"] += int((~fin).sum())
+                e = cexp * (qh @ kh.T)
+                m, f = e.max(1), e[:, :min(32, tk)].max(1)
+                rise = m - f
+                pr = np.exp2(e - m[:, None])
+                o = (pr @ vh) / pr.sum(1)[:, None]
+                fin = np.isfinite(oh)
+                r["out_nonfinite"] = int((~fin).sum())
+                r["e_max"], r["e_min"], r["rise_max"] = e.max(), e.min(), rise.max()
+                r["rows_rise_over"] = int((rise > rise_limit).sum())
+                r["ref_absmax"] = np.abs(o).max()
+                r["ref_absmax_bits"] = _f32_bits(r["ref_absmax"])
+                r["dot_abs_max"] = cexp * (np.abs(qh) @ np.abs(kh).T).max()
+                if fin.any():
+                    err = np.where(fin, np.abs(np.where(fin, oh, 0.0) - o), -1.0).max(1)
+                    r["err_max"] = err.max()
+                    r["err_row"] = int(np.argmax(err == err.max()))
+                else:
+                    r["err_max"], r["err_row"] = 0.0, -1
+                all_rises[i * heads + h] = rise
+    return (rec, all_rises) if rises else rec
+
+
+@dataclass
+class AttentionRow:
+    """One probed `ops.attention` launch: the records of its heads merged (max / min / sum) and the records themselves."""
+    seq: int                     # of the launch's own row in Report.rows
+    module: str
+    images: int
+    heads: int
+    tq: int
+    tk: int
+    dh: int
+    dtype: str
+    q_log2_scaled: bool
+    rise_limit: float
+    q_absmax: float
+    k_absmax: float
+    v_absmax: float
+    in_nonfinite: int
+    out_nonfinite: int
+    e_max: float
+    e_min: float
+    rise_max: float
+    rows_rise_over: int
+    ref_absmax: float
+    err_max: float
+    err_row: int                 # in worst_head
+    worst_head: tuple            # (image, head) of err_max
+    per_head: np.ndarray = field(default=None, repr=False, compare=False)   # ops.ATTENTION_HEALTH_DTYPE, [images * heads], image-major
+    kept: dict = field(default=None, repr=False, compare=False)             # keep=True: clones of q, k, v, out and the launch's arguments
+
+    @staticmethod
+    def from_records(seq, module, shape, dtype, q_log2_scaled, rise_limit, rec, kept=None):
+        images, heads, tq, tk, dh = shape
+        f32 = lambda bits: _bits_f32(int(bits.max()))
+        # the head with the largest error; a head whose record is unspecified (nan) never wins against a number
+        err = np.where(np.isnan(rec["err_max"]) | (rec["err_row"] < 0), -1.0, rec["err_max"])
+        w = int(np.argmax(err))
+        return AttentionRow(seq, module, images, heads, tq, tk, dh, dtype, bool(q_log2_scaled), float(rise_limit),
+                            f32(rec["q_absmax_bits"]), f32(rec["k_absmax_bits"]), f32(rec["v_absmax_bits"]),
+                            int(rec["in_nonfinite"].sum()), int(rec["out_nonfinite"].sum()), float(rec["e_max"].max()),
+                            float(rec["e_min"].min()), float(rec["rise_max"].max()), int(rec["rows_rise_over"].sum()),
+                            f32(rec["ref_absmax_bits"]), float(rec["err_max"][w]), int(rec["err_row"][w]), (w // heads, w % heads),
+                            rec, kept)
+
+    def head(self, image, head):
+        return self.per_head[image * self.heads + head]
+
+    def to_dict(self):
+        d = {f.name: getattr(self, f.name) for f in fields(self) if f.name not in ("per_head", "kept")}
+        d["worst_head"] = list(self.worst_head)
+        d["per_head"] = [[r[name].item() for name in self.per_head.dtype.names] for r in self.per_head]
+        return d
+
+    @staticmethod
+    def from_dict(d):
+        from . import ops
+        rec = np.zeros(len(d["per_head"]), dtype=ops.ATTENTION_HEALTH_DTYPE)
+        for i, values in enumerate(d["per_head"]):
+            rec[i] = tuple(values)
+        return AttentionRow(**{**d, "worst_head": tuple(d["worst_head"]), "per_head": rec})
+
+    @staticmethod
+    def head_lines(rec, heads, order):
+        lines = [f"{'img':>4} {'head':>4} {'q absmax':>10} {'k absmax':>10} {'v absmax':>10} {'in bad':>7} {'out bad':>8} {'e_max':>10} "
+                 f"{'e_min':>10} {'rise_max':>9} {'over':>6} {'ref absmax':>10} {'err_max':>10} {'err_row':>7}"]
+        for i in order:
+            r = rec[i]
+            tail = (f"{r['e_max']:>10.4g} {r['e_min']:>10.4g} {r['rise_max']:>9.4g} {r['rows_rise_over']:>6} "
+                    f"{_bits_f32(r['ref_absmax_bits']):>10.4g} {r['err_max']:>10.4g} {r['err_row']:>7}") if r["in_nonfinite"] == 0 \
+                else "operands non-finite"
+            lines.append(f"{i // heads:>4} {i % heads:>4} {_bits_f32(r['q_absmax_bits']):>10.4g} {_bits_f32(r['k_absmax_bits']):>10.4g} "
+                         f"{_bits_f32(r['v_absmax_bits']):>10.4g} {r['in_nonfinite']:>7} {r['out_nonfinite']:>8} {tail}")
+        return "\n".join(lines)
+
+    def worst_heads(self, k=4):
+        """The k heads with the most non-finite results (then by error), printed in full."""
+        err = np.where(np.isnan(self.per_head["err_max"]), np.inf, self.per_head["err_max"])
+        order = sorted(range(len(self.per_head)), key=lambda i: (-int(self.per_head["out_nonfinite"][i]), -err[i], i))[:k]
+        return self.head_lines(self.per_head, self.heads, order)
+
+
 def _merge(records):
     """One row over several tensors (the sampler's x and pred_x0): the max and the sums."""
     out = dict(records[0])
@@ -139,8 +308,15 @@ class Row:
 
 
 class Report:
-    def __init__(self, rows, near=0.5):
-        self.rows, self.near = list(rows), near
+    def __init__(self, rows, near=0.5, attention=()):
+        self.rows, self.near, self.attention = list(rows), near, list(attention)
+
+    def attention_for(self, seq):
+        """The AttentionRow of the launch whose own row is rows[seq] (probe(attention=True)), or None."""
+        for a in self.attention:
+            if a.seq == seq:
+                return a
+        return None
 
     def first_nonfinite(self):
         for r in self.rows:
@@ -158,12 +334,28 @@ class Report:
             d = {f.name: getattr(r, f.name) for f in fields(r) if f.name != "kept"}
             d["shape"] = list(r.shape)
             rows.append(d)
-        return json.dumps({"near": self.near, "rows": rows})
+        d = {"near": self.near, "rows": rows}
+        if self.attention:
+            d["attention"] = [a.to_dict() for a in self.attention]
+        return json.dumps(d)
 
     @staticmethod
     def from_json(text):
         d = json.loads(text)
-        return Report([Row(**{**r, "shape": tuple(r["shape"])}) for r in d["rows"]], d["near"])
+        return Report([Row(**{**r, "shape": tuple(r["shape"])}) for r in d["rows"]], d["near"],
+                      [AttentionRow.from_dict(a) for a in d.get("attention", [])])
+
+    @staticmethod
+    def attention_table(rows):
+        lines = [f"{'seq':>5} {'n x h':>7} {'tq x tk':>11} {'dh':>4} {'dtype':>5} {'in bad':>7} {'out bad':>8} {'e_max':>10} {'e_min':>10} "
+                 f"{'rise_max':>9} {'over':>6} {'ref absmax':>10} {'err_max':>10} {'at (img, head, row)':>19}  module"]
+        for a in rows:
+            at = f"({a.worst_head[0]}, {a.worst_head[1]}, {a.err_row})"
+            tail = (f"{a.e_max:>10.4g} {a.e_min:>10.4g} {a.rise_max:>9.4g} {a.rows_rise_over:>6} {a.ref_absmax:>10.4g} {a.err_max:>10.4g} "
+                    f"{at:>19}") if a.in_nonfinite == 0 else f"{'operands non-finite':>79}"
+            lines.append(f"{a.seq:>5} {f'{a.images}x{a.heads}':>7} {f'{a.tq}x{a.tk}':>11} {a.dh:>4} {a.dtype:>5} {a.in_nonfinite:>7} "
+                         f"{a.out_nonfinite:>8} {tail}  {a.module}")
+        return "\n".join(lines)
 
     @staticmethod
     def table(rows, extra=None):
@@ -188,7 +380,10 @@ class Report:
             "first non-finite: " + (f"#{bad.seq} {bad.kind} {bad.module} (inf {bad.inf}, nan {bad.nan})" if bad else "none")])
 
     def __str__(self):
-        return self.table(self.rows) + "\n" + self.summary()
+        text = self.table(self.rows) + "\n" + self.summary()
+        if self.attention:
+            text += "\n" + self.attention_table(self.attention)
+        return text
 
 
 # --------------------------------------------------------------------------------------
@@ -214,8 +409,10 @@ class _Scope:
 class Probe:
     """The sink behind `ops._HEALTH` (see the module's documentation); made by `probe()`."""
 
-    def __init__(self, near=0.5, keep=False):
-        self.near, self.keep = float(near), bool(keep)
+    def __init__(self, near=0.5, keep=False, attention=False):
+        self.near, self.keep, self.attention = float(near), bool(keep), bool(attention)
+        self._att_pending = []    # (seq, module, (images, heads, tq, tk, dh), dtype, q_log2_scaled, rise limit, buffer index, first slot, kept)
+        self._att_buffers, self._att_used = [], 0
         self._pending = []        # (module, kind, shapes, dtypes, buffer index, first slot, count, kept)
         self._buffers, self._used = [], _SLOTS
         self._stack, self._names = [], weakref.WeakKeyDictionary()  # module -> path (weak: a freed module's address may be reused)
@@ -278,6 +475,27 @@ class Probe:
                               len(self._buffers) - 1, self._used, len(ts), kept))
         self._used += len(ts)
 
+    def measure_attention(self, q, k, v, out, heads, scale, v_rows, q_log2_scaled):
+        """ops.attention calls this right behind `measure("attention", out)` when `attention` is set: one mobi_attention_health
+        launch on the current stream into the probe's own record buffer, tied to the row just made."""
+        from . import ops
+        if not self._pending or out.numel() == 0:
+            return
+        count = q.shape[0] * heads
+        if not self._att_buffers or self._att_used + count > self._att_buffers[-1].shape[0]:
+            self._att_buffers.append(torch.empty((max(_SLOTS, count), ops.ATTENTION_HEALTH_DTYPE.itemsize // 4), dtype=torch.int32,
+                                                 device=q.device))
+            self._att_used = 0
+        name = DTYPE_NAMES[q.dtype]
+        ops.attention_health(q, k, v, out, heads, scale, v_rows, q_log2_scaled, RISE_LIMIT[name],
+                             records=self._att_buffers[-1][self._att_used:])
+        kept = dict(q=q.clone(), k=k.clone(), v=v.clone(), out=out.clone(), heads=heads, scale=scale, v_rows=v_rows,
+                    q_log2_scaled=q_log2_scaled) if self.keep else None
+        c = v.shape[2] if v_rows else v.shape[1]
+        self._att_pending.append((len(self._pending) - 1, self._pending[-1][0], (q.shape[0], heads, q.shape[1], k.shape[1], c // heads),
+                                  name, bool(q_log2_scaled), RISE_LIMIT[name], len(self._att_buffers) - 1, self._att_used, kept))
+        self._att_used += count
+
     # -- context
     def __enter__(self):
         from . import ops
@@ -314,13 +532,20 @@ class Probe:
             for seq, (module, kind, shapes, dtypes, bi, slot, count, kept) in enumerate(self._pending):
                 lo = int(starts[bi]) + slot
                 rows.append(Row.from_record(seq, module, kind, shapes[0], dtypes[0], _merge(allrec[lo:lo + count]), kept=kept))
-        rep = Report(rows, self.near)
+        att = []
+        if self._att_pending:
+            host = [ops.read_attention_health(b if i + 1 < len(self._att_buffers) else b[:self._att_used])
+                    for i, b in enumerate(self._att_buffers)]
+            for seq, module, shape, dtype, log2, limit, bi, slot, kept in self._att_pending:
+                att.append(AttentionRow.from_records(seq, module, shape, dtype, log2, limit, host[bi][slot:slot + shape[0] * shape[1]].copy(),
+                                                     kept))
+        rep = Report(rows, self.near, att)
         self._report = (len(self._pending), rep)
         return rep
 
 
-def probe(near=0.5, keep=False):
-    return Probe(near, keep)
+def probe(near=0.5, keep=False, attention=False):
+    return Probe(near, keep, attention)
 
 
 # --------------------------------------------------------------------------------------
@@ -442,6 +667,7 @@ def build_parser():
     ap.add_argument("--top", type=int, default=20, help="rows of the worst-headroom table")
     ap.add_argument("--json", type=str, default="", help="write the reports here")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--attention", action="store_true", help="probe inside every attention launch as well (mobi_attention_health)")
     ap.add_argument("overrides", nargs=argparse.REMAINDER, help="dot-list overrides of the config")
     return ap
 
@@ -472,7 +698,7 @@ def synthetic_batch(objects, size, seed=0):
     return move(b)
 
 
-def probed_model_run(model, dtype, *, objects=2, steps=2, scale=5.0, plms=False, seed=0, near=0.5, keep=False):
+def probed_model_run(model, dtype, *, objects=2, steps=2, scale=5.0, plms=False, seed=0, near=0.5, keep=False, attention=False):
     """One synthetic batch through `get_input` -> `steps` sampler steps -> `decode_sample` + `log_data` of a LatentDiffusion model
     under a probe -> the Report: the conditioning producer, both autoencoders in encode and decode, the UNet and the sampler."""
     import mobi_amd
@@ -482,7 +708,7 @@ def probed_model_run(model, dtype, *, objects=2, steps=2, scale=5.0, plms=False,
     batch = synthetic_batch(objects, model.image_size * 8, seed)
     shape = [model.channels, model.image_size, model.image_size]
     sampler = (PLMSSampler if plms else DDIMSampler)(model)
-    with torch.no_grad(), model.ema_scope(), probe(near=near, keep=keep) as hp:
+    with torch.no_grad(), model.ema_scope(), probe(near=near, keep=keep, attention=attention) as hp:
         data = model.get_input(batch, model.first_stage_key, force_c_encode=True, return_vae_rec=True)
         n = data["z"].shape[0]
         x_T = torch.randn([n, *shape], generator=torch.Generator().manual_seed(int(seed) + 1)).cuda()
@@ -508,8 +734,8 @@ class _FirstBatch:
     """Opens a probe at a model's first `get_input` and closes it when its first `log_data` returns: one test-bench batch
     (get_input, sampling, decode_sample, log_data) runs under the probe, eagerly, once; later batches run as always."""
 
-    def __init__(self, model, near=0.5):
-        self.model, self.probe, self.report = model, Probe(near), None
+    def __init__(self, model, near=0.5, attention=False):
+        self.model, self.probe, self.report = model, Probe(near, attention=attention), None
         self._state = 0                                            # 0 not started, 1 probing, 2 done
         get_input, log_data = model.get_input, model.log_data
 
@@ -545,7 +771,9 @@ def test_bench_main(argv=None):
     import os
     from . import set_engine_dtype, test_bench as tb
     from .ldm.util import load_config
-    opt = tb.build_parser().parse_args(argv)
+    argv = sys.argv[2:] if argv is None else list(argv)
+    attention = "--attention" in argv                              # the probe's own flag; the rest is the test bench's
+    opt = tb.build_parser().parse_args([a for a in argv if a != "--attention"])
     if opt.plms and opt.dpm:
         raise SystemExit("--plms and --dpm exclude each other")
     set_engine_dtype({"fp16": torch.float16, "bf16": torch.bfloat16}[opt.dtype])
@@ -554,7 +782,7 @@ def test_bench_main(argv=None):
     load_model, first = tb.load_model, []
 
     def load_and_watch(cfg, ckpt):
-        first.append(_FirstBatch(load_model(cfg, ckpt)))
+        first.append(_FirstBatch(load_model(cfg, ckpt), attention=attention))
         return first[0].model
 
     tb.load_model = load_and_watch                                 # the loop loads its model through this name, after the split is built
@@ -572,8 +800,23 @@ def test_bench_main(argv=None):
     for name, laps in spent.items():                               # (--timing, as the test-bench command prints it)
         print(f"{name}: median {1e3 * float(np.median(laps)):.1f} ms over {len(laps)} batches")
     print(rep.summary())
+    if attention:
+        print(attention_section(rep))
     print(f"The result tree is in {opt.outdir}")
     return 3 if rep.first_nonfinite() is not None else 0
+
+
+def attention_section(rep):
+    """What `--attention` adds to the output: the attention table and, for the first launch whose production result holds inf or
+    nan, its worst heads in full."""
+    lines = [f"attention probe: {len(rep.attention)} launches", Report.attention_table(rep.attention)]
+    bad = next((a for a in rep.attention if a.out_nonfinite > 0), None)
+    if bad is not None:
+        lines += [f"first attention launch with a non-finite result: #{bad.seq} {bad.module} ({bad.images} x {bad.heads} heads, "
+                  f"{bad.tq} x {bad.tk}, dh {bad.dh}, {bad.dtype}, rise limit {bad.rise_limit:g}): its worst heads", bad.worst_heads()]
+    else:
+        lines.append("no attention launch stored inf or nan")
+    return "\n".join(lines)
 
 
 def main(argv=None):
@@ -615,7 +858,7 @@ def main(argv=None):
         out[f"audit_{name}"] = json.loads(audit.to_json())
         bad |= any(r.nonfinite or r.overflow for r in audit.rows)
     reports = {name: probed_model_run(model, torch_dt[name], objects=opt.objects, steps=opt.steps, scale=opt.scale, plms=opt.plms,
-                                      seed=opt.seed) for name in names}
+                                      seed=opt.seed, attention=opt.attention) for name in names}
     first = reports[names[0]]
     extra = None
     if len(names) == 2:
@@ -634,6 +877,8 @@ def main(argv=None):
     for name in names:
         print(f"-- {name}")
         print(reports[name].summary())
+        if opt.attention:
+            print(attention_section(reports[name]))
         out[f"run_{name}"] = json.loads(reports[name].to_json())
         bad |= reports[name].first_nonfinite() is not None
     if opt.json:

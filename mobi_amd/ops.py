@@ -1284,7 +1284,66 @@ def attention(q, k, v, heads, scale, v_rows=False, q_log2_scaled=False):
         _lib.check(lib.mobi_attention(C.byref(p), _stream()), "mobi_attention")
     if _HEALTH is not None:
         _HEALTH.measure("attention", out)
+        if getattr(_HEALTH, "attention", False):
+            _HEALTH.measure_attention(q, k, v, out, heads, scale, v_rows, q_log2_scaled)
     return out
+
+
+ATTENTION_RISE_LIMIT = {torch.float16: 20.0, torch.bfloat16: 120.0}     # octaves (health.RISE_LIMIT states where they come from)
+
+
+def _attention_params(q, k, v, out, heads, scale, v_rows, q_log2_scaled):
+    """The mobi_attention_params of `attention(q, k, v, ...)` whose result is `out`."""
+    n, tq, tk = q.shape[0], q.shape[1], k.shape[1]
+    c = v.shape[2] if v_rows else v.shape[1]
+    p = _lib.AttentionParams()
+    p.q, p.q_img_stride, p.q_row_stride = _ptr(q), q.stride(0), q.stride(1)
+    p.k, p.k_img_stride, p.k_row_stride = _ptr(k), k.stride(0), k.stride(1)
+    p.vt, p.vt_img_stride, p.vt_row_stride = _ptr(v), v.stride(0), v.stride(1)
+    p.v_layout = 1 if v_rows else 0
+    p.q_log2_scaled = 1 if q_log2_scaled else 0
+    p.out, p.out_img_stride, p.out_row_stride = _ptr(out), out.stride(0), out.stride(1)
+    for t_ in (q, k, v, out):
+        assert t_.shape[2] == 1 or t_.stride(2) == 1
+    assert out.shape == (n, tq, c) and out.dtype == q.dtype == k.dtype == v.dtype
+    p.images, p.heads, p.dh, p.tq, p.tk, p.scale, p.dtype = n, heads, c // heads, tq, tk, scale, _dt(q.dtype)
+    return p
+
+
+def attention_health(q, k, v, out, heads, scale, v_rows=False, q_log2_scaled=False, rise_limit=None, records=None):
+    """The attention probe, `mobi_attention_health`, on the current stream: q, k, v, heads, scale, v_rows, q_log2_scaled as
+    `attention` took them, `out` what it returned.  -> the device records, int32 [N * heads, 12] (`_lib.AttentionHealthRecord`,
+    image-major).  rise_limit: the rise in octaves from which a row counts in rows_rise_over (ATTENTION_RISE_LIMIT of the
+    storage type by default); records: an int32 [>= N * heads, 12] dense device buffer to write into (the probe's) instead
+    of a fresh tensor.  Writes nothing else.  `read_attention_health` brings the records to the host."""
+    lib = _lib.load()
+    p = _attention_params(q, k, v, out, heads, scale, v_rows, q_log2_scaled)
+    count, words = q.shape[0] * heads, C.sizeof(_lib.AttentionHealthRecord) // 4
+    if rise_limit is None:
+        rise_limit = ATTENTION_RISE_LIMIT[q.dtype]
+    if records is None:
+        records = torch.empty((count, words), dtype=torch.int32, device=q.device)
+    assert records.dtype == torch.int32 and records.is_contiguous() and records.shape[0] >= count and records.shape[1] == words
+    _lib.check(lib.mobi_attention_health(C.byref(p), float(rise_limit), _ptr(records), _stream()), "mobi_attention_health")
+    return records[:count]
+
+
+def read_attention_health(rec):
+    """The device records of `attention_health` -> a numpy structured array, one element per (image, head) in image-major
+    order, fields as `_lib.AttentionHealthRecord`.  One blocking copy of 48 bytes per head."""
+    import numpy as np
+    words = C.sizeof(_lib.AttentionHealthRecord) // 4
+    host = np.ascontiguousarray(rec.cpu().numpy().reshape(-1, words))
+    return host.view(ATTENTION_HEALTH_DTYPE).reshape(-1).copy()
+
+
+def _attention_health_dtype():
+    import numpy as np
+    kinds = {C.c_uint32: "<u4", C.c_int32: "<i4", C.c_float: "<f4"}
+    return np.dtype([(name, kinds[ct]) for name, ct in _lib.AttentionHealthRecord._fields_])
+
+
+ATTENTION_HEALTH_DTYPE = _attention_health_dtype()
 
 
 def ctx_attention(q, k, v, heads, scale):

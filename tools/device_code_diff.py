@@ -7,7 +7,8 @@ Each file is cross-compiled device-only on both sides with mobi_amd/build.py's f
 code object is disassembled, and one line per file reports the kernel count and a sha256 of the disassembly of either side.
 --ignore-names replaces every function's mangled symbol by its ordinal first and drops the addresses, keeping the encodings
 (for a change of template parameters that must leave the instructions alone: shorter names move the text section).
-Object files are not compared: their __hip_cuid_* symbol hashes the translation unit.  Both directories must sit in a tree where "../../include/mobi_engine.h" resolves.  Exit status 1 if any file differs."""
+Object files are not compared: their __hip_cuid_* symbol hashes the translation unit.  Both directories must sit in a tree where "../../include/mobi_engine.h" resolves.  A file that only NEW_CSRC has is reported as new (its kernel count and sha256) and is no
+difference.  Exit status 1 if any file that both sides have differs."""
 import argparse
 import hashlib
 import os
@@ -56,6 +57,12 @@ def main():
     files = a.files or sorted(f for f in os.listdir(a.new_csrc) if f.endswith(".hip"))
     differ = 0
     for name in files:
+        if not os.path.exists(os.path.join(a.old_csrc, name)):
+            with tempfile.TemporaryDirectory() as tmp:
+                kn, new = disassemble(a.new_csrc, name, tmp, a.ignore_names)
+            print(f"{name:20s} kernels   - | {kn:3d}   disassembly lines       - | {new.count(chr(10)):7d}   "
+                  f"sha256 {'-':16s} | {hashlib.sha256(new.encode()).hexdigest()[:16]}   new file")
+            continue
         with tempfile.TemporaryDirectory() as tmp:
             (ko, old), (kn, new) = (disassemble(d, name, tmp, a.ignore_names) for d in (a.old_csrc, a.new_csrc))
         same = old == new and ko == kn
