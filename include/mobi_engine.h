@@ -61,7 +61,8 @@ extern "C" {
  *      mobi_lidar_overlay_workspace_bytes (mobi_lidar_overlay_params 33, mobi_lidar_overlay_picture 34); likewise the numeric
  *      health launch, mobi_tensor_health (mobi_health_tensor 35, mobi_health_record 36); likewise the camera pictures of the
  *      test bench's copy-paste baseline, mobi_camera_copy_paste (mobi_camera_export_params 31 as it is, no new struct); likewise
- *      the attention probe, mobi_attention_health (mobi_attention_health_record 37; mobi_attention_params 3 as it is) */
+ *      the attention probe, mobi_attention_health (mobi_attention_health_record 37; mobi_attention_params 3 as it is); likewise
+ *      the launch-plan queries of the normalisations, mobi_groupnorm_kernel_variant and mobi_layernorm_kernel_variant (no struct) */
 #define MOBI_ABI_VERSION 6
 
 enum { MOBI_OK = 0, MOBI_ERR_ARG = -1, MOBI_ERR_UNSUPPORTED = -2, MOBI_ERR_LAUNCH = -3, MOBI_ERR_ALIGN = -4 };
@@ -245,6 +246,27 @@ size_t mobi_groupnorm_workspace_bytes(int32_t batch, int32_t hw);
  * producer with mobi_igemm_finish first. */
 int mobi_groupnorm_takes_split(int32_t c0, int32_t c1, int32_t batch, int32_t hw);
 int mobi_groupnorm(const mobi_groupnorm_params* p, void* stream);
+/* What mobi_groupnorm would launch for these parameters under the current MOBI_GN_* environment (no launch, no device needed;
+ * measurement / tests).  Negative = the error mobi_groupnorm would return.  Otherwise the plan, packed:
+ *   bits 0 .. 3    the form (MOBI_GN_FORM_*)
+ *   bits 4 .. 9    gb: adjacent groups a workgroup owns (register forms); pixel chunks per image (chunked form); else 0
+ *   bits 10 .. 13  pw: channels per piece, 8 or 4 (register and chunked forms; else 0)
+ *   bits 14 .. 19  items: pieces a thread holds (register and chunked forms; else 0)
+ *   bits 20 .. 30  threads per workgroup, 256 or 1024 (register and chunked forms; else 0)
+ * mobi_groupnorm launches from the same plan: the two cannot disagree. */
+enum { MOBI_GN_FORM_TWO_LAUNCH = 0,          /* statistics, then apply */
+       MOBI_GN_FORM_TWO_LAUNCH_PRECISE = 1,  /* the same for src_f32 / out_mode 1 .. 3 */
+       MOBI_GN_FORM_LDS = 2,                 /* one launch, the group's slab in LDS */
+       MOBI_GN_FORM_REGS = 3,                /* one launch, the slab in registers */
+       MOBI_GN_FORM_REGS_SLABS = 4,          /* the same, src0 summed from split-K slabs (src0_split) */
+       MOBI_GN_FORM_CHUNKS = 5 };            /* one launch, pixel chunks meeting through memory (needs `sync`) */
+#define MOBI_GN_PLAN(form, gb, pw, items, threads) ((form) | (gb) << 4 | (pw) << 10 | (items) << 14 | (threads) << 20)
+#define MOBI_GN_PLAN_FORM(plan) ((plan) & 15)
+#define MOBI_GN_PLAN_GB(plan) ((plan) >> 4 & 63)
+#define MOBI_GN_PLAN_PW(plan) ((plan) >> 10 & 15)
+#define MOBI_GN_PLAN_ITEMS(plan) ((plan) >> 14 & 63)
+#define MOBI_GN_PLAN_THREADS(plan) ((plan) >> 20 & 2047)
+int mobi_groupnorm_kernel_variant(const mobi_groupnorm_params* p);
 
 /* LayerNorm over the channel axis of token rows (nn.LayerNorm, eps 1e-5,
  * attention.py:213-223,232-256).  `images` blocks of `rows_per_image` rows; the
@@ -258,6 +280,9 @@ typedef struct mobi_layernorm_params {
   int32_t dtype;
 } mobi_layernorm_params;
 int mobi_layernorm(const mobi_layernorm_params* p, void* stream);
+/* The kernel body mobi_layernorm would launch (no launch, no device needed): MAXV | LPR << 8 -- LPR lanes share a row and each
+ * holds up to MAXV 8-channel pieces of it.  Negative = the error mobi_layernorm would return. */
+int mobi_layernorm_kernel_variant(const mobi_layernorm_params* p);
 
 /* ---------------------------------------------------------------------------
  * Fused attention  out = softmax(q k^T * scale) v, one launch for all images

@@ -290,7 +290,9 @@ SYMBOLS = {
     "mobi_groupnorm_takes_split": (C.c_int, [i32, i32, i32, i32]),
     "mobi_groupnorm_workspace_bytes": (C.c_size_t, [i32, i32]),
     "mobi_groupnorm": (C.c_int, [C.POINTER(GroupNormParams), vp]),
+    "mobi_groupnorm_kernel_variant": (C.c_int, [C.POINTER(GroupNormParams)]),
     "mobi_layernorm": (C.c_int, [C.POINTER(LayerNormParams), vp]),
+    "mobi_layernorm_kernel_variant": (C.c_int, [C.POINTER(LayerNormParams)]),
     "mobi_attention": (C.c_int, [C.POINTER(AttentionParams), vp]),
     "mobi_ctx_attention": (C.c_int, [C.POINTER(CtxAttentionParams), vp]),
     "mobi_two_key_adapter": (C.c_int, [C.POINTER(TwoKeyAdapterParams), vp]),

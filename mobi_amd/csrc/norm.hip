@@ -10,7 +10,8 @@
 //          a fixed 8-channel column, folds per-channel sums into the 32 groups through LDS in
 //          a fixed order (deterministic) and writes one (sum, sumsq) pair per group -- sums of x - k, with the
 //          group's shift k = its first element (gn_shift): fp32 sums of x and x^2 themselves lose the variance of a
-//          group whose mean is large against its spread, and a constant group's (x - k) sums are exactly zero;
+//          group whose mean is large against its spread, and a constant group's (x - k) sums are exactly zero (the precise
+//          forms, whose fp32 outputs show the statistics' own rounding, take a k near the group's mean: gn_shift_x);
 //          apply: every block first combines its image's chunk partials in fp64 (mean = k + S / n,
 //          var = Q / n - (S / n)^2), then streams y = (x - mean[c]) * a[c] + beta[c], optional SiLU.
 //          2 B read (stats) + 2 B read + 2 B written (apply) per element; fully coalesced 16-byte accesses;
@@ -52,11 +53,35 @@ __device__ __forceinline__ float gn_shift(const GnArgs& a, int img, int g) {
                    : (float)reinterpret_cast<const T*>(a.src0)[(long long)img * a.hw * a.c0 + c];
 }
 
-// chunk partials (sums of x - k, k = gn_shift) of the image -> per-group shift-free mean, rstd in s_mean / s_rstd; all 256
+// The shift of the precise forms (fp32 source, out_mode 1 .. 3): the group's first element plus the mean distance to it of the
+// group's channels at four pixels spread over the image, summed in a fixed order (every block of the image computes the same
+// value; a constant group gives its constant exactly).  One element can lie three standard deviations from the group's mean,
+// and the fp32 partial sums of (x - k)^2 then carry 1 + (k - mean)^2 / var times their rounding into the variance: rstd of an
+// fp32 output was off by 1.5e-6 in the worst of 64 groups, ten times what two fp32 passes give (tests/test_gpu_norm_groups.py).
+// One thread per group fills a table in LDS: 4 C / 32 loads each.
+template <typename T>
+__device__ __forceinline__ float gn_shift_x(const GnArgs& a, int img, int g) {
+  const int cpg = a.C / 32;
+  auto at = [&](long long p, int c) -> float {
+    if (a.src_f32) return reinterpret_cast<const float*>(a.src0)[p * a.C + c];
+    return c >= a.c0 ? (float)reinterpret_cast<const T*>(a.src1)[p * a.c1 + (c - a.c0)]
+                     : (float)reinterpret_cast<const T*>(a.src0)[p * a.c0 + c];
+  };
+  const long long p0 = (long long)img * a.hw;
+  const float x0 = at(p0, g * cpg);
+  float s = 0.f;
+  for (int q = 0; q < 4; ++q) {
+    const long long p = p0 + (long long)q * a.hw / 4;
+    for (int j = 0; j < cpg; ++j) s += at(p, g * cpg + j) - x0;
+  }
+  return x0 + s / (float)(4 * cpg);
+}
+
+// chunk partials (sums of x - k, k = gn_shift; X: gn_shift_x) of the image -> per-group shift-free mean, rstd in s_mean / s_rstd; all 256
 // threads take part: thread (sub = tid >> 5, g = tid & 31) sums chunks sub, sub + 8, ... of group g in fp64 (independent loads,
 // one round trip), LDS folds the eight partial sums in a fixed order.  (32 threads walking all chunks serially cost ~8 us of
 // exposed latency per block.)  s_mean holds the fp32 mean, s_dev the fp32 S / n (the mean less k: what the fp32 outputs use).
-template <typename T>
+template <typename T, bool X = false>
 __device__ __forceinline__ void gn_combine(const GnArgs& a, int img, double (*s_ps)[32], double (*s_pq)[32], float* s_mean,
                                            float* s_dev, float* s_shift, float* s_rstd) {
   const int tid = threadIdx.x;
@@ -73,7 +98,7 @@ __device__ __forceinline__ void gn_combine(const GnArgs& a, int img, double (*s_
 #pragma unroll
     for (int k = 0; k < 8; ++k) { s += s_ps[k][tid]; q += s_pq[k][tid]; }
     const double n = (double)a.hw * (double)(a.C / 32);
-    const double k = (double)gn_shift<T>(a, img, tid);
+    const double k = (double)(X ? gn_shift_x<T>(a, img, tid) : gn_shift<T>(a, img, tid));
     const double d = s / n;
     double var = q / n - d * d;
     var = var < 0.0 ? 0.0 : var;
@@ -84,13 +109,19 @@ __device__ __forceinline__ void gn_combine(const GnArgs& a, int img, double (*s_
   __syncthreads();
 }
 
-template <typename T>
+// X: the statistics launch of the precise forms with a 16-bit source -- the shift of gn_shift_x, the block's fold in fp64
+template <typename T, bool X = false>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const GnArgs a) {
   // LDS: per (row slot, channel) partial sums; rows*C <= 2048+ or C <= 2560 when one slot
   __shared__ float s_sum[2560 + 512];
   __shared__ float s_sq[2560 + 512];
+  __shared__ float s_k[32];
   const int tid = threadIdx.x;
   const int img = blockIdx.y, chunk = blockIdx.x;
+  if (X) {
+    if (tid < 32) s_k[tid] = gn_shift_x<T>(a, img, tid);
+    __syncthreads();
+  }
   const int V = a.C >> 3;                              // 8-channel columns per pixel
   const int rows = V <= 256 ? 256 / V : 1;             // pixels swept per iteration
   const int per = (a.hw + a.chunks - 1) / a.chunks;
@@ -114,7 +145,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const GnArgs a) {
       const int cpg = a.C / 32;
       float k[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) k[j] = gn_shift<T>(a, img, (c + j) / cpg);
+      for (int j = 0; j < 8; ++j) k[j] = X ? s_k[(c + j) / cpg] : gn_shift<T>(a, img, (c + j) / cpg);
       // four independent 16-byte loads in flight per thread (the loop is latency-bound otherwise: one load per
       // thread and iteration keeps only ~32 KB per CU in flight)
       int p = p_begin + slot;
@@ -146,14 +177,24 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const GnArgs a) {
   __syncthreads();
   if (tid < 32) {
     const int cpg = a.C / 32;
-    float gs = 0.f, gq = 0.f;
-    for (int r = 0; r < rows; ++r)
-      for (int j = 0; j < cpg; ++j) {
-        gs += s_sum[r * a.C + tid * cpg + j];
-        gq += s_sq[r * a.C + tid * cpg + j];
-      }
     float* w = a.ws + ((long long)(img * a.chunks + chunk) * 32 + tid) * 2;
-    w[0] = gs; w[1] = gq;
+    if (X) {
+      double gs = 0.0, gq = 0.0;
+      for (int r = 0; r < rows; ++r)
+        for (int j = 0; j < cpg; ++j) {
+          gs += (double)s_sum[r * a.C + tid * cpg + j];
+          gq += (double)s_sq[r * a.C + tid * cpg + j];
+        }
+      w[0] = (float)gs; w[1] = (float)gq;
+    } else {
+      float gs = 0.f, gq = 0.f;
+      for (int r = 0; r < rows; ++r)
+        for (int j = 0; j < cpg; ++j) {
+          gs += s_sum[r * a.C + tid * cpg + j];
+          gq += s_sq[r * a.C + tid * cpg + j];
+        }
+      w[0] = gs; w[1] = gq;
+    }
   }
 }
 
@@ -228,15 +269,20 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const GnArgs a) {
 
 // ---------------------------------------------------------------------------------------
 // The two-launch form for fp32 sources and for the "precise" outputs (GnArgs.src_f32 / out_mode): the lidar decoder's tail of
-// the fp16 parity configuration (ldm/modules/diffusionmodules/model.py).  Same statistics arithmetic as gn_stats_kernel /
-// gn_apply_kernel (per-chunk fp32 partial sums of x - k, fp64 fold); the apply keeps the shift apart,
-// y = ((x - k) - S / n) * sc + beta: x - k is exact, so an fp32 output does not carry the rounding of an fp32 mean (|mean| 2^-24
-// against the spread).  Not tuned -- a handful of launches per decode.
+// the fp16 parity configuration (ldm/modules/diffusionmodules/model.py).  The statistics arithmetic of gn_stats_kernel /
+// gn_apply_kernel (per-chunk fp32 partial sums of x - k, fp64 fold) with the shift of gn_shift_x -- close to the group's mean,
+// so the partial sums' rounding reaches the variance unamplified -- and the block's own fold in fp64 too; the apply keeps the
+// shift apart, y = ((x - k) - S / n) * sc + beta: x - k rounds relative to the spread, so an fp32 output does not carry the
+// rounding of an fp32 mean (|mean| 2^-24 against the spread).  Not tuned -- a handful of launches per decode.
 __global__ __launch_bounds__(256) void gn_stats_f32_kernel(const GnArgs a) {
+  constexpr bool X = true;                               // a precise form by definition: gn_shift_x, fp64 fold
   __shared__ float s_sum[2560 + 512];
   __shared__ float s_sq[2560 + 512];
+  __shared__ float s_k[32];
   const int tid = threadIdx.x;
   const int img = blockIdx.y, chunk = blockIdx.x;
+  if (tid < 32) s_k[tid] = gn_shift_x<float>(a, img, tid);
+  __syncthreads();
   const int V = a.C >> 3;
   const int rows = V <= 256 ? 256 / V : 1;
   const int per = (a.hw + a.chunks - 1) / a.chunks;
@@ -255,7 +301,7 @@ __global__ __launch_bounds__(256) void gn_stats_f32_kernel(const GnArgs a) {
       const int cpg = a.C / 32;
       float k[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) k[j] = gn_shift<float>(a, img, (c + j) / cpg);
+      for (int j = 0; j < 8; ++j) k[j] = s_k[(c + j) / cpg];
       for (int p = p_begin + slot; p < p_end; p += rows) {
         float f[8];
         ld8f(s0 + (long long)p * a.C + c, f);
@@ -272,14 +318,24 @@ __global__ __launch_bounds__(256) void gn_stats_f32_kernel(const GnArgs a) {
   __syncthreads();
   if (tid < 32) {
     const int cpg = a.C / 32;
-    float gs = 0.f, gq = 0.f;
-    for (int r = 0; r < rows; ++r)
-      for (int j = 0; j < cpg; ++j) {
-        gs += s_sum[r * a.C + tid * cpg + j];
-        gq += s_sq[r * a.C + tid * cpg + j];
-      }
     float* w = a.ws + ((long long)(img * a.chunks + chunk) * 32 + tid) * 2;
-    w[0] = gs; w[1] = gq;
+    if (X) {
+      double gs = 0.0, gq = 0.0;
+      for (int r = 0; r < rows; ++r)
+        for (int j = 0; j < cpg; ++j) {
+          gs += (double)s_sum[r * a.C + tid * cpg + j];
+          gq += (double)s_sq[r * a.C + tid * cpg + j];
+        }
+      w[0] = (float)gs; w[1] = (float)gq;
+    } else {
+      float gs = 0.f, gq = 0.f;
+      for (int r = 0; r < rows; ++r)
+        for (int j = 0; j < cpg; ++j) {
+          gs += s_sum[r * a.C + tid * cpg + j];
+          gq += s_sq[r * a.C + tid * cpg + j];
+        }
+      w[0] = gs; w[1] = gq;
+    }
   }
 }
 
@@ -290,7 +346,7 @@ __global__ __launch_bounds__(256) void gn_apply_x_kernel(const GnArgs a) {
   __shared__ double s_ps[8][32], s_pq[8][32];
   const int tid = threadIdx.x;
   const int img = blockIdx.y;
-  gn_combine<T>(a, img, s_ps, s_pq, s_mean, s_dev, s_shift, s_rstd);
+  gn_combine<T, true>(a, img, s_ps, s_pq, s_mean, s_dev, s_shift, s_rstd);
   const int cpg = a.C / 32;
   for (int c = tid; c < a.C; c += 256) {
     const int g = c / cpg;
@@ -696,22 +752,33 @@ static bool gn_regs_geometry(int C, int hw, int batch, GnRegsGeom* geo, int* thr
 
 // src0 from split-K slabs: the register form with at most 8 pieces per thread (split launches have few pixels: the 32 x 32
 // level's 320-channel tensors are the largest -- 8 pieces of 8 bytes), both sources split at a piece boundary
+static bool gn_regs_split_geometry(int c0, int c1, int hw, int batch, GnRegsGeom* geo, int* th, int* it, int* pw) {
+  if (!gn_regs_geometry(c0 + c1, hw, batch, geo, th, it, pw)) return false;
+  // 8-byte pieces (C = 320: the 32 x 32 level of mobi_nusc_256) only on request: in the step graph 21.0 us against 9.8 + 6.5 for
+  // GroupNorm + reduce launch on [8, 1024, 320] x 4 slabs (tools/defer_breakdown.sh) -- 128 blocks read 42 MB of slabs
+  if (*pw == 4 && tuning().gn_split_pw4 != 1) return false;
+  return *it <= 8 && c0 % *pw == 0;
+}
+
 static bool gn_regs_takes_split(int c0, int c1, int hw, int batch) {
   GnRegsGeom geo;
   int th, it, pw;
-  if (!gn_regs_geometry(c0 + c1, hw, batch, &geo, &th, &it, &pw)) return false;
-  // 8-byte pieces (C = 320: the 32 x 32 level of mobi_nusc_256) only on request: in the step graph 21.0 us against 9.8 + 6.5 for
-  // GroupNorm + reduce launch on [8, 1024, 320] x 4 slabs (tools/defer_breakdown.sh) -- 128 blocks read 42 MB of slabs
-  if (pw == 4 && tuning().gn_split_pw4 != 1) return false;
-  return it <= 8 && c0 % pw == 0;
+  return gn_regs_split_geometry(c0, c1, hw, batch, &geo, &th, &it, &pw);
 }
 
+// What launch_gn launches: the form (MOBI_GN_FORM_* of mobi_engine.h) and, for the register and chunked forms, the kernel
+// instantiation and its geometry.  plan_gn decides, launch_gn only launches; mobi_groupnorm_kernel_variant reports the plan.
+struct GnCoopGeom { int chunks, ppb, slots, V; };
+struct GnPlan {
+  int form, threads, items, pw;
+  GnRegsGeom regs;
+  GnCoopGeom coop;
+};
+
 template <typename T>
-static bool launch_gn_regs_split(const GnArgs& a, int batch, hipStream_t st) {
-  GnRegsGeom geo;
-  int th, it, pw;
-  if (!gn_regs_geometry(a.C, a.hw, batch, &geo, &th, &it, &pw) || it > 8 || a.c0 % pw) return false;
-  if (pw == 4 && tuning().gn_split_pw4 != 1) return false;
+static void launch_gn_regs_split(const GnArgs& a, const GnPlan& pl, int batch, hipStream_t st) {
+  const GnRegsGeom geo = pl.regs;
+  const int th = pl.threads, it = pl.items, pw = pl.pw;
   const dim3 grid((unsigned)(32 / geo.gb * batch));
 #define MOBI_GNS(TH_, IT_, PW_) hipLaunchKernelGGL((gn_regs_kernel<T, TH_, IT_, PW_, true>), grid, dim3(TH_), 0, st, a, geo)
   if (pw == 4) MOBI_GNS(1024, 8, 4);
@@ -727,14 +794,12 @@ static bool launch_gn_regs_split(const GnArgs& a, int batch, hipStream_t st) {
     }
   }
 #undef MOBI_GNS
-  return true;
 }
 
 template <typename T>
-static bool launch_gn_regs(const GnArgs& a, int batch, hipStream_t st) {
-  GnRegsGeom geo;
-  int th, it, pw;
-  if (!gn_regs_geometry(a.C, a.hw, batch, &geo, &th, &it, &pw)) return false;
+static void launch_gn_regs(const GnArgs& a, const GnPlan& pl, int batch, hipStream_t st) {
+  const GnRegsGeom geo = pl.regs;
+  const int th = pl.threads, it = pl.items, pw = pl.pw;
   const dim3 grid((unsigned)(32 / geo.gb * batch));
 #define MOBI_GNR(TH_, IT_, PW_) hipLaunchKernelGGL((gn_regs_kernel<T, TH_, IT_, PW_>), grid, dim3(TH_), 0, st, a, geo)
   if (pw == 4) {
@@ -756,7 +821,6 @@ static bool launch_gn_regs(const GnArgs& a, int batch, hipStream_t st) {
     }
   }
 #undef MOBI_GNR
-  return true;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -839,8 +903,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const LnArgs a) {
 // Coherence as in the in-launch split-K finish (csrc/igemm.hip): the partials are stored and loaded device-coherently (sc1), the
 // counter is a device-scope atomic, nothing else changes its cache policy; a block's SECOND arrival (after its fold) lets the last
 // one return the counter to zero, so one zeroed buffer serves every launch of a stream.
-// Algorithmic bytes: 2 B read + 2 B written per element.
-struct GnCoopGeom { int chunks, ppb, slots, V; };
+// Algorithmic bytes: 2 B read + 2 B written per element.  (GnCoopGeom { chunks, ppb, slots, V } stands with GnPlan above.)
 
 __device__ __forceinline__ void st8_dev(float* p, float x, float y) {
   const u32x2 v = {__builtin_bit_cast(unsigned, x), __builtin_bit_cast(unsigned, y)};
@@ -1037,10 +1100,9 @@ static bool gn_coop_default(int C, int hw, int batch) {
 }
 
 template <typename T>
-static bool launch_gn_coop(const GnArgs& a, int batch, hipStream_t st) {
-  GnCoopGeom geo;
-  int it;
-  if (!a.sync || !gn_coop_geometry(a.C, a.hw, batch, gn_compute_units(), &geo, &it)) return false;
+static void launch_gn_coop(const GnArgs& a, const GnPlan& pl, int batch, hipStream_t st) {
+  const GnCoopGeom geo = pl.coop;
+  const int it = pl.items;
   const dim3 grid((unsigned)(batch * geo.chunks));
 #define MOBI_GNC(IT_) hipLaunchKernelGGL((gn_coop_kernel<T, IT_>), grid, dim3(1024), 0, st, a, geo)
   switch (it) {
@@ -1048,28 +1110,20 @@ static bool launch_gn_coop(const GnArgs& a, int batch, hipStream_t st) {
     case 8: MOBI_GNC(8); break;   case 12: MOBI_GNC(12); break; default: MOBI_GNC(16); break;
   }
 #undef MOBI_GNC
-  return true;
 }
 
-template <typename T>
-static int launch_gn(const GnArgs& a, int batch, hipStream_t st) {
-  // small tensors: one launch, the group's slab in LDS (channel pairs: C / 32 even; both sources split at an even channel)
+// the plan step of launch_gn: MOBI_OK and *pl, or the error of a split source no register body takes
+static int plan_gn(const GnArgs& a, int batch, GnPlan* pl) {
+  pl->form = MOBI_GN_FORM_TWO_LAUNCH; pl->threads = pl->items = pl->pw = 0;
+  pl->regs = GnRegsGeom{0, 0, 0}; pl->coop = GnCoopGeom{0, 0, 0, 0};
   const int cpg = a.C / 32;
   if (a.slabs) {                                        // src0 from its producer's split-K slabs: the register form or nothing
-    if (!launch_gn_regs_split<T>(a, batch, st)) return MOBI_ERR_UNSUPPORTED;
-    MOBI_CHECK_LAUNCH();
+    if (!gn_regs_split_geometry(a.c0, a.c1, a.hw, batch, &pl->regs, &pl->threads, &pl->items, &pl->pw)) return MOBI_ERR_UNSUPPORTED;
+    pl->form = MOBI_GN_FORM_REGS_SLABS;
     return MOBI_OK;
   }
   if (a.src_f32 || a.out_mode) {                        // fp32 source / precise outputs: the two-launch form of their own
-    if (a.src_f32) hipLaunchKernelGGL(gn_stats_f32_kernel, dim3(a.chunks, batch), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((gn_stats_kernel<T>), dim3(a.chunks, batch), dim3(256), 0, st, a);
-    MOBI_CHECK_LAUNCH();
-    long long blocks = ((long long)a.hw * (a.C >> 3) + 256 * 4 - 1) / (256 * 4);
-    const long long cap = (2048 + batch - 1) / batch;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL((gn_apply_x_kernel<T>), dim3((unsigned)blocks, batch), dim3(256), 0, st, a);
-    MOBI_CHECK_LAUNCH();
+    pl->form = MOBI_GN_FORM_TWO_LAUNCH_PRECISE;
     return MOBI_OK;
   }
   const int mode = tuning().gn_fused;                   // 0: two launches; 1: the LDS form where it fits; else registers first
@@ -1078,45 +1132,81 @@ static int launch_gn(const GnArgs& a, int batch, hipStream_t st) {
   {
     const int coop = tuning().gn_coop;
     const bool want = coop == 1 || (coop != 0 && gn_coop_default(a.C, a.hw, batch));
-    if (want && mode != 0 && mode != 1 && launch_gn_coop<T>(a, batch, st)) {
-      MOBI_CHECK_LAUNCH();
+    if (want && mode != 0 && mode != 1 && a.sync && gn_coop_geometry(a.C, a.hw, batch, gn_compute_units(), &pl->coop, &pl->items)) {
+      pl->form = MOBI_GN_FORM_CHUNKS; pl->threads = 1024; pl->pw = 8;
       return MOBI_OK;
     }
+    pl->items = 0;
   }
-  if (mode != 0 && mode != 1 && launch_gn_regs<T>(a, batch, st)) {
-    MOBI_CHECK_LAUNCH();
+  if (mode != 0 && mode != 1 && gn_regs_geometry(a.C, a.hw, batch, &pl->regs, &pl->threads, &pl->items, &pl->pw)) {
+    pl->form = MOBI_GN_FORM_REGS;
     return MOBI_OK;
   }
-  if (!(cpg & 1) && (long long)a.hw * cpg <= GN1_MAX && mode != 0) {
-    hipLaunchKernelGGL((gn_fused_kernel<T>), dim3(32, batch), dim3(256), 0, st, a);
-    MOBI_CHECK_LAUNCH();
-    return MOBI_OK;
+  pl->threads = pl->items = pl->pw = 0; pl->regs = GnRegsGeom{0, 0, 0};
+  // small tensors: one launch, the group's slab in LDS (channel pairs: C / 32 even; both sources split at an even channel)
+  if (!(cpg & 1) && (long long)a.hw * cpg <= GN1_MAX && mode != 0) pl->form = MOBI_GN_FORM_LDS;
+  return MOBI_OK;
+}
+
+static int gn_plan_packed(const GnPlan& pl) {
+  const int gb = pl.form == MOBI_GN_FORM_CHUNKS ? pl.coop.chunks : pl.regs.gb;
+  return MOBI_GN_PLAN(pl.form, gb, pl.pw, pl.items, pl.threads);
+}
+
+template <typename T>
+static int launch_gn(const GnArgs& a, int batch, hipStream_t st) {
+  GnPlan pl;
+  const int rc = plan_gn(a, batch, &pl);
+  if (rc != MOBI_OK) return rc;
+  switch (pl.form) {
+    case MOBI_GN_FORM_REGS_SLABS: launch_gn_regs_split<T>(a, pl, batch, st); break;
+    case MOBI_GN_FORM_CHUNKS: launch_gn_coop<T>(a, pl, batch, st); break;
+    case MOBI_GN_FORM_REGS: launch_gn_regs<T>(a, pl, batch, st); break;
+    case MOBI_GN_FORM_LDS: hipLaunchKernelGGL((gn_fused_kernel<T>), dim3(32, batch), dim3(256), 0, st, a); break;
+    default: {                                          // statistics, then apply
+      const bool precise = pl.form == MOBI_GN_FORM_TWO_LAUNCH_PRECISE;
+      if (a.src_f32) hipLaunchKernelGGL(gn_stats_f32_kernel, dim3(a.chunks, batch), dim3(256), 0, st, a);
+      else if (precise) hipLaunchKernelGGL((gn_stats_kernel<T, true>), dim3(a.chunks, batch), dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((gn_stats_kernel<T>), dim3(a.chunks, batch), dim3(256), 0, st, a);
+      MOBI_CHECK_LAUNCH();
+      long long blocks = ((long long)a.hw * (a.C >> 3) + 256 * 4 - 1) / (256 * 4);
+      const long long cap = (2048 + batch - 1) / batch;
+      if (blocks > cap) blocks = cap;
+      if (blocks < 1) blocks = 1;
+      if (precise) hipLaunchKernelGGL((gn_apply_x_kernel<T>), dim3((unsigned)blocks, batch), dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((gn_apply_kernel<T>), dim3((unsigned)blocks, batch), dim3(256), (size_t)12 * a.C, st, a);
+    }
   }
-  hipLaunchKernelGGL((gn_stats_kernel<T>), dim3(a.chunks, batch), dim3(256), 0, st, a);
-  MOBI_CHECK_LAUNCH();
-  const long long vecs = (long long)a.hw * (a.C >> 3);
-  long long blocks = (vecs + 256 * 4 - 1) / (256 * 4);
-  const long long cap = (2048 + batch - 1) / batch;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL((gn_apply_kernel<T>), dim3((unsigned)blocks, batch), dim3(256), (size_t)12 * a.C, st, a);
   MOBI_CHECK_LAUNCH();
   return MOBI_OK;
+}
+
+// the body launch_ln launches, MAXV | LPR << 8 (what mobi_layernorm_kernel_variant reports), or the error of a row too wide
+static int plan_ln(const LnArgs& a) {
+  const int V = a.C >> 3;
+  if (V <= 8) return 1 | 8 << 8;
+  if (V <= 40) return 5 | 8 << 8;                             // C <= 320
+  if (V <= 80) return 5 | 16 << 8;                            // C <= 640
+  if (V <= 160) return 5 | 32 << 8;                           // C <= 1280
+  if (V <= 320) return 5 | 64 << 8;                           // C <= 2560
+  return MOBI_ERR_UNSUPPORTED;
 }
 
 template <typename T>
 static int launch_ln(const LnArgs& a, hipStream_t st) {
   const long long total = (long long)a.images * a.rows;
-  const int V = a.C >> 3;
+  const int body = plan_ln(a);
+  if (body < 0) return body;
 #define MOBI_LN(MAXV_, LPR_)                                                                                           \
   hipLaunchKernelGGL((layernorm_kernel<T, MAXV_, LPR_>), dim3((unsigned)((total + 4 * (64 / LPR_) - 1) / (4 * (64 / LPR_)))), \
                      dim3(256), 0, st, a)
-  if (V <= 8) MOBI_LN(1, 8);
-  else if (V <= 40) MOBI_LN(5, 8);                            // C <= 320
-  else if (V <= 80) MOBI_LN(5, 16);                           // C <= 640
-  else if (V <= 160) MOBI_LN(5, 32);                          // C <= 1280
-  else if (V <= 320) MOBI_LN(5, 64);                          // C <= 2560
-  else return MOBI_ERR_UNSUPPORTED;
+  switch (body) {
+    case 1 | 8 << 8: MOBI_LN(1, 8); break;
+    case 5 | 8 << 8: MOBI_LN(5, 8); break;
+    case 5 | 16 << 8: MOBI_LN(5, 16); break;
+    case 5 | 32 << 8: MOBI_LN(5, 32); break;
+    default: MOBI_LN(5, 64); break;
+  }
 #undef MOBI_LN
   MOBI_CHECK_LAUNCH();
   return MOBI_OK;
@@ -1136,7 +1226,8 @@ extern "C" int mobi_groupnorm_takes_split(int32_t c0, int32_t c1, int32_t batch,
   return mobi::gn_regs_takes_split(c0, c1, hw, batch) ? 1 : 0;
 }
 
-extern "C" int mobi_groupnorm(const mobi_groupnorm_params* p, void* stream) {
+// the argument checks of mobi_groupnorm and its kernel arguments (shared with mobi_groupnorm_kernel_variant)
+static int gn_prepare(const mobi_groupnorm_params* p, mobi::GnArgs& a) {
   using namespace mobi;
   if (!p || (!p->src0 && !p->src0_split) || !p->out || !p->ws || !p->gamma || !p->beta) return MOBI_ERR_ARG;
   if (p->dtype != MOBI_F16 && p->dtype != MOBI_BF16) return MOBI_ERR_ARG;
@@ -1146,7 +1237,6 @@ extern "C" int mobi_groupnorm(const mobi_groupnorm_params* p, void* stream) {
   if (C > 2560 || (long long)p->hw * (C >> 3) >= 0x7fffffffLL) return MOBI_ERR_UNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(p->src0) | reinterpret_cast<uintptr_t>(p->src1) |
        reinterpret_cast<uintptr_t>(p->out)) & 15) return MOBI_ERR_ALIGN;
-  GnArgs a;
   a.src0 = p->src0; a.src1 = p->c1 ? p->src1 : nullptr; a.c0 = p->c0; a.c1 = p->c1; a.C = C;
   a.hw = p->hw; a.chunks = gn_chunks(p->hw);
   a.gamma = p->gamma; a.beta = p->beta; a.eps = p->eps; a.silu = p->silu;
@@ -1172,11 +1262,28 @@ extern "C" int mobi_groupnorm(const mobi_groupnorm_params* p, void* stream) {
     a.s_resid = ss->residual; a.s_res_img = ss->res_img_stride ? ss->res_img_stride : (long long)p->hw * p->c0;
     a.finished = ss->finished;
   }
+  return MOBI_OK;
+}
+
+extern "C" int mobi_groupnorm(const mobi_groupnorm_params* p, void* stream) {
+  using namespace mobi;
+  GnArgs a;
+  const int rc = gn_prepare(p, a);
+  if (rc != MOBI_OK) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   return p->dtype == MOBI_F16 ? launch_gn<f16_t>(a, p->batch, st) : launch_gn<bf16_t>(a, p->batch, st);
 }
 
-extern "C" int mobi_layernorm(const mobi_layernorm_params* p, void* stream) {
+extern "C" int mobi_groupnorm_kernel_variant(const mobi_groupnorm_params* p) {
+  using namespace mobi;
+  GnArgs a;
+  GnPlan pl;
+  int rc = gn_prepare(p, a);
+  if (rc == MOBI_OK) rc = plan_gn(a, p->batch, &pl);
+  return rc != MOBI_OK ? rc : gn_plan_packed(pl);
+}
+
+static int ln_prepare(const mobi_layernorm_params* p, mobi::LnArgs& a) {
   using namespace mobi;
   if (!p || !p->src || !p->out || !p->gamma || !p->beta) return MOBI_ERR_ARG;
   if (p->dtype != MOBI_F16 && p->dtype != MOBI_BF16) return MOBI_ERR_ARG;
@@ -1184,12 +1291,26 @@ extern "C" int mobi_layernorm(const mobi_layernorm_params* p, void* stream) {
   if ((p->src_img_stride & 7) || (p->out_img_stride & 7)) return MOBI_ERR_ALIGN;
   if ((reinterpret_cast<uintptr_t>(p->src) | reinterpret_cast<uintptr_t>(p->out) | reinterpret_cast<uintptr_t>(p->gamma) |
        reinterpret_cast<uintptr_t>(p->beta)) & 15) return MOBI_ERR_ALIGN;
-  LnArgs a;
   a.src = p->src; a.out = p->out; a.images = p->images; a.rows = p->rows_per_image; a.C = p->channels;
   const long long dense = (long long)p->rows_per_image * p->channels;
   a.src_img = p->src_img_stride ? p->src_img_stride : dense;
   a.out_img = p->out_img_stride ? p->out_img_stride : dense;
   a.gamma = p->gamma; a.beta = p->beta; a.eps = p->eps;
+  return MOBI_OK;
+}
+
+extern "C" int mobi_layernorm(const mobi_layernorm_params* p, void* stream) {
+  using namespace mobi;
+  LnArgs a;
+  const int rc = ln_prepare(p, a);
+  if (rc != MOBI_OK) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   return p->dtype == MOBI_F16 ? launch_ln<f16_t>(a, st) : launch_ln<bf16_t>(a, st);
+}
+
+extern "C" int mobi_layernorm_kernel_variant(const mobi_layernorm_params* p) {
+  using namespace mobi;
+  LnArgs a;
+  const int rc = ln_prepare(p, a);
+  return rc != MOBI_OK ? rc : plan_ln(a);
 }

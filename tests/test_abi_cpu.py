@@ -214,6 +214,63 @@ def test_split_source_entry_points_validate_on_the_host(lib):
     assert lib.mobi_groupnorm(C.byref(g), None) == -1                     # neither a tensor nor its slabs
 
 
+def test_norm_plan_queries_answer_on_the_host(lib, tune):
+    """mobi_groupnorm_kernel_variant / mobi_layernorm_kernel_variant launch nothing: the packing the header documents (the
+    MOBI_GN_PLAN_* macros, parsed from it), the error mobi_groupnorm itself returns, the forms the A/B knobs force."""
+    from mobi_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "mobi_engine.h")).read()
+    forms = dict(re.findall(r"MOBI_GN_FORM_([A-Z_]+) = (\d)", hdr))
+    assert forms == dict(TWO_LAUNCH="0", TWO_LAUNCH_PRECISE="1", LDS="2", REGS="3", REGS_SLABS="4", CHUNKS="5")
+    shifts = re.search(r"#define MOBI_GN_PLAN\(form, gb, pw, items, threads\) \(\(form\) \| \(gb\) << (\d+) \| \(pw\) << (\d+) \| "
+                       r"\(items\) << (\d+) \| \(threads\) << (\d+)\)", hdr)
+    assert shifts and [int(s) for s in shifts.groups()] == [4, 10, 14, 20]
+    pack = lambda form, gb, pw, items, threads: form | gb << 4 | pw << 10 | items << 14 | threads << 20
+    for key in ("MOBI_GN_FUSED", "MOBI_GN_COOP", "MOBI_GN_SPLIT_PW4"):
+        tune.delenv(key)
+    g = _lib.GroupNormParams()
+    assert lib.mobi_groupnorm_kernel_variant(None) == -1 and lib.mobi_groupnorm_kernel_variant(C.byref(g)) == -1
+    g.src0 = g.out = g.ws = g.gamma = g.beta = 4096
+    g.c0, g.batch, g.hw, g.eps = 1280, 16, 256, 1e-5
+    assert lib.mobi_groupnorm_kernel_variant(C.byref(g)) == pack(3, 1, 8, 6, 256)       # the 16 x 16 level: 5 pieces per pixel, 51 pixel slots, 6 items
+    g.c0, g.hw = 320, 4096
+    assert lib.mobi_groupnorm_kernel_variant(C.byref(g)) == pack(3, 2, 4, 24, 1024)     # the 64 x 64 level: 8-byte pieces
+    g.c0, g.c1, g.src1 = 640, 320, 4096
+    assert lib.mobi_groupnorm_kernel_variant(C.byref(g)) == pack(0, 0, 0, 0, 0)         # its 960-channel concat: two launches
+    g.c1, g.src1, g.c0, g.hw = 0, None, 48, 64
+    assert lib.mobi_groupnorm_kernel_variant(C.byref(g)) == -2 == lib.mobi_groupnorm(C.byref(g), None)
+    g.c0, g.out = 64, 4104
+    assert lib.mobi_groupnorm_kernel_variant(C.byref(g)) == -4 == lib.mobi_groupnorm(C.byref(g), None)
+    g.out = 4096
+    assert lib.mobi_groupnorm_kernel_variant(C.byref(g)) == pack(2, 0, 0, 0, 0)         # C / 32 = 2: no register body, the LDS form
+    g.src_f32 = 1
+    assert lib.mobi_groupnorm_kernel_variant(C.byref(g)) == pack(1, 0, 0, 0, 0)
+    g.src_f32, g.c0 = 0, 1280
+    tune.setenv("MOBI_GN_FUSED", "0")
+    assert lib.mobi_groupnorm_kernel_variant(C.byref(g)) == pack(0, 0, 0, 0, 0)
+    tune.setenv("MOBI_GN_FUSED", "1")
+    assert lib.mobi_groupnorm_kernel_variant(C.byref(g)) == pack(2, 0, 0, 0, 0)
+    tune.delenv("MOBI_GN_FUSED")
+    ss = _lib.SplitSource()
+    ss.slabs, ss.count, ss.row_stride = 4096, 4, 1280
+    g.src0, g.src0_split = None, C.pointer(ss)
+    assert lib.mobi_groupnorm_kernel_variant(C.byref(g)) == pack(4, 1, 8, 2, 256)       # [16, 64, 1280] from four slabs
+    assert lib.mobi_groupnorm_takes_split(1280, 0, 16, 64) == 1
+    g.c0, g.hw, ss.row_stride = 320, 1024, 320
+    assert lib.mobi_groupnorm_kernel_variant(C.byref(g)) == -2 and lib.mobi_groupnorm_takes_split(320, 0, 16, 1024) == 0
+    tune.setenv("MOBI_GN_SPLIT_PW4", "1")
+    assert lib.mobi_groupnorm_kernel_variant(C.byref(g)) == pack(4, 2, 4, 8, 1024) and lib.mobi_groupnorm_takes_split(320, 0, 16, 1024) == 1
+    ln = _lib.LayerNormParams()
+    assert lib.mobi_layernorm_kernel_variant(None) == -1 and lib.mobi_layernorm_kernel_variant(C.byref(ln)) == -1
+    ln.src = ln.out = ln.gamma = ln.beta = 4096
+    ln.images, ln.rows_per_image = 2, 77
+    for ch, want in ((8, 1 | 8 << 8), (64, 1 | 8 << 8), (72, 5 | 8 << 8), (320, 5 | 8 << 8), (640, 5 | 16 << 8), (1280, 5 | 32 << 8),
+                     (1288, 5 | 64 << 8), (2560, 5 | 64 << 8), (2568, -2), (100, -2)):
+        ln.channels = ch
+        assert lib.mobi_layernorm_kernel_variant(C.byref(ln)) == want, ch
+    ln.channels, ln.src_img_stride = 320, 77 * 320 + 4
+    assert lib.mobi_layernorm_kernel_variant(C.byref(ln)) == -4 == lib.mobi_layernorm(C.byref(ln), None)
+
+
 def test_integration_md_stub_matches_the_library(monkeypatch):
     """The ctypes stub INTEGRATION.md shows a maintainer is executed as written (from the repo root): its own ABI-version and
     struct-size assertions run against the built library, so the document cannot fall behind the header again."""
