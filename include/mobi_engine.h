@@ -183,9 +183,19 @@ int32_t mobi_igemm_slab_count(const mobi_igemm_params* p);
 int mobi_igemm_finish(const mobi_igemm_params* p, void* stream);
 /* Library heuristic for split_k (1 = do not split) and the workspace it needs. */
 int mobi_igemm_plan_splits(const mobi_igemm_params* p);
-/* Which main loop mobi_igemm would run for these parameters (no launch; measurement / tests):
- * the persistent direct-to-LDS kernels (256-pixel tiles; ping-pong schedule where the register epilogue applies),
- * or the register-staged kernel with 256- or 128-pixel tiles.  Negative = the error mobi_igemm would return. */
+/* Which main loop mobi_igemm would run for these parameters (no launch; measurement / tests).  Tiles are pixels x channels,
+ * the channel tile for n_packed % 160 != 0 | == 0.  Negative = the error mobi_igemm would return.
+ *   MOBI_IGEMM_STAGED_128  128 x 128 | 160, operands staged through registers (generic gather: operands beyond 2 GB)
+ *   MOBI_IGEMM_STAGED_256  256 x 128 | 160, the same kernel with eight waves
+ *   MOBI_IGEMM_DIRECT_LDS  the SAME register-staged 256-pixel kernel as MOBI_IGEMM_STAGED_256: the library has no
+ *                          direct-to-LDS kernel any more, and this value is reported where the former one would have taken the
+ *                          launch (channel runs of 64, operands below 2 GB) -- kept so that no answer changes
+ *   MOBI_IGEMM_PINGPONG    256 x 128 | 160, persistent LDS-DMA kernel, ping-pong schedule, register epilogue or fp32 slabs
+ *   MOBI_IGEMM_RING_128    128 x 128 | 160, LDS-DMA ring in 32-deep k-steps, or in 64-deep steps where the grid is at most one
+ *                          block per CU and the channel runs are multiples of 64
+ *   MOBI_IGEMM_RING_256    256 x 256 | 320 on the ring kernel with eight waves
+ *   MOBI_IGEMM_RING_128W   128 x 256 | 320 on it (A/B only: MOBI_IGEMM_WIDE=1, MOBI_IGEMM_WIDE128=1)
+ *   MOBI_IGEMM_SMALL       32 x 32, the operands-in-registers kernel for small 1 x 1 products */
 enum { MOBI_IGEMM_STAGED_128 = 0, MOBI_IGEMM_STAGED_256 = 1, MOBI_IGEMM_DIRECT_LDS = 2, MOBI_IGEMM_PINGPONG = 3,
        MOBI_IGEMM_RING_128 = 4, MOBI_IGEMM_RING_256 = 5, MOBI_IGEMM_RING_128W = 6, MOBI_IGEMM_SMALL = 7 };
 int mobi_igemm_kernel_variant(const mobi_igemm_params* p);

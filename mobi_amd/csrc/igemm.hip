@@ -8,21 +8,18 @@
 // MFMA 16x16x32, fp32 accumulators, wave tile 64 pixels x 80 (64) channels, [row][64 k] LDS images with 128-byte
 // rows and a 16-byte-slot XOR swizzle (slot ^= row & 7: conflict-free ds_read_b128 fragment reads).
 //
-// Three main loops (igemm_prepare picks one per launch, mobi_igemm_kernel_variant reports it):
-//   igemm_pp_kernel    persistent 256-pixel tiles, operands by LDS-DMA into three stages, PING-PONG schedule (the
-//                      two waves of a SIMD one phase apart: LOAD | MATRIX), deferred register epilogue.  Every
-//                      launch whose tiles are full, whose output is row-major T and that has at most one of
-//                      bias / per-image vector; also the split-K launches with long k ranges (fp32 slabs).
-//   igemm_ring_kernel    128-pixel tiles, four waves, two blocks per CU, operands by LDS-DMA into a ring of four 32-deep
-//                      k-slots: small m, split-K ranges, ragged tiles, every output mode; as 256 x 320 tiles also the
-//                      256-pixel launches that need an LDS-staged epilogue (transposed / fp32 / ragged / bias AND vector)
-//   igemm_kernel       128- / 256-pixel tiles staged through registers, generic gather: operands beyond 2 GB
+// Main loops (igemm_plan, csrc/igemm_plan.hip, picks one per launch; mobi_igemm_kernel_variant reports it):
+//   igemm_pp_kernel      persistent 256-pixel tiles, operands by LDS-DMA into three stages, PING-PONG schedule (the two waves of a
+//                        SIMD one phase apart: LOAD | MATRIX), deferred register epilogue or fp32 slabs
+//   igemm_ring_kernel    128- / 256-pixel tiles, operands by LDS-DMA into a ring of four 32-deep k-slots, LDS-staged or register
+//                        epilogue; igemm_ring64_kernel: its 128-pixel tiles in 64-deep steps
+//   igemm_kernel         128- / 256-pixel tiles staged through registers, generic gather: operands beyond 2 GB
 #include <stdlib.h>
 
 #include <type_traits>
 
 #include "common.h"
-#include "tuning.h"
+#include "igemm_plan.h"
 #include "igemm_small.h"
 
 // A/B switch (build with -DMOBI_IGEMM_FENCE=1): pin the load / MFMA / LDS-write phases of a k step
@@ -134,50 +131,8 @@ __device__ unsigned long long* g_phase = nullptr;
 // (a plain load from here instead of a load + select; the library allocates nothing).
 __device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
 
-struct IgemmArgs {
-  const void* src0; const void* src1;
-  int c0, c1, C;
-  int hin, win, up, hout, wout, hw_out;
-  int kh, kw, stride, pad_h, pad_w;
-  int img_pix_stride;      // pixels between images of the sources (elements / channels)
-  const void* weight; long long w_group_stride;
-  int n_packed, cout, ktot, nk;
-  int M;                 // rows per group
-  int imgs_per_group;
-  const float* bias; const float* rowvec; int rowvec_stride;
-  const void* residual; long long res_img_stride;
-  void* out; long long out_img_stride;
-  int out_mode, epilogue;
-  float scale;
-  int tiles_m, tiles_n;
-  int n_major;             // work list walks the pixel tiles of one channel tile first: an XCD (a contiguous range of the
-                           // list) then streams ITS slice of the weights instead of all of them (launches whose weights
-                           // outweigh their activations: the 16 x 16 / 8 x 8 levels)
-  int src0_bytes, src1_bytes, w_bytes, fast, glds;
-  int k_order;             // always 0 (k = tap*C + c); igemm_pp_kernel still tests it (the field is part of the argument block)
-  int wm;                  // waves along the pixel axis (2 or 4): block tile = 64*wm pixels
-  int splits, nk_per;      // split-K: blockIdx.y owns k-tiles [y*nk_per, (y+1)*nk_per)
-  float* split_ws;         // f32 [splits][M][n_packed] partial sums (NULL: single pass)
-  const float* ln_svec;    // LayerNorm folded into this 1 x 1 launch (see ln_fold_acc): row sums of the packed W diag(gamma), or NULL
-  float ln_eps;
-  int sync_mode;           // 0: no `sync`; 1: device-coherent slab traffic; 2: a tile's blocks share one XCD's L2 (see splitk_arrive_and_finish)
-  int* sync;               // split-K finished inside the launch: one arrival counter per output tile (zero before and after
-                           // the launch), or NULL: the slabs are summed by igemm_splitk_reduce_kernel (a second launch)
-  int ring_direct;         // 256 x 320 ring tiles: register epilogue (full tiles, row-major T output, bias OR per-image vector)
-  int sm_direct;           // 128 x 160 ring tiles: register epilogue / register slab stores (full tiles)
-  const void* w_tiled;     // W as 1-KiB request images (ring kernels), or NULL
-  int sm64;                // 128-pixel tiles on the 64-deep-step kernel (igemm_ring64_kernel)
-  int lin_window;          // always 0 (kept: the struct is the kernels' argument block)
-  int epi_direct;          // direct-to-LDS kernel: register epilogue (full tiles, row-major T output)
-  int pp;                  // register-epilogue launch on the ping-pong kernel
-  int sm;                  // 128-pixel tiles on the LDS-DMA ring kernel (igemm_ring_kernel<.., false>)
-  int wide;                // ring kernel with eight waves: 2 = 256 x 320 (256) tiles, 1 = 128 x 320 (256) tiles
-  int hw_shift, w_shift;   // log2(hw_out), log2(wout) when both are powers of two (ping-pong kernel), else -1
-  int small;               // 32 | 64: the operands-in-registers kernel of csrc/igemm_small.hip with that square tile (0: not)
-};
-
 // (a macro, not a function of `a`: a reference to the kernel-argument struct makes the compiler keep a copy of it in scratch)
-// (the ping-pong kernel, at its register limit, always walks pixel-major: igemm_prepare leaves n_major 0 for it)
+// (the ping-pong kernel, at its register limit, always walks pixel-major: the plan leaves n_major 0 for it)
 #define MOBI_TILE_OF_M(L_, tile_m_, tile_n_) const int tile_n_ = (L_) % a.tiles_n, tile_m_ = (L_) / a.tiles_n
 #define MOBI_TILE_OF(L_, tile_m_, tile_n_)                                                     \
   const int tdiv_##tile_m_ = __builtin_amdgcn_readfirstlane(a.n_major ? a.tiles_m : a.tiles_n); \
@@ -2461,21 +2416,6 @@ __global__ __launch_bounds__(256) void igemm_splitk_reduce_kernel(const IgemmArg
   }
 }
 
-// CUs of the current device (cached per device ordinal); 256 on MI355X.  MOBI_IGEMM_PERSIST_BLOCKS overrides the
-// persistent grid size (tests: few blocks walk many output tiles).
-static int compute_units() {
-  if (tuning().persist_blocks > 0) return tuning().persist_blocks;
-  static int cached[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (!cached[dev]) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cached[dev] = n;
-  }
-  return cached[dev];
-}
-
 template <typename T>
 static int launch_splitk_reduce(const IgemmArgs& a, hipStream_t st) {
   long long blocks = ((long long)a.M * (a.cout >> 3) + 255) / 256;
@@ -2485,149 +2425,53 @@ static int launch_splitk_reduce(const IgemmArgs& a, hipStream_t st) {
   return MOBI_OK;
 }
 
+// One launch of the plan: the body picks the kernel, the plan's flags its instantiation.  The code object holds the kernels in
+// the order in which this function first names them: keep it (leaky ReLU first, then the bodies; tools/device_code_diff.py tells).
 template <typename T>
-static int launch_igemm(const mobi_igemm_params* p, const IgemmArgs& a, int groups, hipStream_t st) {
-  const bool tr = p->out_mode == MOBI_OUT_TRANSPOSED;
-  const bool nt5 = (a.n_packed % 160) == 0;
-  dim3 grid(a.tiles_m * a.tiles_n, a.splits, groups);
-#define MOBI_IGEMM_LAUNCH(NT_, TR_, WM_) hipLaunchKernelGGL((igemm_kernel<T, NT_, TR_, WM_>), grid, dim3(128 * WM_), 0, st, a)
-#define MOBI_IGEMM_BY_TR(NT_, WM_) \
-  do { if (tr) MOBI_IGEMM_LAUNCH(NT_, true, WM_); else MOBI_IGEMM_LAUNCH(NT_, false, WM_); } while (0)
-  if (a.epilogue == MOBI_EPI_LEAKY_RELU) {
-    // (igemm_prepare has put every such launch on the ring kernels' staged epilogue: 256- or 128-pixel tiles)
-    if (a.wide == 2) {
-      if (nt5) hipLaunchKernelGGL((igemm_ring_kernel<T, 5, false, 8, 8, false, true>), grid, dim3(512), 0, st, a);
-      else     hipLaunchKernelGGL((igemm_ring_kernel<T, 4, false, 8, 8, false, true>), grid, dim3(512), 0, st, a);
-    } else {
-      if (nt5) hipLaunchKernelGGL((igemm_ring_kernel<T, 5, false, 4, 4, false, true>), grid, dim3(256), 0, st, a);
-      else     hipLaunchKernelGGL((igemm_ring_kernel<T, 4, false, 4, 4, false, true>), grid, dim3(256), 0, st, a);
-    }
+static int launch_igemm(const IgemmPlan& pl, hipStream_t st) {
+  const IgemmArgs& a = pl.a;
+  const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]), block(pl.block);
+#define MOBI_LAUNCH(...) hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, st, a)
+#define MOBI_STAGED(NT_, TR_, WM_) MOBI_LAUNCH(igemm_kernel<T, NT_, TR_, WM_>)
+#define MOBI_PP(NT_, ...) MOBI_LAUNCH(igemm_pp_kernel<T, NT_, __VA_ARGS__>)                  // GEGLU, SLAB
+#define MOBI_RING(NT_, TR_, ...) MOBI_LAUNCH(igemm_ring_kernel<T, NT_, TR_, __VA_ARGS__>)    // NW, MT, LNF, LEAKY
+#define MOBI_RING64(NT_, TR_, LNF_)                                                                      \
+  do { if (pl.ovl) MOBI_LAUNCH(igemm_ring64_kernel<T, NT_, TR_, LNF_, true>); else MOBI_LAUNCH(igemm_ring64_kernel<T, NT_, TR_, LNF_, false>); } while (0)
+#define MOBI_BY_NT(L_, ...) do { if (pl.nt5) L_(5, __VA_ARGS__); else L_(4, __VA_ARGS__); } while (0)
+#define MOBI_BY_NT_TR(L_, ...)                                                                           \
+  do { if (pl.nt5) { if (pl.tr) L_(5, true, __VA_ARGS__); else L_(5, false, __VA_ARGS__); }              \
+       else        { if (pl.tr) L_(4, true, __VA_ARGS__); else L_(4, false, __VA_ARGS__); } } while (0)
+  if (pl.leaky) {                                            // on the ring kernels' LDS-staged epilogue, 256- or 128-pixel tiles
+    if (pl.body == Body::Ring256) MOBI_BY_NT(MOBI_RING, false, 8, 8, false, true);
+    else                          MOBI_BY_NT(MOBI_RING, false, 4, 4, false, true);
   }
-  else if (a.wide == 2) {
-#define MOBI_W2_LAUNCH(NT_, TR_) hipLaunchKernelGGL((igemm_ring_kernel<T, NT_, TR_, 8, 8>), grid, dim3(512), 0, st, a)
-    if (a.ln_svec) {                                         // LayerNorm folded into the launch: instantiations of their own
-      if (nt5) hipLaunchKernelGGL((igemm_ring_kernel<T, 5, false, 8, 8, true>), grid, dim3(512), 0, st, a);
-      else     hipLaunchKernelGGL((igemm_ring_kernel<T, 4, false, 8, 8, true>), grid, dim3(512), 0, st, a);
-    }
-    else if (nt5) { if (tr) MOBI_W2_LAUNCH(5, true); else MOBI_W2_LAUNCH(5, false); }
-    else     { if (tr) MOBI_W2_LAUNCH(4, true); else MOBI_W2_LAUNCH(4, false); }
-#undef MOBI_W2_LAUNCH
+  else switch (pl.body) {
+    case Body::Ring256:                                      // (LayerNorm folded into the launch: instantiations of their own)
+      if (pl.lnf) MOBI_BY_NT(MOBI_RING, false, 8, 8, true); else MOBI_BY_NT_TR(MOBI_RING, 8, 8);
+      break;
+    case Body::Ring128W: MOBI_BY_NT(MOBI_RING, false, 8, 4); break;
+    case Body::PingPong:
+      if (pl.slab) MOBI_BY_NT(MOBI_PP, false, true); else if (pl.geglu) MOBI_BY_NT(MOBI_PP, true); else MOBI_BY_NT(MOBI_PP, false);
+      break;
+    case Body::Staged256: MOBI_BY_NT_TR(MOBI_STAGED, 4); break;
+    case Body::Ring64:
+      if (pl.lnf) MOBI_BY_NT(MOBI_RING64, false, true); else MOBI_BY_NT_TR(MOBI_RING64, false);
+      break;
+    case Body::Ring128:
+      if (pl.lnf) MOBI_BY_NT(MOBI_RING, false, 4, 4, true); else MOBI_BY_NT_TR(MOBI_RING, 4, 4);
+      break;
+    case Body::Staged128: MOBI_BY_NT_TR(MOBI_STAGED, 2); break;
+    case Body::Small: return MOBI_ERR_ARG;                   // (launch_small's: mobi_igemm does not come here)
   }
-  else if (a.wide == 1) {
-    if (nt5) hipLaunchKernelGGL((igemm_ring_kernel<T, 5, false, 8, 4>), grid, dim3(512), 0, st, a);
-    else     hipLaunchKernelGGL((igemm_ring_kernel<T, 4, false, 8, 4>), grid, dim3(512), 0, st, a);
-  }
-  else if (a.wm == 4 && a.fast && a.glds && a.pp) {
-    // persistent: one 156-KB-LDS block per CU walks the output tiles
-    dim3 block(512);
-    dim3 pgrid(grid.x < (unsigned)compute_units() ? grid.x : (unsigned)compute_units(), grid.y, grid.z);
-    if (a.split_ws) {
-      if (nt5) hipLaunchKernelGGL((igemm_pp_kernel<T, 5, false, true>), pgrid, block, 0, st, a);
-      else     hipLaunchKernelGGL((igemm_pp_kernel<T, 4, false, true>), pgrid, block, 0, st, a);
-    } else {
-#define MOBI_PP_LAUNCH(NT_, G_) hipLaunchKernelGGL((igemm_pp_kernel<T, NT_, G_>), pgrid, block, 0, st, a)
-      if (a.epilogue == MOBI_EPI_GEGLU) { if (nt5) MOBI_PP_LAUNCH(5, true); else MOBI_PP_LAUNCH(4, true); }
-      else                              { if (nt5) MOBI_PP_LAUNCH(5, false); else MOBI_PP_LAUNCH(4, false); }
-#undef MOBI_PP_LAUNCH
-    }
-  }
-  else if (a.wm == 4) { if (nt5) MOBI_IGEMM_BY_TR(5, 4); else MOBI_IGEMM_BY_TR(4, 4); }
-  else if (a.sm && a.sm64) {
-    // requests dealt out between the MFMAs (MOBI_IGEMM_SM64_OVL=0: the sequential step, the A/B partner)
-#define MOBI_SM64_LAUNCH_W(NT_, TR_, LNF_, OVL_) \
-  hipLaunchKernelGGL((igemm_ring64_kernel<T, NT_, TR_, LNF_, OVL_>), grid, dim3(256), 0, st, a)
-#define MOBI_SM64_LAUNCH(NT_, TR_, LNF_) \
-  do { if (tuning().sm64_ovl != 0) MOBI_SM64_LAUNCH_W(NT_, TR_, LNF_, true); else MOBI_SM64_LAUNCH_W(NT_, TR_, LNF_, false); } while (0)
-    if (a.ln_svec) { if (nt5) MOBI_SM64_LAUNCH(5, false, true); else MOBI_SM64_LAUNCH(4, false, true); }
-    else if (nt5) { if (tr) MOBI_SM64_LAUNCH(5, true, false); else MOBI_SM64_LAUNCH(5, false, false); }
-    else     { if (tr) MOBI_SM64_LAUNCH(4, true, false); else MOBI_SM64_LAUNCH(4, false, false); }
-#undef MOBI_SM64_LAUNCH
-#undef MOBI_SM64_LAUNCH_W
-  }
-  else if (a.sm) {
-#define MOBI_SM_LAUNCH(NT_, TR_) hipLaunchKernelGGL((igemm_ring_kernel<T, NT_, TR_, 4, 4>), grid, dim3(256), 0, st, a)
-    if (a.ln_svec) {
-      if (nt5) hipLaunchKernelGGL((igemm_ring_kernel<T, 5, false, 4, 4, true>), grid, dim3(256), 0, st, a);
-      else     hipLaunchKernelGGL((igemm_ring_kernel<T, 4, false, 4, 4, true>), grid, dim3(256), 0, st, a);
-    }
-    else if (nt5) { if (tr) MOBI_SM_LAUNCH(5, true); else MOBI_SM_LAUNCH(5, false); }
-    else     { if (tr) MOBI_SM_LAUNCH(4, true); else MOBI_SM_LAUNCH(4, false); }
-#undef MOBI_SM_LAUNCH
-  }
-  else                { if (nt5) MOBI_IGEMM_BY_TR(5, 2); else MOBI_IGEMM_BY_TR(4, 2); }
-#undef MOBI_IGEMM_BY_TR
-#undef MOBI_IGEMM_LAUNCH
+#undef MOBI_BY_NT_TR
+#undef MOBI_BY_NT
+#undef MOBI_RING64
+#undef MOBI_RING
+#undef MOBI_PP
+#undef MOBI_STAGED
+#undef MOBI_LAUNCH
   MOBI_CHECK_LAUNCH();
-  // (with `sync` the tile's last block has summed the slabs; with defer_finish the consumer does -- mobi_groupnorm's src0_split --
-  //  or a later mobi_igemm_finish)
-  if (a.split_ws && !a.sync && !p->defer_finish) return launch_splitk_reduce<T>(a, st);
-  return MOBI_OK;
-}
-
-// Small problems go to csrc/igemm_small.hip (coalesced loads, a wave-private LDS transposition, k split over the block's four
-// waves, no slabs): returns its tile (32), or 0.  Rules (tools/small_lab.py, graph-timed on cold operands,
-// profiles/r04_small_lab.txt):
-//   1 x 1: up to 1.8 GFLOP of 2 M N K -- 1.0 GFLOP at K = 320, where a wave has a single batch and the LDS kernels' launch is a
-//          10-step loop (8192 x 320 x 320: 16.6 against 12.6 us; 4096 x 320 x 320: 9.9 against 11.8);
-//   3 x 3 (pad 1, stride 1): NOT routed (MOBI_IGEMM_SMALL_CONV_M output pixels, default 0) -- built for the 4 x 4 levels of
-//          `mobi_nusc_256` (128 pixels, 30-60 MB of weights per launch) and measured SLOWER there: 36.1 against 24.7 us
-//          (1280 -> 1280), 66 against 35 (2560 -> 1280): a wave walks 36-72 batches one HBM latency after the other, and 160
-//          blocks of four waves are 2.5 waves per CU (profiles/r04_small_lab_conv.txt).  Kept for tests and the A/B.
-// MOBI_IGEMM_SMALL_MFLOP overrides the 1 x 1 cap; MOBI_IGEMM_SMALL=0 never; 32: every eligible launch whatever its size (A/B, tests).
-constexpr int SMALL_MFLOP_DEFAULT = 1800, SMALL_MFLOP_K320 = 1000, SMALL_CONV_M_DEFAULT = 0;
-static int small_tile(const mobi_igemm_params* p) {
-  if (tuning().small == 0) return 0;
-  // a forced tile geometry (the A/B knobs of the LDS kernels) keeps the launch on them unless this kernel is forced too
-  if (tuning().small < 0 && (tuning().wm == 2 || tuning().wm == 4 || tuning().wide >= 0 || tuning().sm == 0)) return 0;
-  const bool conv3 = p->kh == 3 && p->kw == 3 && p->pad_h == 1 && p->pad_w == 1;
-  if (!(p->kh == 1 && p->kw == 1) && !conv3) return 0;
-  if (p->stride != 1 || p->upsample || p->groups != 1 || p->epilogue != MOBI_EPI_NONE || p->k_order != 0 || p->split_k > 1) return 0;
-  if (p->out_mode != MOBI_OUT_ROWS && p->out_mode != MOBI_OUT_ROWS_F32) return 0;
-  if (p->hout != p->hin || p->wout != p->win) return 0;
-  const int ct = p->c0 + p->c1, N = p->n_packed;
-  const long long K = (long long)ct * p->kh * p->kw;
-  if (ct % 320 || (p->c1 > 0 && p->c0 % 80) || N != p->cout || N % 32) return 0;
-  const long long hw = (long long)p->hin * p->win, M = (long long)p->batch * hw;
-  const long long ips = p->src_img_stride ? p->src_img_stride / p->c0 : hw;
-  const long long cmax = p->c0 > p->c1 ? p->c0 : p->c1;
-  if ((((long long)p->batch - 1) * ips + hw) * cmax * 2 >= 0x7fffffffLL || (long long)N * K * 2 >= 0x7fffffffLL) return 0;
-  if (tuning().small > 0) return 32;
-  if (conv3) {
-    const int cap_m = tuning().small_conv_m >= 0 ? tuning().small_conv_m : SMALL_CONV_M_DEFAULT;
-    return M <= cap_m ? 32 : 0;
-  }
-  const int cap = tuning().small_mflop >= 0 ? tuning().small_mflop : (K == 320 ? SMALL_MFLOP_K320 : SMALL_MFLOP_DEFAULT);
-  if (2.0 * (double)M * N * (double)K > 1e6 * cap) return 0;
-  return 32;
-}
-
-// split-K plan: only when the tile grid cannot fill the chip and k is long
-static int plan_splits(long long M, int n_packed, int ktot) {
-  const int bn = (n_packed % 160) == 0 ? 160 : 128;
-  const long long tiles = ((M + 127) / 128) * ((n_packed + bn - 1) / bn);
-  const int nk = (ktot + 63) / 64;
-  // round 5 (profiles/r05_split_sweep.txt, slabs + reduce launch timed together): 20 k-tiles never pay for a second launch
-  // ([2048 | 1024 x 1280 x 1280] 22.2 / 20.7 us unsplit against 23.3 / 21.1 split in two; [8192 x 320 x 1280] 21.9 against 23.3)
-  const bool r5 = tuning().split_round4 != 0;   // MOBI_IGEMM_SPLIT_ROUND4=0: round 4's plan (A/B)
-  if (tiles >= 384 || nk < (r5 ? 24 : 16)) return 1;
-  if (tiles >= 256 && (r5 ? nk <= 40 : nk < 40)) return 1;   // one full wave of blocks, short k ([4096 x 1280 x 2560]: 40.3 us unsplit, 44.1 in two)
-  const long long target = tuning().split_target > 0 ? tuning().split_target : 512;      // MOBI_IGEMM_SPLIT_TARGET (sweeps)
-  long long s = (target + tiles - 1) / tiles;
-  const long long cap = tiles <= 16 ? 16 : 8;               // a handful of tiles (the 4x4 / 8x8 levels): measured best at 16
-  if (s > cap) s = cap;
-  if (s > nk / 8) s = nk / 8;
-  // the reduce launch sums four slabs per round: 5 .. 7 splits buy a second round for little more parallelism ([1024 x 1280 x 2560]
-  // 23.6 us at 4 against 29.5 at 5; [2048 x 640 x 2560] 23.0 against 28.3), and so do 8 on 64 tiles or more with at most 96 k-tiles
-  // ([1024 x 1280 x 5120] 31.3 against 35.7, [2048 x 640 x 5760] 32.6 against 35.7; fewer tiles still want 8: [512 x 1280 x 5120])
-  if (r5) {
-    if (s > 4 && s < 8) s = 4;
-    if (s == 8 && nk <= 96 && tiles >= 64) s = 4;
-  }
-  // one round of 128-pixel tiles and a very long k range per split (the 16 x 16 level's 1280 -> 1280 and 2560 -> 1280 3 x 3
-  // convolutions: 90 / 180 k-tiles per split at s = 2): twice the splits -- 114.7 against 126.3 us and 198.8 against 225.3
-  // (tools/sweep_split.py), -0.08 ms per step; MOBI_IGEMM_SPLIT_LONGK=0 keeps the old plan (A/B)
-  if (tiles >= 128 && tiles <= 256 && s >= 2 && nk / s >= 80 && tuning().split_longk != 0) s *= 2;
-  return s < 2 ? 1 : (int)s;
+  return pl.reduce_after ? launch_splitk_reduce<T>(a, st) : MOBI_OK;
 }
 
 }  // namespace mobi
@@ -2643,272 +2487,8 @@ extern "C" int mobi_debug_set_phases(void* buf) {
 }
 #endif
 
-extern "C" int mobi_igemm_plan_splits(const mobi_igemm_params* p) {
-  // (GEGLU and MOBI_EPI_LEAKY_RELU launches never split)
-  if (!p || p->groups != 1 || p->epilogue != MOBI_EPI_NONE || p->out_mode == MOBI_OUT_TRANSPOSED || p->ln_svec) return 1;
-  {
-    mobi_igemm_params q = *p;
-    q.split_k = 0;
-    if (mobi::small_tile(&q)) return 1;
-  }
-  return mobi::plan_splits((long long)p->batch * p->hout * p->wout, p->n_packed, p->kh * p->kw * (p->c0 + p->c1));
-}
-
-extern "C" size_t mobi_igemm_workspace_bytes(const mobi_igemm_params* p, int32_t splits) {
-  if (!p || splits <= 1) return 0;
-  return (size_t)splits * p->batch * p->hout * p->wout * p->n_packed * sizeof(float);
-}
-
-// arrival counters of a split launch that finishes itself: one int per output tile of the SMALLEST tile geometry (128 pixels
-// x 128 channels), whichever kernel runs it
-extern "C" size_t mobi_igemm_sync_bytes(const mobi_igemm_params* p, int32_t splits) {
-  if (!p || splits <= 1) return 0;
-  const size_t m = (size_t)p->batch * p->hout * p->wout;
-  return ((m + 127) / 128) * (((size_t)p->n_packed + 127) / 128) * sizeof(int32_t);
-}
-
-// argument checks + launch plan (tile height, addressing path, main-loop variant, split-K ranges, epilogue kind)
-static int igemm_prepare(const mobi_igemm_params* p, mobi::IgemmArgs& a) {
-  using namespace mobi;
-  if (!p || !p->src0 || !p->weight || !p->out) return MOBI_ERR_ARG;
-  if (p->dtype != MOBI_F16 && p->dtype != MOBI_BF16) return MOBI_ERR_ARG;
-  if (p->c0 <= 0 || (p->c0 & 31) || p->c1 < 0 || (p->c1 & 31) || (p->c1 > 0 && !p->src1)) return MOBI_ERR_UNSUPPORTED;
-  if (p->batch <= 0 || p->hin <= 0 || p->win <= 0 || p->hout <= 0 || p->wout <= 0) return MOBI_ERR_ARG;
-  if (p->kh <= 0 || p->kw <= 0 || p->stride <= 0 || p->groups <= 0 || p->batch % p->groups) return MOBI_ERR_ARG;
-  if (p->cout <= 0 || p->n_packed <= 0) return MOBI_ERR_ARG;
-  if (p->upsample != 0 && p->upsample != 1) return MOBI_ERR_ARG;
-  const bool geglu = p->epilogue == MOBI_EPI_GEGLU;
-  const bool leaky = p->epilogue == MOBI_EPI_LEAKY_RELU;
-  if (p->epilogue != MOBI_EPI_NONE && !geglu && !leaky) return MOBI_ERR_ARG;
-  // leaky ReLU: row-major output, one pass, no LayerNorm fold, tap-major k (the ring kernels' staged epilogue applies it)
-  if (leaky && (p->out_mode == MOBI_OUT_TRANSPOSED || p->ln_svec || p->split_k > 1 || p->k_order != 0))
-    return MOBI_ERR_UNSUPPORTED;
-  if (p->out_mode < 0 || p->out_mode > 2) return MOBI_ERR_ARG;
-  if (p->out_mode != MOBI_OUT_TRANSPOSED && (p->cout & 7)) return MOBI_ERR_UNSUPPORTED;
-  if (geglu && (p->out_mode != MOBI_OUT_ROWS || p->rowvec || p->residual)) return MOBI_ERR_UNSUPPORTED;
-  if (!geglu && p->n_packed != p->cout) return MOBI_ERR_ARG;
-  if (geglu && p->n_packed != 2 * p->cout) return MOBI_ERR_ARG;
-  if (p->out_mode == MOBI_OUT_TRANSPOSED && (p->rowvec || p->residual)) return MOBI_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(p->bias) | reinterpret_cast<uintptr_t>(p->rowvec)) & 15) return MOBI_ERR_ALIGN;
-  if (p->rowvec && (p->rowvec_stride & 3)) return MOBI_ERR_ALIGN;
-  if ((reinterpret_cast<uintptr_t>(p->src0) | reinterpret_cast<uintptr_t>(p->src1) |
-       reinterpret_cast<uintptr_t>(p->weight) | reinterpret_cast<uintptr_t>(p->out) |
-       reinterpret_cast<uintptr_t>(p->residual)) & 15) return MOBI_ERR_ALIGN;
-
-  // LayerNorm folded into the launch (ln_fold_acc): a 1 x 1 product of ONE source whose block sweeps all of k
-  const bool lnf = p->ln_svec != nullptr;
-  if (lnf) {
-    if (p->kh != 1 || p->kw != 1 || p->c1 || p->stride != 1 || p->upsample || p->groups != 1 || p->split_k > 1 || p->rowvec ||
-        p->residual || p->out_mode == MOBI_OUT_TRANSPOSED || p->scale != 1.0f || p->k_order != 0 || p->hout != p->hin || p->wout != p->win)
-      return MOBI_ERR_UNSUPPORTED;
-    if (reinterpret_cast<uintptr_t>(p->ln_svec) & 15) return MOBI_ERR_ALIGN;
-  }
-  a.ln_svec = p->ln_svec; a.ln_eps = p->ln_eps;
-  a.src0 = p->src0; a.src1 = p->src1;
-  a.c0 = p->c0; a.c1 = p->c1; a.C = p->c0 + p->c1;
-  a.hin = p->hin; a.win = p->win; a.up = p->upsample;
-  a.hout = p->hout; a.wout = p->wout; a.hw_out = p->hout * p->wout;
-  a.kh = p->kh; a.kw = p->kw; a.stride = p->stride; a.pad_h = p->pad_h; a.pad_w = p->pad_w;
-  const long long hw_in = (long long)p->hin * p->win;
-  if (p->src_img_stride && (p->c1 || p->src_img_stride % p->c0)) return MOBI_ERR_UNSUPPORTED;
-  const long long ips = p->src_img_stride ? p->src_img_stride / p->c0 : hw_in;
-  if (ips * p->batch > 0x7fffffffLL) return MOBI_ERR_UNSUPPORTED;
-  a.img_pix_stride = (int)ips;
-  a.weight = p->weight; a.w_group_stride = p->groups > 1 ? p->w_group_stride : 0;
-  a.n_packed = p->n_packed; a.cout = p->cout;
-  a.ktot = p->kh * p->kw * a.C;
-  a.nk = (a.ktot + 63) / 64;
-  a.imgs_per_group = p->batch / p->groups;
-  a.M = a.imgs_per_group * a.hw_out;
-  a.bias = p->bias; a.rowvec = p->rowvec; a.residual = p->residual;
-  a.rowvec_stride = p->rowvec_stride ? p->rowvec_stride : p->cout;
-  a.res_img_stride = p->res_img_stride ? p->res_img_stride : (long long)a.hw_out * p->cout;
-  a.out = p->out;
-  a.out_img_stride = p->out_img_stride ? p->out_img_stride : (long long)a.hw_out * p->cout;
-  a.out_mode = p->out_mode; a.epilogue = p->epilogue; a.scale = p->scale;
-  const int bn = (p->n_packed % 160) == 0 ? 160 : 128;
-  // 256-pixel tiles (8 waves, one block per CU) when that still gives every CU a block; MOBI_IGEMM_WM overrides
-  {
-    const long long tiles256 = ((a.M + 255) / 256) * (long long)((p->n_packed + bn - 1) / bn);
-    a.wm = tiles256 >= 256 ? 4 : 2;
-    // split-K launches with long k ranges: 256-pixel tiles (ping-pong kernel) once tiles x splits fill the chip
-    if (p->split_k > 1 && a.M % 256 == 0 && tiles256 * p->split_k >= 256 && a.nk / p->split_k >= 16) a.wm = 4;
-    if (tuning().pp_split == 0 && p->split_k > 1 && tiles256 < 256) a.wm = 2;
-    if (tuning().wm == 2 || tuning().wm == 4) a.wm = tuning().wm;
-  }
-  a.tiles_m = (a.M + 64 * a.wm - 1) / (64 * a.wm);
-  bool ring_ok = false;
-  {
-    // a.fast (what the ping-pong kernel needs): k-tiles never straddle a tap or a source, and every byte offset fits 31 bits
-    const long long ext0 = (((long long)p->batch - 1) * ips + hw_in) * p->c0 * 2;
-    const long long ext1 = p->c1 ? (((long long)p->batch - 1) * ips + hw_in) * p->c1 * 2 : 0;
-    const long long wext = (long long)p->n_packed * a.ktot * 2;
-    a.fast = (a.C % 64 == 0) && (p->c1 == 0 || p->c0 % 64 == 0) && ext0 < 0x7fffffffLL && ext1 < 0x7fffffffLL &&
-             wext < 0x7fffffffLL;
-    if (tuning().fast == 0) a.fast = 0;
-    // tap-major k only: the chunk-major order (1) measured slower and no kernel is routed for it any more
-    if (p->k_order != 0) return p->k_order == 1 ? MOBI_ERR_UNSUPPORTED : MOBI_ERR_ARG;
-    a.k_order = 0;
-    a.glds = 1;
-    if (tuning().glds == 0) a.glds = 0;
-    // 128-pixel tiles: the LDS-DMA ring kernel whenever the 32-bit buffer offsets reach every operand byte
-    // (k-steps are 32 deep there: channel counts are multiples of 32 by the ABI's own rule)
-    ring_ok = ext0 < 0x7fffffffLL && ext1 < 0x7fffffffLL && wext < 0x7fffffffLL;
-    a.sm = a.wm == 2 && ring_ok;
-    if (tuning().sm == 0) a.sm = 0;
-    a.src0_bytes = (int)(ext0 < 0x7fffffffLL ? ext0 : 0);
-    a.src1_bytes = (int)(ext1 < 0x7fffffffLL ? ext1 : 0);
-    a.w_bytes = (int)(wext < 0x7fffffffLL ? wext : 0);
-  }
-  a.tiles_n = (p->n_packed + bn - 1) / bn;
-  if ((long long)a.tiles_m * a.tiles_n > 0x7fffffffLL) return MOBI_ERR_UNSUPPORTED;
-  a.splits = 1; a.nk_per = a.nk; a.split_ws = nullptr;
-  if (p->split_k > 1) {
-    if (!p->ws || p->groups != 1 || geglu || p->out_mode == MOBI_OUT_TRANSPOSED || p->split_k > 64) return MOBI_ERR_UNSUPPORTED;
-    if (reinterpret_cast<uintptr_t>(p->ws) & 15) return MOBI_ERR_ALIGN;
-    a.nk_per = (a.nk + p->split_k - 1) / p->split_k;
-    a.splits = (a.nk + a.nk_per - 1) / a.nk_per;            // no empty k ranges: every slab that is summed is written
-    a.split_ws = reinterpret_cast<float*>(p->ws);
-  }
-  if (p->defer_finish != 0 && p->defer_finish != 1) return MOBI_ERR_ARG;
-  // deferred finish: the slabs are the launch's result -- T rows only (what a consumer reconstructs), never with `sync`
-  if (p->defer_finish && (!a.split_ws || p->sync || p->out_mode != MOBI_OUT_ROWS)) return MOBI_ERR_UNSUPPORTED;
-  a.lin_window = 0;                                         // (it belonged to the chunk-major k order)
-  // register epilogue of the direct-to-LDS kernel: every tile full, row-major T output, no per-image vector
-  // (a per-image vector takes the bias registers: never both, and every wave's 64 pixels inside one image)
-  a.epi_direct = a.wm == 4 && a.fast && a.glds && p->out_mode == MOBI_OUT_ROWS && !a.split_ws &&
-                 (!p->rowvec || (!p->bias && a.hw_out % 64 == 0)) && a.M % 256 == 0 && p->n_packed % bn == 0 &&
-                 a.nk_per >= 3;
-  if (tuning().epi_direct == 0) a.epi_direct = 0;
-  // ping-pong kernel: window pixels linear in the tap (no upsampling, <= 16 taps), one k range
-  auto log2_exact = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (1 << s) == v ? s : -1; };
-  a.hw_shift = log2_exact(a.hw_out); a.w_shift = log2_exact(a.wout);
-  a.pp = a.epi_direct && a.splits == 1 && p->scale == 1.0f && a.hw_shift >= 6 && a.w_shift >= 0 &&
-         a.hout < 32768 && a.wout < 32768;
-  // split-K on the ping-pong kernel (fp32 slabs from the registers, finished by the reduce launch): long k, full tiles
-  if (a.split_ws && a.wm == 4 && a.fast && a.glds && p->out_mode != MOBI_OUT_TRANSPOSED && a.M % 256 == 0 &&
-      p->n_packed % bn == 0 && a.nk_per >= 3 && p->scale == 1.0f && a.hw_shift >= 6 && a.w_shift >= 0 &&
-      a.hout < 32768 && a.wout < 32768)
-    a.pp = 1;
-  if (tuning().pp == 0) a.pp = 0;
-  // 256 x 320 (256) tiles on the ring kernel
-  // (measured, tools/ab_wide.py: 3x3 convolutions at 64x64 x 16: 1071-1245 vs 813-976 TFLOP/s on the ping-pong kernel;
-  //  it needs about one block per CU: with 128 tiles -- the 32x32 level at N = 640 -- half the chip idles and it loses;
-  //  the 128 x 320 tile (twice the blocks at the ping-pong tile's bytes per FLOP) measured 829-965 TFLOP/s there against
-  //  982-1085 on the ping-pong kernel: kept for A/B (MOBI_IGEMM_WIDE128=1), not routed)
-  a.wide = 0;
-  if ((a.wm == 4 || tuning().wide > 0) && ring_ok && tuning().wide != 0) {
-    const int bnw = (p->n_packed % 160) == 0 ? 320 : 256;
-    const long long tn = (p->n_packed + bnw - 1) / bnw;
-    auto fills = [&](long long blocks) {
-      const long long rounds = (blocks + 255) / 256;
-      return blocks >= 190 && blocks * 5 >= rounds * 256 * 4 - 64 * (rounds == 1);   // rounds about 80 % full on average
-                                                                       // (192 blocks, 1280 -> 3840 at 16 x 16 x 16: 43.4 vs 51.7 us)
-    };
-    const long long t256 = ((a.M + 255) / 256) * tn * a.splits, t128 = ((a.M + 127) / 128) * tn * a.splits;
-    int pick = tuning().wide > 0 ? tuning().wide : (fills(t256) ? 2 : (fills(t128) && tuning().wide128 == 1 ? 1 : 0));
-    // a channel tile that is half padding or more (128 output channels in a 256-wide tile: the VAEs' 128-channel levels)
-    // loses to the ping-pong kernel's 256 x 128 tile: 878 vs 1160 us on 128 -> 128 3x3 at 512 x 512 x 8 (tools/kbench.py conv)
-    if (tuning().wide <= 0 && pick == 2 && p->n_packed * 2 <= bnw && a.pp) pick = 0;
-    // launches of the 256-pixel geometry that the ping-pong kernel's register epilogue does not take (transposed / fp32
-    // output, ragged tiles, bias AND per-image vector, per-image weights): the ring kernel's LDS-staged epilogue does
-    // (a source of fewer than 64 channels into a wide layer -- the UNet's 9-channel input, padded to 32: a tap per k-step --
-    //  stays on the register-staged kernel: 38 against 104 us on 9 -> 320 at 64 x 64 x 16)
-    if (!pick && a.wm == 4 && !a.pp && (a.C >= 64 || p->out_mode != MOBI_OUT_ROWS || p->n_packed < 256)) pick = 2;
-    if (lnf) pick = a.wm == 4 ? 2 : 0;                      // the LayerNorm fold lives in the 256 x 320 / 128 x 160 ring tiles
-    if (pick) {
-      a.wide = pick;
-      a.wm = pick == 2 ? 4 : 2;
-      a.tiles_m = (a.M + 64 * a.wm - 1) / (64 * a.wm);
-      a.tiles_n = (int)tn;
-      a.sm = 0;
-    }
-  }
-  // order of the work list (tile_of): by channel tile when a 1 x 1 launch's weights outweigh the activations it reads --
-  // every XCD's L2 then fetches its slice of the weights and all of the (smaller) activations instead of all of the weights
-  // and its slice of the activations.  Measured (tools/ab_nmajor.sh): the 16 x 16 level's GEGLU projection (26 MB of weights,
-  // 10.5 MB of activations) 219-223 against 233-237 us; 3 x 3 convolutions LOSE 3-6 % (143.7 vs 139.5 us at 1280 -> 1280,
-  // 16 x 16: nine taps re-read the whole activation tensor through every L2), so they keep the pixel-major order.
-  {
-    const long long wbytes = (long long)p->n_packed * a.ktot * 2;
-    const long long abytes = (long long)p->batch * p->hin * p->win * a.C * 2;
-    a.n_major = p->groups == 1 && a.tiles_n >= 2 && p->kh * p->kw == 1 && wbytes > abytes && tuning().n_major != 0;
-    if (tuning().n_major == 1 && p->groups == 1) a.n_major = 1;
-    if (!a.wide && a.wm == 4 && a.fast && a.glds && a.pp) a.n_major = 0;      // the ping-pong kernel's launches
-  }
-  // 64-deep steps for the 128-pixel geometry: channel runs of 64 (a k-step never straddles a tap or a source), >= 3 steps
-  // (one block per CU: only grids of at most one round of blocks -- with more, two co-resident blocks of the 32-deep ring win:
-  //  36.2 vs 45.3 us on 320 -> 320 3x3 at 32 x 32 x 8 split 4, tools/ab_sm64.py)
-  a.sm64 = a.sm && a.C % 64 == 0 && (p->c1 == 0 || p->c0 % 64 == 0) && a.nk_per >= 1 &&
-           (long long)a.tiles_m * a.tiles_n * a.splits * p->groups <= (long long)compute_units() && tuning().sm64 != 0;
-  if (tuning().sm64 == 1 && a.sm && a.C % 64 == 0 && (p->c1 == 0 || p->c0 % 64 == 0)) a.sm64 = 1;
-  a.w_tiled = (p->weight_tiled && !a.sm64 && (a.sm || a.wide) &&
-               (p->groups == 1 || p->w_group_stride == (long long)p->n_packed * a.ktot) && p->n_packed % 16 == 0 &&
-               a.ktot % 32 == 0 && !(reinterpret_cast<uintptr_t>(p->weight_tiled) & 15) && tuning().w_tiled != 0)
-                  ? p->weight_tiled : nullptr;
-  // 128 x 160 ring tiles: register epilogue / slab stores when every tile is full (the staged epilogue keeps ragged tiles,
-  // transposed / fp32 output, bias AND per-image vector)
-  // (groups: every group's rows are whole tiles -- a.M is the rows of ONE group -- and the epilogue addresses rows, residual and
-  //  per-image vector through the group's first image; the bias is shared by the groups)
-  a.sm_direct = (a.sm || a.wide == 1) && (p->out_mode == MOBI_OUT_ROWS || a.split_ws) && p->out_mode != MOBI_OUT_TRANSPOSED &&
-                a.M % 128 == 0 && p->n_packed % (a.wide == 1 ? 2 * bn : bn) == 0 &&
-                (a.split_ws || !p->rowvec || (!p->bias && a.hw_out % 64 == 0)) && tuning().sm_direct != 0;
-  {
-    const int bnw = (p->n_packed % 160) == 0 ? 320 : 256;
-    a.ring_direct = a.wide == 2 && p->out_mode == MOBI_OUT_ROWS && !a.split_ws && p->groups == 1 &&
-                    (!p->rowvec || (!p->bias && a.hw_out % 128 == 0)) && a.M % 256 == 0 && p->n_packed % bnw == 0 &&
-                    p->scale == 1.0f && !p->residual && tuning().ring_direct != 0;
-    // (with a residual the staged epilogue is as fast or a microsecond faster: 28.1 vs 29.2 us on 320 -> 320 1x1 at 64 x 64 x 16,
-    //  98.9 vs 100.2 on the 3x3; MOBI_IGEMM_RING_DIRECT=1 forces the register epilogue there too)
-    if (tuning().ring_direct == 1 && p->residual && a.wide == 2 && p->out_mode == MOBI_OUT_ROWS && !a.split_ws && p->groups == 1 &&
-        (!p->rowvec || (!p->bias && a.hw_out % 128 == 0)) && a.M % 256 == 0 && p->n_packed % bnw == 0 && p->scale == 1.0f)
-      a.ring_direct = 1;
-  }
-  if (leaky) {
-    // MOBI_EPI_LEAKY_RELU lives in the ring kernels' LDS-staged epilogue only: 256 x 256 (320) tiles for launches of the
-    // 256-pixel geometry with at least 256 output channels, 128 x 128 (160) tiles otherwise; the register epilogues, the
-    // ping-pong / direct / small kernels and the 64-deep ring never see it.  Operands beyond the ring's 2 GB: unsupported.
-    if (!ring_ok) return MOBI_ERR_UNSUPPORTED;
-    a.pp = 0; a.epi_direct = 0; a.sm_direct = 0; a.ring_direct = 0; a.sm64 = 0; a.n_major = 0;
-    if (a.wm == 4 && p->n_packed >= 256) {
-      const int bnw = (p->n_packed % 160) == 0 ? 320 : 256;
-      a.wide = 2; a.sm = 0;
-      a.tiles_m = (a.M + 255) / 256;
-      a.tiles_n = (p->n_packed + bnw - 1) / bnw;
-    } else {
-      a.wide = 0; a.wm = 2; a.sm = 1;
-      a.tiles_m = (a.M + 127) / 128;
-      a.tiles_n = (p->n_packed + bn - 1) / bn;
-    }
-    a.w_tiled = (p->weight_tiled && (p->groups == 1 || p->w_group_stride == (long long)p->n_packed * a.ktot) &&
-                 p->n_packed % 16 == 0 && a.ktot % 32 == 0 && !(reinterpret_cast<uintptr_t>(p->weight_tiled) & 15) &&
-                 tuning().w_tiled != 0) ? p->weight_tiled : nullptr;
-    if ((long long)a.tiles_m * a.tiles_n > 0x7fffffffLL) return MOBI_ERR_UNSUPPORTED;
-  }
-  a.small = lnf || leaky ? 0 : small_tile(p);
-  if (lnf && !(a.wide || a.sm)) return MOBI_ERR_UNSUPPORTED;  // (operands beyond the ring kernels' 2 GB: LayerNorm as a launch)
-  // split-K finished inside the launch: the LDS-DMA kernels (ring tiles of every geometry; the ping-pong kernel when every
-  // block owns exactly one output tile -- its epilogue is deferred into the next tile's loop otherwise); the register-staged
-  // fallback keeps the reduce launch.  MOBI_IGEMM_FUSED_SPLIT=0: never (A/B)
-  // At most FOUR splits (splitk_finish_tile).  MOBI_IGEMM_FUSED_SPLIT: 0 never; 1 device-coherent slab traffic; 2 (default) the
-  // same-XCD form where the grid's x extent (the tile count: one tile per block) is a multiple of 8, the reduce launch elsewhere
-  a.sync = nullptr; a.sync_mode = 0;
-  if (a.split_ws && p->sync && !a.small && tuning().fused_split != 0 && a.splits <= 4 &&
-      (long long)a.splits * a.M * a.n_packed * 4 < 0x7fffffffLL) {
-    if (reinterpret_cast<uintptr_t>(p->sync) & 3) return MOBI_ERR_ALIGN;
-    const long long tiles = (long long)a.tiles_m * a.tiles_n;
-    const bool pp_launch = !a.wide && a.wm == 4 && a.fast && a.glds && a.pp;
-    const bool ring_launch = a.wide || a.sm;
-    const int mode = tuning().fused_split == 1 ? 1 : 2;
-    if ((ring_launch || (pp_launch && tiles <= (long long)compute_units())) && (mode == 1 || tiles % 8 == 0)) {
-      a.sync = reinterpret_cast<int*>(p->sync);
-      a.sync_mode = mode;
-    }
-  }
-  return MOBI_OK;
-}
-
-static int launch_small(const mobi_igemm_params* p, const mobi::IgemmArgs& a, hipStream_t st) {
+static int launch_small(const mobi_igemm_params* p, const mobi::IgemmPlan& pl, hipStream_t st) {
+  const mobi::IgemmArgs& a = pl.a;
   mobi::SmallGemmArgs s;
   s.src0 = a.src0; s.src1 = a.src1; s.c0 = a.c0; s.c1 = a.c1;
   s.taps = a.kh * a.kw; s.hin = a.hin; s.win = a.win;
@@ -2919,7 +2499,7 @@ static int launch_small(const mobi_igemm_params* p, const mobi::IgemmArgs& a, hi
   s.residual = a.residual; s.res_img_stride = a.res_img_stride;
   s.out = a.out; s.out_img_stride = a.out_img_stride; s.out_f32 = a.out_mode == MOBI_OUT_ROWS_F32;
   s.scale = a.scale;
-  s.tiles_m = (a.M + a.small - 1) / a.small; s.tiles_n = a.n_packed / a.small;
+  s.tiles_m = (a.M + pl.tile_m - 1) / pl.tile_m; s.tiles_n = a.n_packed / pl.tile_n;
   const long long wbytes = (long long)a.n_packed * a.ktot * 2, abytes = (long long)a.M * a.ktot * 2;
   s.n_major = wbytes > abytes;
   return mobi::launch_small_gemm(s, p->dtype, st);
@@ -2927,38 +2507,20 @@ static int launch_small(const mobi_igemm_params* p, const mobi::IgemmArgs& a, hi
 
 extern "C" int mobi_igemm(const mobi_igemm_params* p, void* stream) {
   using namespace mobi;
-  IgemmArgs a;
-  const int rc = igemm_prepare(p, a);
+  IgemmPlan pl;
+  const int rc = igemm_plan(p, pl);
   if (rc != MOBI_OK) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (a.small) return launch_small(p, a, st);
-  return p->dtype == MOBI_F16 ? launch_igemm<f16_t>(p, a, p->groups, st) : launch_igemm<bf16_t>(p, a, p->groups, st);
-}
-
-extern "C" int32_t mobi_igemm_slab_count(const mobi_igemm_params* p) {
-  mobi::IgemmArgs a;
-  const int rc = igemm_prepare(p, a);
-  if (rc != MOBI_OK) return rc;
-  return a.small ? 1 : a.splits;
+  if (pl.body == Body::Small) return launch_small(p, pl, st);
+  return p->dtype == MOBI_F16 ? launch_igemm<f16_t>(pl, st) : launch_igemm<bf16_t>(pl, st);
 }
 
 extern "C" int mobi_igemm_finish(const mobi_igemm_params* p, void* stream) {
   using namespace mobi;
-  IgemmArgs a;
-  const int rc = igemm_prepare(p, a);
+  IgemmPlan pl;
+  const int rc = igemm_plan(p, pl);
   if (rc != MOBI_OK) return rc;
-  if (!a.split_ws || a.small || a.sync) return MOBI_ERR_ARG;       // nothing was deferred
+  if (!pl.a.split_ws || pl.body == Body::Small || pl.a.sync) return MOBI_ERR_ARG;       // nothing was deferred
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  return p->dtype == MOBI_F16 ? launch_splitk_reduce<f16_t>(a, st) : launch_splitk_reduce<bf16_t>(a, st);
-}
-
-extern "C" int mobi_igemm_kernel_variant(const mobi_igemm_params* p) {
-  mobi::IgemmArgs a;
-  const int rc = igemm_prepare(p, a);
-  if (rc != MOBI_OK) return rc;
-  if (a.small) return MOBI_IGEMM_SMALL;
-  if (a.wide) return a.wide == 2 ? MOBI_IGEMM_RING_256 : MOBI_IGEMM_RING_128W;
-  if (a.wm == 4 && a.fast && a.glds) return a.pp ? MOBI_IGEMM_PINGPONG : MOBI_IGEMM_DIRECT_LDS;
-  if (a.wm == 4) return MOBI_IGEMM_STAGED_256;
-  return a.sm ? MOBI_IGEMM_RING_128 : MOBI_IGEMM_STAGED_128;
+  return p->dtype == MOBI_F16 ? launch_splitk_reduce<f16_t>(pl.a, st) : launch_splitk_reduce<bf16_t>(pl.a, st);
 }

@@ -1,5 +1,5 @@
 // The small-problem form of mobi_igemm's 1 x 1 case (csrc/igemm_small.hip): coalesced loads, a wave-private LDS transposition,
-// k split over the four waves of a block, one fixed-order sum through LDS.  Launched by igemm.hip's plan (`small_tile`).
+// k split over the four waves of a block, one fixed-order sum through LDS.  Launched by igemm.hip where the plan says so (`small_tile`, igemm_plan.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -5,8 +5,8 @@ list covers what it promises (`missing`).
 
 A body is forced with the A/B environment of csrc/tuning.hip:
   staged128   SM=0 WM=2 WIDE=0            igemm_kernel<.., WM 2>
-  staged256   WM=4 WIDE=0 PP=0            igemm_kernel<.., WM 4> (reported as direct_lds where C % 64 == 0: the library
-                                          has no direct-to-LDS kernel and runs the register-staged one)
+  staged256   WM=4 WIDE=0 PP=0            igemm_kernel<.., WM 4> (Body::Staged256; reported as direct_lds where C % 64 == 0:
+                                          mobi_engine.h says why)
   pingpong    WM=4 WIDE=0                 igemm_pp_kernel (eligible shapes only)
   ring256s    WM=4 WIDE=2 RING_DIRECT=0       igemm_ring_kernel<.., 8, 8>, LDS-staged epilogue
   ring256r    WM=4 WIDE=2 RING_DIRECT=1       the same, register epilogue where it applies
@@ -191,7 +191,7 @@ def build():
     add("ring128w", "slab.split2", Case(8, 4, 4, 64, 256, split_k=2, residual="dense", **C3))
     add("ring64", "slab.split2.f32", Case(8, 4, 4, 64, 128, split_k=2, out_mode="f32", **C3))
     # the in-launch finish in its same-XCD form (MOBI_IGEMM_FUSED_SPLIT 2, the default) needs a tile count that is a multiple
-    # of 8 (igemm_prepare: `mode == 1 || tiles % 8 == 0`): 4 x 2 tiles of 128 x 128 / 160 / 256, 2 x 4 of 256 x 128 / 160 on the
+    # of 8 (in_launch_finish, csrc/igemm_plan.hip: `mode == 1 || tiles % 8 == 0`): 4 x 2 tiles of 128 x 128 / 160 / 256, 2 x 4 of 256 x 128 / 160 on the
     # ping-pong kernel, 4 x 2 of 256 x 256 (M = 1,024: the one shape beyond the suite's usual 600 rows)
     sync8 = Case(8, 8, 8, 64, 256, split_k=2, residual="dense", rowvec=True, **C3)
     add("ring128s", "sync8.split2", sync8)                            # staged slab stores

@@ -1,4 +1,4 @@
-"""The implicit GEMM (mobi_igemm, csrc/igemm.hip + csrc/igemm_small.hip) in plain torch on the CPU: the float64 reference of
+"""The implicit GEMM (mobi_igemm, csrc/igemm.hip + csrc/igemm_plan.hip + csrc/igemm_small.hip) in plain torch on the CPU: the float64 reference of
 the contract in include/mobi_engine.h, the fp32 restatement with the kernels' rounding points, the row / channel measures, the
 a-priori fp32 bound, the operand builder and the launch plan of tests/test_gpu_igemm_rows.py.  Nothing here calls the engine or
 needs a GPU (tests/test_igemm_ref_cpu.py runs it alone); the builder only needs one when asked for device views.
@@ -19,7 +19,7 @@ from oracle import weights as W
 U32 = 2.0 ** -24                        # unit roundoff of fp32
 STAGED_128, STAGED_256, DIRECT_LDS, PINGPONG, RING_128, RING_256, RING_128W, SMALL = range(8)   # MOBI_IGEMM_* (mobi_engine.h)
 BODY_NAMES = ("staged128", "staged256", "direct_lds", "pingpong", "ring128", "ring256", "ring128w", "small")
-COMPUTE_UNITS = 256                     # MI355X (compute_units() of csrc/igemm.hip; also its answer without a device)
+COMPUTE_UNITS = 256                     # MI355X (compute_units() of csrc/igemm_plan.hip; also its answer without a device)
 LN_EPS = 1e-5
 
 
@@ -273,7 +273,7 @@ def f32_bound(case, o):
 
 
 def split_ranges(case, split_k):
-    """k ranges of a split launch, igemm_prepare: nk = ceil(k / 64) tiles, nk_per = ceil(nk / split_k) per range, ranges
+    """k ranges of a split launch, split_ranges of csrc/igemm_plan.hip: nk = ceil(k / 64) tiles, nk_per = ceil(nk / split_k) per range, ranges
     never empty ('a.splits = (a.nk + a.nk_per - 1) / a.nk_per')."""
     nk = (case.ktot + 63) // 64
     per = (nk + split_k - 1) // split_k
@@ -469,7 +469,7 @@ def _exact_log2(v):
 
 
 def _small_tile(case, t, split_k):
-    """small_tile of csrc/igemm.hip."""
+    """small_tile of csrc/igemm_plan.hip."""
     if t("SMALL") == 0:
         return 0
     if t("SMALL") < 0 and (t("WM") in (2, 4) or t("WIDE") >= 0 or t("SM") == 0):
@@ -494,8 +494,8 @@ def _small_tile(case, t, split_k):
 
 def plan(case, knobs=None, cu=COMPUTE_UNITS):
     """The body (MOBI_IGEMM_*) and the sub-forms a launch of `case` takes under the MOBI_IGEMM_* environment `knobs`
-    ({'WM': 2, ...}, unset = -1): a restatement of the predicates of igemm_prepare (csrc/igemm.hip; the comments
-    below quote the line each one restates) and the instantiation launch_igemm picks, for operands far below 2 GB and
+    ({'WM': 2, ...}, unset = -1): a restatement of the predicates of igemm_plan (csrc/igemm_plan.hip: pixel_waves,
+    wide_tiles, route; the comments below quote the line each one restates) and the instantiation launch_igemm (csrc/igemm.hip) picks, for operands far below 2 GB and
     tap-major k (the only order there is).  The GPU test asserts `body` against mobi_igemm_kernel_variant; nothing in the library reports the other fields
     (sm64, sm_direct, ring_direct, epi_direct / pp, in-launch finish, w_tiled, the kernel symbol): they are a restated claim,
     only as good as this reading of the code."""
@@ -510,7 +510,7 @@ def plan(case, knobs=None, cu=COMPUTE_UNITS):
     nk = (case.ktot + 63) // 64
     bn = 160 if npk % 160 == 0 else 128
     up = lambda a, b: (a + b - 1) // b
-    tiles256 = up(M, 256) * up(npk, bn)                                 # `const long long tiles256 =` .. `a.wm = tuning().wm`
+    tiles256 = up(M, 256) * up(npk, bn)                                 # pixel_waves: `const long long tiles256 =` .. `wm = tuning().wm`
     wm = 4 if tiles256 >= 256 else 2
     if split_k and M % 256 == 0 and tiles256 * split_k >= 256 and nk // split_k >= 16:
         wm = 4
@@ -519,9 +519,9 @@ def plan(case, knobs=None, cu=COMPUTE_UNITS):
     if t("WM") in (2, 4):
         wm = t("WM")
     tiles_m, tiles_n = up(M, 64 * wm), up(npk, bn)
-    fast = C % 64 == 0 and (case.c1 == 0 or case.c0 % 64 == 0) and t("FAST") != 0        # `a.fast =` (extents < 2 GB here)
+    fast = C % 64 == 0 and (case.c1 == 0 or case.c0 % 64 == 0) and t("FAST") != 0        # `const bool fast =` (extents < 2 GB here)
     glds = t("GLDS") != 0
-    sm = wm == 2 and t("SM") != 0                                       # `a.sm = a.wm == 2 && ring_ok` (small operands)
+    sm = wm == 2 and t("SM") != 0                                       # `g.ring_ok && t.sm != 0 ? Body::Ring128` (small operands)
     splits, nk_per = 1, nk
     if split_k:                                                         # `if (p->split_k > 1) {`
         nk_per = up(nk, split_k)
@@ -529,16 +529,16 @@ def plan(case, knobs=None, cu=COMPUTE_UNITS):
     split_ws = bool(split_k)
     vec_ok = lambda mult: not rowvec or (not bias and hw % mult == 0)
     epi_direct = (wm == 4 and fast and glds and rows and not split_ws and vec_ok(64) and M % 256 == 0 and npk % bn == 0 and
-                  nk_per >= 3 and t("EPI_DIRECT") != 0)                 # `a.epi_direct =`
+                  nk_per >= 3 and t("EPI_DIRECT") != 0)                 # `const bool epi_direct =`
     shifts = _exact_log2(hw) >= 6 and _exact_log2(case.wo) >= 0
-    pp = epi_direct and splits == 1 and case.scale == 1.0 and shifts    # `a.pp = a.epi_direct &&`
+    pp = epi_direct and splits == 1 and case.scale == 1.0 and shifts    # `const bool pp =`, the form without a split
     if split_ws and wm == 4 and fast and glds and not tr and M % 256 == 0 and npk % bn == 0 and nk_per >= 3 and \
-            case.scale == 1.0 and shifts:                               # `if (a.split_ws && a.wm == 4 && a.fast`
+            case.scale == 1.0 and shifts:                               # `const bool pp =`, `split ? pp_tiles && !tr`
         pp = True
     if t("PP") == 0:
         pp = False
     wide = 0
-    if (wm == 4 or t("WIDE") > 0) and t("WIDE") != 0:                   # `if ((a.wm == 4 || tuning().wide > 0) && ring_ok`
+    if (wm == 4 or t("WIDE") > 0) and t("WIDE") != 0:                   # wide_tiles: `if (!((wm == 4 || knob > 0) && g.ring_ok`
         bnw = 320 if npk % 160 == 0 else 256
         tn = up(npk, bnw)
 
@@ -557,7 +557,7 @@ def plan(case, knobs=None, cu=COMPUTE_UNITS):
             wide, wm, sm = pick, (4 if pick == 2 else 2), False
             tiles_m, tiles_n = up(M, 64 * wm), tn
     k64 = C % 64 == 0 and (case.c1 == 0 or case.c0 % 64 == 0)
-    sm64 = sm and k64 and nk_per >= 1 and tiles_m * tiles_n * splits * case.groups <= cu and t("SM64") != 0     # `a.sm64 =`
+    sm64 = sm and k64 and nk_per >= 1 and tiles_m * tiles_n * splits * case.groups <= cu and t("SM64") != 0     # `body = Body::Ring64`
     if t("SM64") == 1 and sm and k64:
         sm64 = True
     dense_groups = case.groups == 1 or case.w_gap == 0
@@ -576,10 +576,10 @@ def plan(case, knobs=None, cu=COMPUTE_UNITS):
         else:
             wide, wm, sm, tiles_m, tiles_n = 0, 2, True, up(M, 128), up(npk, bn)
         w_tiled = tileable
-    small = 0 if lnf or leaky else _small_tile(case, t, split_k)        # `a.small =`
+    small = 0 if lnf or leaky else _small_tile(case, t, split_k)        # `const int small =`
     pp_launch = not wide and wm == 4 and fast and glds and pp
     sync_mode = 0
-    if split_ws and case.finish == "sync" and not small and t("FUSED_SPLIT") != 0 and splits <= 4:                # `if (a.split_ws && p->sync && !a.small`
+    if split_ws and case.finish == "sync" and not small and t("FUSED_SPLIT") != 0 and splits <= 4:                # `if (split && p->sync && !small`, in_launch_finish
         mode = 1 if t("FUSED_SPLIT") == 1 else 2
         tiles = tiles_m * tiles_n
         if ((wide or sm) or (pp_launch and tiles <= cu)) and (mode == 1 or tiles % 8 == 0):

@@ -8,7 +8,7 @@ The body cases go through the C ABI (_lib.IgemmParams): each operand is a view i
 strides beyond dense, a gap between per-group weight matrices, defer_finish + mobi_igemm_finish and the refusals, which
 ops.igemm cannot all express; one path keeps the cases uniform.  test_wrapper_derives_strides_and_pointers runs the forms
 the wrapper can express through ops.igemm on the same NaN-surrounded views.  Which launches of test_split_forms_are_bit_identical
-finish inside the launch is igemm_ref.plan's reading of igemm_prepare (the library does not report it); the sync8.* cases are
+finish inside the launch is igemm_ref.plan's reading of igemm_plan (the library does not report it); the sync8.* cases are
 built so that both modes do, and the test refuses a fall-back for them.
 
 Criteria, for every launch (a test collects every case's figures before it fails):
@@ -186,7 +186,7 @@ def test_split_forms_are_bit_identical(lib, tune, dtype):
         for mode in (1, 2):
             set_knobs(tune, dict(knobs, FUSED_SPLIT=mode))
             assert L.variant() == L.plan["body"], cid
-            # whether the launch finishes itself is plan()'s reading of igemm_prepare (mode 2 needs tiles % 8 == 0, both need
+            # whether the launch finishes itself is plan()'s reading of igemm_plan (mode 2 needs tiles % 8 == 0, both need
             # <= 4 slabs); the cases built for it (sync8.*) must get the mode asked for, a fall-back to the reduce launch
             # would compare that launch with itself
             taken = IC.in_launch_mode(case, knobs, mode)
@@ -328,7 +328,7 @@ def _query(lib, case, **fields):
 
 
 def test_refusals(lib, tune):
-    """One case per `return MOBI_ERR_*` of igemm_prepare that arguments alone can reach (csrc/igemm.hip); no launch."""
+    """One case per `return MOBI_ERR_*` of igemm_plan that arguments alone can reach (csrc/igemm_plan.hip); no launch."""
     set_knobs(tune, {})
     base = Case(2, 4, 4, 64, 136, kh=3, kw=3, pad_h=1, pad_w=1)
     split = dataclasses.replace(base, split_k=2)
